@@ -10,6 +10,12 @@ checkpoints offline), text embeddings synthetic N(0,1).
 
   python bench.py [--gpus N --steps K --warmup W] [--frames 16 --size 512 --lora-rank 8 --lora-mode fused]
 N>1 (torch.distributed.run, one rank per GPU): see --parallel.  Rank 0 prints ONE JSON line.
+
+A plain run only sets up, warms up, times the K steps and prints the line (the records below stay null).  --full adds
+the records that take runs of their own: the instrumented step's roofline / per-kernel table, the MFMA / HBM ceiling
+probes, the VAE decode, the CPU baseline and, at N>1, the bitwise shard preflight and the sub-records (each still has
+its --no-* switch).  --dump-outputs DIR writes what the last timed step left (the latents; --train: the tensors
+the step returns and the trainable parameters) as DIR/<name>.npy, float32.
 """
 from __future__ import annotations
 
@@ -74,6 +80,12 @@ def parse():
                          "(default: the CFG pair in two halves whose all-to-alls overlap the other half's compute)")
     ap.add_argument("--configs3-frames", type=int, default=32)
     ap.add_argument("--configs3-size", type=int, default=768)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: roofline / per-kernel table, ceiling "
+                         "probes, VAE decode record, CPU baseline, and at N>1 the shard preflight and the sub-records")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the timed path produced in its last step as "
+                         "DIR/<name>.npy (float32; at most 64 MB in all, larger arrays as a fixed seeded sample)")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
@@ -93,6 +105,30 @@ def parse():
                     help="--train: one forward / backward per clip (the reference's loop shape) instead of the whole "
                          "accumulation window batched (TrainStep.window; same gradient)")
     return ap.parse_args()
+
+
+DUMP_BUDGET_BYTES = 64 * 2 ** 20
+
+
+def snapshot_outputs(tensors):
+    """Host float32 copies of the timed path's outputs, taken right after the timed steps (later records run more
+    steps on the same buffers)."""
+    return {k: v.detach().to("cpu", torch.float32).contiguous().clone() for k, v in tensors.items()}
+
+
+def dump_outputs(dirname, arrays, rank=0, world=1):
+    """arrays (name -> host float32 tensor) as dirname/<name>.npy (<name>_rank<r>.npy at N>1).  Every array gets an
+    equal share of the 64 MB budget; a larger one is written as a fixed sample of its flattened elements (indices
+    drawn once from numpy's default_rng(0), sorted), the same from run to run."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays) * world) // 4  # float32 elements per file
+    for name, t in arrays.items():
+        a = t.numpy().astype(np.float32, copy=False)
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=share, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), a)
 
 
 def _lib_md5():
@@ -526,8 +562,12 @@ def bench_train(args, world, rank, local, dev):
     value = args.frames * args.grad_accum * world / (ms_step * 1e-3)
     ok = bool(torch.isfinite(out["loss"]).item())
     lr_now = float(opt.param_groups[0]["lr"])
+    if args.dump_outputs:
+        res = {k: v.reshape(-1) for k, v in out.items() if torch.is_tensor(v)}
+        res["trainable_params"] = torch.cat([p.detach().reshape(-1).float() for p in params])
+        dump_outputs(args.dump_outputs, snapshot_outputs(res), rank, world)
     rl = table = step_rl = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # one instrumented eager step (HIP events around every launch on its stream), enqueued behind a busy kernel
         lat_e = lat if vae is None else encode_frames(vae, frames, vgen)
         torch.cuda.synchronize()
@@ -544,7 +584,7 @@ def bench_train(args, world, rank, local, dev):
         step_rl = {"alg_tflop": round(fl / 1e12, 2), "achieved_tflops": round(fl / (ms_step * 1e-3) / 1e12, 1),
                    "frac": round(fl / (ms_step * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4)}
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         del step, opt, unet
         torch.cuda.empty_cache()
         cpu = train_cpu_baseline(args, cfg)
@@ -611,8 +651,10 @@ def main():
                          nclips=nclips, sharded=sharded)
     den, ms_step, value = head["den"], head["ms_per_step"], head["value"]
     ok = bool(torch.isfinite(den.lat).all().item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, snapshot_outputs({"latents": den.lat}), rank, world)
 
-    rl, table = (None, None) if args.no_roofline else roofline(den, ms_step)
+    rl, table = roofline(den, ms_step) if args.full and not args.no_roofline else (None, None)
     step = None
     if rl is not None:
         # whole denoise step against the chip: algorithmic flops of every launch (table in DESIGN.md 3) per
@@ -624,7 +666,7 @@ def main():
             rl["peak_measured"] = measured_peaks(dev, rl)
             step["frac_of_measured"] = round(step["achieved_tflops"] / rl["peak_measured"]["mfma_bf16_tflops"], 4)
     graphed = den.graph is not None
-    vae_rec = None if args.no_vae else vae_decode_timing(args, den, dev, ms_step)
+    vae_rec = vae_decode_timing(args, den, dev, ms_step) if args.full and not args.no_vae else None
     den.graph = None  # (piecewise graphs hold no collective; released before the next run's memory)
     del den, head["den"]
     torch.cuda.empty_cache()
@@ -633,7 +675,7 @@ def main():
     # N ways (strong scaling) and, on 8 GPUs, BASELINE configs[3] (one 32 x 768^2 clip, 4 frames per GPU); each runs
     # its own bitwise preflight, piecewise capture and timing with the same --steps / --warmup
     subs = {}
-    if sharded and world > 1:
+    if sharded and world > 1 and args.full:
         want_strong = args.strong_record == "on" or (args.strong_record == "auto" and nclips != 1)
         want_c3 = args.configs3 == "on" or (args.configs3 == "auto" and world == 8)
         plans = []
@@ -668,7 +710,7 @@ def main():
             del r
             torch.cuda.empty_cache()
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         del unet
         torch.cuda.empty_cache()
         cpu = cpu_baseline(args, cfg)
@@ -707,8 +749,9 @@ def main():
 
 def timed_denoise(args, unet, cfg, world, rank, dev, rehearsal, *, frames, size, nclips, sharded, exchange=None):
     """One denoiser of `nclips` clips of `frames` x size^2 (frame-sharded over the ranks when `sharded`): preflight
-    (sharded), capture (one HIP graph; piecewise at N > 1), --warmup untimed and --steps timed replays bracketed by
-    barrier + synchronize, the max over ranks.  Returns the denoiser (for the roofline / VAE records) and the timing."""
+    (sharded, --full), capture (one HIP graph; piecewise at N > 1), --warmup untimed and --steps timed replays
+    bracketed by barrier + synchronize, the max over ranks.  Returns the denoiser (for the roofline / VAE records) and
+    the timing."""
     from video_style_transfer_amd.pipeline import AnimateDiffDenoiser
     shard = None
     if sharded:
@@ -723,7 +766,7 @@ def timed_denoise(args, unet, cfg, world, rank, dev, rehearsal, *, frames, size,
     den.set_prompt_embeds(enc[1:], pooled[1:], enc[:1], pooled[:1])
     den.init_latents(seed=42 + seed_rank)
     graph_note = None
-    preflight = shard_preflight(den, unet, world, rank) if shard is not None else None
+    preflight = shard_preflight(den, unet, world, rank) if shard is not None and args.full else None
     if not args.no_graph:
         # N = 1: one HIP graph per step; a step that cannot be captured fails the run.  Frame-sharded N > 1: the step
         # is captured piecewise (frame_shard.PiecewiseGraph: the graphs split at the collectives, which run between

@@ -29,9 +29,9 @@ def test_bench_two_rank_frame_shard_rehearsal():
         pytest.skip("no HIP device")
     env = dict(os.environ, VST_BENCH_REHEARSAL="gloo", OMP_NUM_THREADS="4")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-           "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps",
-           "1", "--warmup", "0", "--frames", "16", "--size", "256", "--no-cpu-baseline", "--no-vae", "--no-roofline",
-           "--configs3", "on", "--configs3-frames", "8", "--configs3-size", "256"]
+           "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full",
+           "--steps", "1", "--warmup", "0", "--frames", "16", "--size", "256", "--no-cpu-baseline", "--no-vae",
+           "--no-roofline", "--configs3", "on", "--configs3-frames", "8", "--configs3-size", "256"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]

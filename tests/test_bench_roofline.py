@@ -30,3 +30,22 @@ def test_roofline_bounds_per_shape():
     assert qkv["bound"] == "mfma" and abs(qkv["frac"] - fl2 / 80e-6 / 2.5e15) < 1e-3
     assert "8192x1280x1312 xattn" in v
     assert set(table) == {"gemm_p8<256x192,lora>", "gemm_p8<256x256,lora>", "gemm_p8<256x192,lora,xattn>"}
+
+
+def test_dump_outputs_float32_and_budget(tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy per array, whole when it fits its share of the budget, otherwise the same sorted
+    sample of its flattened elements on every run."""
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(0)
+    small, big = torch.randn(2, 3, 5, generator=g, dtype=torch.float64), torch.randn(1000, generator=g)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 2 * 4 * 100)  # 100 float32 elements per array
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), bench.snapshot_outputs({"small": small, "big": big}))
+    a_small, a_big = np.load(tmp_path / "a" / "small.npy"), np.load(tmp_path / "a" / "big.npy")
+    assert a_small.dtype == np.float32 and a_small.shape == (2, 3, 5)
+    assert np.array_equal(a_small, small.float().numpy())
+    assert a_big.dtype == np.float32 and a_big.shape == (100,)
+    idx = np.sort(np.random.default_rng(0).choice(1000, size=100, replace=False))
+    assert np.array_equal(a_big, big.numpy()[idx])
+    assert np.array_equal(a_big, np.load(tmp_path / "b" / "big.npy"))

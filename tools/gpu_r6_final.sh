@@ -16,11 +16,11 @@ run 300 r6f_pmc_fetch.log rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-for
 run 300 r6f_pmc_write.log rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_write -o pmc -- python -u bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-vae --no-peaks --no-roofline
 python tools/pmc_traffic.py gpurun_out/pmc_fetch gpurun_out/pmc_write gpurun_out/pmc_so.md5 > gpurun_out/pmc_traffic_r6.json && cp gpurun_out/pmc_traffic_r6.json profiles/ && echo "[step] pmc json ok"
 rm -rf gpurun_out/pmc_fetch gpurun_out/pmc_write
-run 420 r6f_bench.json python -u bench.py
+run 420 r6f_bench.json python -u bench.py --full
 tail -c 400 gpurun_out/r6f_bench.json
 run 400 r6f_rocprof.log rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/r6f_prof -o r6f -- python -u bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-vae --no-peaks
 mkdir -p gpurun_out/r6f_keep
 for f in $(find gpurun_out/r6f_prof -name "*kernel_stats.csv"); do cp $f gpurun_out/r6f_keep/; done
 rm -rf gpurun_out/r6f_prof
-run 400 r6f_bench_train.json python -u bench.py --train --no-cpu-baseline
+run 400 r6f_bench_train.json python -u bench.py --train --full --no-cpu-baseline
 tail -c 300 gpurun_out/r6f_bench_train.json

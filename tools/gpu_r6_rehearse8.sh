@@ -6,7 +6,7 @@ mkdir -p gpurun_out
 export VST_BENCH_REHEARSAL=gloo OMP_NUM_THREADS=2 PYTHONUNBUFFERED=1
 EXTRA=${1:---strong-record off --gather-record off --configs3 off}
 timeout -k 10 1000 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
-  --master-port 29611 bench.py --gpus 8 --steps 1 --warmup 0 --no-cpu-baseline --no-vae --no-roofline $EXTRA \
+  --master-port 29611 bench.py --gpus 8 --full --steps 1 --warmup 0 --no-cpu-baseline --no-vae --no-roofline $EXTRA \
   > gpurun_out/r6_rehearse8.log 2>&1 &
 pid=$!
 while kill -0 $pid 2>/dev/null; do
