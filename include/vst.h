@@ -11,6 +11,21 @@
  *   - `stream` is a hipStream_t; every call is asynchronous on it and graph-capturable;
  *   - return 0 (VST_OK) on success, 1 for a bad argument, 2 for a launch failure, 3 for a
  *     supported-shape refusal (vst_gemm_lora, vst_gemm_cross_attention).
+ *
+ * View contract (tests/test_view_contract_gpu.py holds every entry point to it):
+ *   - a matrix operand that comes with a row stride (lda, ldw, ldr, ldc, ldq, ldkv, ldo, ldx, ldy, ...) may be
+ *     any row-major view: the stride is in ELEMENTS, at least the row width and a multiple of 8 (ld_row_bias and
+ *     vst_gemm_tn's ldc: a multiple of 4); the columns between the width and the stride belong to the
+ *     caller and are neither read into a result nor written;
+ *   - the base pointer of every bf16 operand is 16-byte aligned (the loaders and epilogues move 16-byte chunks),
+ *     and so are fp32 vectors read as float4 (bias, row_bias, gamma, beta, pe, lse).  Bases at smaller offsets
+ *     are outside the contract; only vst_gemm_tn checks its output pointer (8 bytes) and refuses;
+ *   - operands WITHOUT a row stride in their signature are contiguous: conv inputs x1 / x2 ([nimg*H*W][C]) and
+ *     conv weights ([Cout][9*(C1+C2)], rows padded to 8), bias / gamma / beta / pe / table, lse, colstat and
+ *     GroupNorm partials, every workspace, vst_permute_rows / vst_silu / vst_add / vst_quick_gelu operands,
+ *     vst_gemm_f32out's C, vst_colsum's y, the dgamma / dbeta vectors, the fp32 NCHW / latent tensors;
+ *   - an output is written exactly on [rows) x [cols) of its view and nowhere else: no guard row or column is
+ *     touched, and every element of the view is written by every call.
  */
 #ifndef VST_H
 #define VST_H

@@ -40,6 +40,93 @@ def test_bad_arguments_rejected_without_gpu():
                                          0.125, 1, None) == 1  # no lse
 
 
+def test_gemm_tn_refuses_misaligned_output_without_gpu():
+    """vst_gemm_tn stores 8 bytes (4 bf16) at C + n * ldc + k: an output base that is not 8-byte aligned (a view at an
+    odd column of a buffer) is refused with VST_ERR_ARG before any launch, like the strides and widths it already
+    checks."""
+    from video_style_transfer_amd import _lib
+    lib = _lib.load()
+    A, B, C = 4096, 8192, 16384  # never dereferenced: every call below is refused on the host
+    for off in (2, 4, 6, 10):
+        assert lib.vst_gemm_tn(A, 8, B, 8, 64, 8, 8, C + off, 8, None, 0, None) == 1, off
+    assert lib.vst_gemm_tn(A, 8, B, 8, 64, 8, 8, C, 6, None, 0, None) == 1       # ldc % 4
+    assert lib.vst_gemm_tn(A, 8, B, 8, 64, 8, 8, None, 8, None, 0, None) == 1    # no output
+
+
+def test_wrote_drops_colstat_of_overlapping_views():
+    """kernels._wrote (called for every out= a wrapper hands to a kernel) drops the GroupNorm column statistics of
+    every registered tensor that shares storage bytes with the written view: a launch into out=t[4:] overwrites rows
+    of t, whose entry is keyed by t.data_ptr(), not by the view's.  Writes to other storage, or to bytes of the same
+    storage that t does not cover, leave the entry alone."""
+    import weakref
+    from video_style_transfer_amd import kernels as K
+    K.colstat_reset()
+    cs = torch.zeros(1, 64, 2)
+
+    def register(t):
+        K._COLSTAT[t.data_ptr()] = (weakref.ref(t), t._version, cs)
+
+    t = torch.zeros(8, 64, dtype=torch.bfloat16)
+    register(t)
+    K._wrote(t[4:])
+    assert K.colstat_of(t) is None
+    register(t)
+    K._wrote(t[2:3, 8:16])                                   # a block inside t
+    assert K.colstat_of(t) is None
+    register(t)
+    K._wrote(torch.zeros(8, 64, dtype=torch.bfloat16))       # a disjoint tensor
+    assert K.colstat_of(t) is cs
+    K._wrote(None)
+    assert K.colstat_of(t) is cs
+    # the registered tensor is itself a view: writes to its neighbours in the same storage do not touch it ...
+    big = torch.zeros(24, 64, dtype=torch.bfloat16)
+    mid = big[8:16]
+    K.colstat_reset()
+    register(mid)
+    K._wrote(big[:8])
+    K._wrote(big[16:])
+    assert K.colstat_of(mid) is cs
+    K._wrote(big[15:17])                                     # ... one that reaches into its last row does
+    assert K.colstat_of(mid) is None
+    register(mid)
+    K._wrote(big.view(torch.int16)[0:9])                     # (another dtype over the same bytes)
+    assert K.colstat_of(mid) is None
+    # an entry whose tensor died is dropped on the way
+    dead = torch.zeros(8, 64, dtype=torch.bfloat16)
+    register(dead)
+    key = dead.data_ptr()
+    del dead
+    K._wrote(t)
+    assert key not in K._COLSTAT
+    K.colstat_reset()
+
+
+def test_out_validation_is_host_side():
+    """Every wrapper validates out= before it touches the library: a wrong dtype, width, rank or column stride raises
+    VstError naming the argument (here on CPU tensors, so the device check fires first for those; the shape / dtype
+    checks of kernels._out are exercised directly)."""
+    from video_style_transfer_amd import kernels as K
+
+    class FakeCuda(torch.Tensor):  # a CPU tensor that claims to be on the device: _out never launches anything
+        @property
+        def is_cuda(self):
+            return True
+
+    def fake(*shape, dtype=torch.bfloat16):
+        return torch.zeros(*shape, dtype=dtype).as_subclass(FakeCuda)
+
+    K._out(fake(6, 16), (6, 16), torch.bfloat16, "out", "op")
+    K._out(fake(6, 32)[:, 8:24], (6, 16), torch.bfloat16, "out", "op")   # a column view is fine
+    for bad, what in ((fake(6, 16, dtype=torch.float32), "expected"), (fake(6, 8), "shape"), (fake(5, 16), "shape"),
+                      (fake(6 * 16), "2-D"), (fake(16, 6).t(), "2-D"), (fake(6, 32)[:, ::2], "2-D"),
+                      (torch.zeros(6, 16, dtype=torch.bfloat16), "device")):
+        with pytest.raises(K._lib.VstError, match=f"op: out .*{what}"):
+            K._out(bad, (6, 16), torch.bfloat16, "out", "op")
+    with pytest.raises(K._lib.VstError, match="op: out must be contiguous"):
+        K._out_flat(fake(6, 32)[:, :16], (6, 16), torch.bfloat16, "out", "op")
+    K._out_flat(fake(6, 16), (6, 16), torch.bfloat16, "out", "op")
+
+
 def test_gemm_lora_policy_without_gpu():
     """vst_gemm_lora_supported (host policy, no launch): the SDXL UnZipLoRA r=8 projections run the down-projection
     inside the 8-phase GEMM, whatever M is (whether the in-GEMM path is taken is shape-only, so a frame-sharded rank

@@ -165,10 +165,15 @@ extern "C" int vst_gemm_tn(const void* A, int lda, const void* B, int ldb, int M
                            void* workspace, size_t ws_bytes, void* stream) {
   if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0) return VST_ERR_ARG;
   if ((N & 7) || (K & 7) || (lda & 7) || (ldb & 7) || (ldc & 3) || lda < N || ldb < K || ldc < K) return VST_ERR_ARG;
+  // the epilogues store 8 bytes (4 bf16) at C + n * ldc + k with k % 4 == 0: with ldc % 4 == 0 every store is aligned
+  // exactly when the base is
+  if ((uintptr_t)C & 7) return VST_ERR_ARG;
   Fit31 fit;
   const uint32_t ab = fit(((size_t)(M - 1) * lda + N) * 2);
   const uint32_t bb = fit(((size_t)(M - 1) * ldb + K) * 2);
-  if (fit.over) return VST_ERR_ARG;  // past the 32-bit buffer offsets: refuse (the caller splits the tokens)
+  // past the 32-bit buffer offsets: refused.  Nothing here or in kernels.linear_tn splits the tokens of such a call
+  // (the partial sums of two calls would have to be added in fp32 to keep the result's rounding).
+  if (fit.over) return VST_ERR_ARG;
   const int splits = tn_splits(M, N, K);
   const size_t need = splits > 1 ? (size_t)splits * N * K * sizeof(float) : 0;
   if (need && (!workspace || ws_bytes < need)) return VST_ERR_ARG;

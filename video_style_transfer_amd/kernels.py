@@ -142,8 +142,56 @@ def _workspace(device):
 def _wrote(t):
     """A launch is about to write t through a raw pointer (which does not bump t._version): drop any GroupNorm column
     statistics registered for its storage (colstat_of), so they are never read for overwritten data."""
-    if _COLSTAT and t is not None:
-        _COLSTAT.pop(t.data_ptr(), None)
+    if not _COLSTAT or t is None:
+        return
+    # every entry whose registered tensor shares bytes with the written view goes, not only the one registered at the
+    # view's own data_ptr(): a write into out=t[rows:] overwrites part of t, whose entry sits at t.data_ptr()
+    sp = _span(t)
+    for key, e in list(_COLSTAT.items()):
+        base = e[0]()
+        if base is None:
+            del _COLSTAT[key]
+            continue
+        sb = _span(base)
+        if sb[0] == sp[0] and sb[1] < sp[2] and sp[1] < sb[2]:
+            del _COLSTAT[key]
+
+
+def _span(t):
+    """(storage pointer, first byte, one past the last byte) of the storage bytes the view t can touch."""
+    st = t.untyped_storage().data_ptr()
+    lo = t.storage_offset() * t.element_size()
+    if t.numel() == 0:
+        return st, lo, lo
+    last = sum((n - 1) * s for n, s in zip(t.shape, t.stride()))
+    return st, lo, lo + (last + 1) * t.element_size()
+
+
+def _out(t, shape, dtype, name, fn):
+    """Validate an output view before a launch writes it through its raw pointer: on the device, the expected dtype,
+    2-D with unit column stride, exactly `shape`.  A kernel given anything else writes outside the view."""
+    _wrote(t)
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _lib.VstError(f"{fn}: {name} must be a device tensor; the HIP path has no CPU fallback")
+    if t.dtype != dtype:
+        raise _lib.VstError(f"{fn}: {name} expected {dtype}, got {t.dtype}")
+    if t.dim() != 2 or t.stride(1) != 1:
+        raise _lib.VstError(f"{fn}: {name} expected a 2-D row-major view, got shape {tuple(t.shape)} stride "
+                            f"{t.stride()}")
+    if tuple(t.shape) != tuple(shape):
+        raise _lib.VstError(f"{fn}: {name} shape {tuple(t.shape)} != {tuple(shape)}")
+    return t
+
+
+def _out_flat(t, shape, dtype, name, fn):
+    """Validate an output the kernel addresses as one contiguous block (no row stride in its ABI)."""
+    _wrote(t)
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _lib.VstError(f"{fn}: {name} must be a device tensor; the HIP path has no CPU fallback")
+    if t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise _lib.VstError(f"{fn}: {name} must be contiguous {dtype} {tuple(shape)}, got {t.dtype} "
+                            f"{tuple(t.shape)} stride {t.stride()}")
+    return t
 
 
 def _dev(t: torch.Tensor, dtype, name):
@@ -187,9 +235,7 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None = None, *
     n_out = N // 2 if geglu else N
     if out is None:
         out = torch.empty((M, n_out), dtype=BF16, device=x.device)
-    _dev(out, BF16, "out")
-    if out.shape != (M, n_out):
-        raise _lib.VstError(f"linear: out shape {tuple(out.shape)} != {(M, n_out)}")
+    _out(out, (M, n_out), BF16, "out", "linear")
     if bias is not None and (bias.dtype != F32 or bias.numel() != N or not bias.is_cuda):
         raise _lib.VstError("linear: bias must be fp32 [N] on device")
     if residual is not None:
@@ -199,6 +245,14 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None = None, *
     if row_bias is not None:
         if row_bias.dtype != F32 or not row_bias.is_cuda or row_bias.shape[-1] != N:
             raise _lib.VstError("linear: row_bias must be fp32 [M/div, N]")
+        if row_bias.dim() == 2 and row_bias.shape[0] > 1 and (row_bias.stride(1) != 1 or row_bias.stride(0) % 4
+                                                              or row_bias.data_ptr() % 16):
+            raise _lib.VstError("linear: row_bias view needs unit column stride, a row stride that is a multiple of "
+                                "4 and a 16-byte aligned base")
+        if row_bias.dim() != 2 and not row_bias.is_contiguous():
+            raise _lib.VstError("linear: row_bias must be a 2-D view or contiguous")
+        if row_bias_div <= 0 or (M - 1) // row_bias_div >= row_bias.numel() // N:
+            raise _lib.VstError(f"linear: row_bias has {row_bias.numel() // N} rows, M={M} div={row_bias_div}")
     # algorithmic work: the LoRA columns count only their real rank (alg_k2), not the zero padding
     k_alg = K1 + (0 if x2 is None else (x2.shape[1] if alg_k2 is None else alg_k2))
     kind = kind or ("gemm_geglu" if geglu else ("gemm_lora" if x2 is not None and alg_k2 is not None else "gemm"))
@@ -207,7 +261,8 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None = None, *
               lambda: gemm_kernel_name(M, N, K, 1 if geglu else 0), (M, N, K)):
         ws = _workspace(x.device)
         _lib.call("vst_gemm_ex", _p(x), _ld(x), _p(x2), 0 if x2 is None else _ld(x2), K1, _p(w), _ld(w), M, N, K,
-                  _p(bias), _p(row_bias), row_bias_div, N if row_bias is not None else 0, _p(residual),
+                  _p(bias), _p(row_bias), row_bias_div,
+                  0 if row_bias is None else (_ld(row_bias) if row_bias.dim() == 2 else N), _p(residual),
                   0 if residual is None else _ld(residual), _p(out), _ld(out), 1 if geglu else (2 if act else 0),
                   GEMM_POLICY["tile"], _splits(), _p(ws), _WS_BYTES, _stream())
     return out
@@ -224,9 +279,7 @@ def linear_tn(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor | None = None)
     K = b.shape[1]
     if out is None:
         out = torch.empty((N, K), dtype=BF16, device=a.device)
-    _dev(out, BF16, "out")
-    if out.shape != (N, K):
-        raise _lib.VstError(f"linear_tn: out shape {tuple(out.shape)} != {(N, K)}")
+    _out(out, (N, K), BF16, "out", "linear_tn")
     wsb = int(_lib.load().vst_gemm_tn_workspace_bytes(M, N, K))
     ws = torch.empty(max(wsb // 4, 1), dtype=F32, device=a.device) if wsb else None
     with _Rec("gemm_tn", 2.0 * M * N * K, 2.0 * (M * N + M * K + N * K), lambda: "gemm_tn", (N, K, M)):
@@ -326,9 +379,7 @@ def linear_lora(x: torch.Tensor, w: torch.Tensor, a: torch.Tensor, group_n: int,
         raise _lib.VstError(f"linear_lora: x {tuple(x.shape)} a {tuple(a.shape)} w {tuple(w.shape)}")
     if out is None:
         out = torch.empty((M, N), dtype=BF16, device=x.device)
-    _dev(out, BF16, "out")
-    if out.shape != (M, N):
-        raise _lib.VstError(f"linear_lora: out shape {tuple(out.shape)} != {(M, N)}")
+    _out(out, (M, N), BF16, "out", "linear_lora")
     if bias is not None and (bias.dtype != F32 or bias.numel() != N or not bias.is_cuda):
         raise _lib.VstError("linear_lora: bias must be fp32 [N] on device")
     if residual is not None:
@@ -393,9 +444,7 @@ def linear_cross_attention(x: torch.Tensor, w: torch.Tensor, a: torch.Tensor | N
         raise _lib.VstError(f"linear_cross_attention: M={M} N={N} K={K} Nq={Nq} Nk={Nk} not fusable")
     if out is None:
         out = torch.empty((M, N), dtype=BF16, device=x.device)
-    _dev(out, BF16, "out")
-    if out.shape != (M, N):
-        raise _lib.VstError(f"linear_cross_attention: out shape {tuple(out.shape)} != {(M, N)}")
+    _out(out, (M, N), BF16, "out", "linear_cross_attention")
     r = P if r_alg is None else r_alg
     flops = 2.0 * M * N * (K + r) + 2.0 * M * K * r + 4.0 * M * N * Nk
     nbytes = 2.0 * (M * K + N * (K + r) + r * K + 2 * (k.shape[0]) * N + M * N)
@@ -462,7 +511,7 @@ def linear_temporal_attention(x: torch.Tensor, w_t: torch.Tensor, b_t: torch.Ten
     C = heads * head_dim
     if out is None:
         out = torch.empty((M, C), dtype=BF16, device=x.device)
-    _dev(out, BF16, "out")
+    _out(out, (M, C), BF16, "out", "linear_temporal_attention")
     flops = 2.0 * M * 3 * C * K + 4.0 * M * F * C
     nbytes = 2.0 * (M * K + 3 * C * K + M * C)
     with _Rec("gemm_tattn", flops, nbytes, lambda: "gemm_p8<256x256,tattn>", (M, N, K)):
@@ -556,11 +605,13 @@ def conv3x3(x1: torch.Tensor, nimg: int, H: int, W: int, w: torch.Tensor, bias: 
     M = nimg * OH * OW
     if out is None:
         out = torch.empty((M, Cout), dtype=BF16, device=x1.device)
-    _wrote(out)
+    _out(out, (M, Cout), BF16, "out", "conv3x3")
     if bias is not None and (bias.dtype != F32 or bias.numel() != Cout):
         raise _lib.VstError("conv3x3: bias must be fp32 [Cout]")
     if residual is not None:
         _dev(residual, BF16, "residual")
+        if residual.shape != (M, Cout):
+            raise _lib.VstError(f"conv3x3: residual shape {tuple(residual.shape)} != {(M, Cout)}")
     if row_bias is not None and (row_bias.dtype != F32 or not row_bias.is_cuda or row_bias.dim() != 2
                                  or row_bias.stride(1) != 1 or row_bias.shape[1] != Cout):
         raise _lib.VstError("conv3x3: row_bias must be an fp32 [nimg/div, Cout] device view with unit column stride")
@@ -598,9 +649,12 @@ def spatial_attention(q, k, v, nbatch, heads, Nq, Nk, kv_div=1, out=None, scale=
         raise _lib.VstError("spatial_attention: k and v must share a row stride")
     if out is None:
         out = torch.empty((nbatch * Nq, heads * 64), dtype=BF16, device=q.device)
-    _dev(out, BF16, "out")
-    if lse is not None and (lse.dtype != F32 or not lse.is_cuda or lse.numel() != nbatch * heads * Nq):
-        raise _lib.VstError("spatial_attention: lse must be fp32 [nbatch*heads*Nq] on device")
+    _out(out, (nbatch * Nq, heads * 64), BF16, "out", "spatial_attention")
+    if lse is not None:
+        _wrote(lse)
+    if lse is not None and (lse.dtype != F32 or not lse.is_cuda or lse.numel() != nbatch * heads * Nq
+                            or not lse.is_contiguous()):
+        raise _lib.VstError("spatial_attention: lse must be contiguous fp32 [nbatch*heads*Nq] on device")
     scale = 0.125 if scale is None else scale
     with _Rec("spatial_attention", 4.0 * nbatch * heads * Nq * Nk * 64,
               2.0 * 64 * heads * (2 * nbatch * Nq + 2 * (nbatch // kv_div) * Nk), None, (nbatch * heads, Nq, Nk)):
@@ -619,7 +673,7 @@ def temporal_attention(q, k, v, nclip, F, HW, heads, head_dim, out=None, scale=N
         raise _lib.VstError("temporal_attention: rows != nclip*F*HW")
     if out is None:
         out = torch.empty((q.shape[0], heads * head_dim), dtype=BF16, device=q.device)
-    _wrote(out)
+    _out(out, (q.shape[0], heads * head_dim), BF16, "out", "temporal_attention")
     scale = head_dim ** -0.5 if scale is None else scale
     T = nclip * F * HW
     with _Rec("temporal_attention", 4.0 * T * F * heads * head_dim, 2.0 * 4 * T * heads * head_dim):
@@ -654,9 +708,7 @@ def motion_attention_block(x, nclip, F, HW, heads, gamma, beta, eps, pe, wqkv, b
         raise _lib.VstError("motion_attention_block: gamma and beta are required")
     if out is None:
         out = torch.empty((T, C), dtype=BF16, device=x.device)
-    _dev(out, BF16, "out")
-    if out.shape != (T, C):
-        raise _lib.VstError(f"motion_attention_block: out shape {tuple(out.shape)} != {(T, C)}")
+    _out(out, (T, C), BF16, "out", "motion_attention_block")
     D = C // heads
     scale = D ** -0.5 if scale is None else scale
     flops = 2.0 * T * C * 4 * C + 4.0 * T * F * C
@@ -679,7 +731,7 @@ def group_norm(x1, nsamples, rows_per_sample, groups, eps, gamma, beta, *, silu=
         raise _lib.VstError("group_norm: rows != nsamples*rows_per_sample")
     if out is None:
         out = torch.empty((x1.shape[0], C), dtype=BF16, device=x1.device)
-    _wrote(out)
+    _out(out, (x1.shape[0], C), BF16, "out", "group_norm")
     ws_bytes = _lib.load().vst_groupnorm_workspace_bytes(nsamples, rows_per_sample, groups, C)
     ws = torch.empty((ws_bytes + 3) // 4, dtype=F32, device=x1.device)
     if colstat is not None:
@@ -740,7 +792,7 @@ def group_norm_apply_partials(x, nclips, frames_local, rows_per_frame, groups, e
                             "[nranks, nclips, frames_local, chunks, groups, 2] on device")
     if out is None:
         out = torch.empty((x.shape[0], C), dtype=BF16, device=x.device)
-    _dev(out, BF16, "out")
+    _out(out, (x.shape[0], C), BF16, "out", "group_norm_apply_partials")
     ss = torch.empty(2 * nclips * C, dtype=F32, device=x.device)
     with _Rec("groupnorm", 0.0, 2.0 * 2 * x.shape[0] * C):
         _lib.call("vst_groupnorm_apply_partials", _p(x), _ld(x), C, nclips, frames_local, rows_per_frame, groups,
@@ -756,7 +808,7 @@ def permute_rows(src, dims, perm, out=None):
         raise _lib.VstError("permute_rows: src must be contiguous with prod(dims) rows")
     if out is None:
         out = torch.empty_like(src)
-    _wrote(out)
+    _out_flat(out, src.shape, BF16, "out", "permute_rows")
     with _Rec("permute", 0.0, 2.0 * 2 * src.numel()):
         _lib.call("vst_permute_rows", _p(src), _p(out), src.shape[1], *dims, *perm, _stream())
     return out
@@ -770,7 +822,7 @@ def add_row_table(x, table, *, div=1, mod=1, out=None):
         raise _lib.VstError("add_row_table: table must be fp32 [>= mod, C] on device")
     if out is None:
         out = torch.empty((rows, C), dtype=BF16, device=x.device)
-    _wrote(out)
+    _out(out, (rows, C), BF16, "out", "add_row_table")
     with _Rec("add_row_table", 0.0, 2.0 * 2 * rows * C):
         _lib.call("vst_add_row_table", _p(x), _ld(x), C, rows, _p(table.contiguous()), div, mod, _p(out), _ld(out),
                   _stream())
@@ -789,7 +841,7 @@ def unpack_tokens(src, out):
     return out
 
 
-def layer_norm_lora(x, gamma, beta, eps, A, *, r_alg=None, out=None):
+def layer_norm_lora(x, gamma, beta, eps, A, *, r_alg=None, out=None, u=None):
     """(LN(x), LN(x) @ A^T) in one pass; A: bf16 [R, C] (R % 16 == 0, <= 64) — LayerNorm + UnZipLoRA down."""
     _dev(x, BF16, "x")
     _dev(A, BF16, "A")
@@ -799,11 +851,13 @@ def layer_norm_lora(x, gamma, beta, eps, A, *, r_alg=None, out=None):
         raise _lib.VstError(f"layer_norm_lora: x {tuple(x.shape)} A {tuple(A.shape)}")
     if out is None:
         out = torch.empty((rows, C), dtype=BF16, device=x.device)
-    _wrote(out)
-    u = torch.empty((rows, R), dtype=BF16, device=x.device)
+    _out(out, (rows, C), BF16, "out", "layer_norm_lora")
+    if u is None:
+        u = torch.empty((rows, R), dtype=BF16, device=x.device)
+    _out(u, (rows, R), BF16, "u", "layer_norm_lora")
     with _Rec("layernorm_lora", 2.0 * rows * C * (r_alg or R), 2.0 * (2 * rows * C + rows * R)):
         _lib.call("vst_layernorm_lora", _p(x), _ld(x), C, rows, _p(gamma), _p(beta), float(eps), _p(A), R, _p(out),
-                  _ld(out), _p(u), R, _stream())
+                  _ld(out), _p(u), _ld(u), _stream())
     return out, u
 
 
@@ -812,7 +866,7 @@ def layer_norm(x, gamma, beta, eps=1e-5, *, pe=None, pe_div=1, pe_mod=1, out=Non
     rows, C = x.shape
     if out is None:
         out = torch.empty((rows, C), dtype=BF16, device=x.device)
-    _wrote(out)
+    _out(out, (rows, C), BF16, "out", "layer_norm")
     with _Rec("layernorm", 0.0, 2.0 * 2 * rows * C):
         _lib.call("vst_layernorm", _p(x), _ld(x), C, rows, _p(gamma), _p(beta), float(eps), _p(pe), pe_div, pe_mod,
                   _p(out), _ld(out), _stream())
@@ -828,16 +882,25 @@ def timestep_embedding(t, n, dim, out, *, col0=0, per_row=1, step_idx=None, flip
     return out
 
 
+def _elementwise(fn, out, *ins):
+    """silu / add address every operand as one flat bf16 block of the first input's size."""
+    _wrote(out)
+    for name, t in (("out", out),) + tuple((f"input {i}", t) for i, t in enumerate(ins)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != BF16 or not t.is_contiguous() \
+                or t.numel() != ins[0].numel():
+            raise _lib.VstError(f"{fn}: {name} must be a contiguous bf16 device tensor of {ins[0].numel()} elements")
+
+
 def silu(x, out=None):
     out = torch.empty_like(x) if out is None else out
-    _wrote(out)
+    _elementwise("silu", out, x)
     _lib.call("vst_silu", _p(x), _p(out), x.numel(), _stream())
     return out
 
 
 def add(a, b, out=None):
     out = torch.empty_like(a) if out is None else out
-    _wrote(out)
+    _elementwise("add", out, a, b)
     _lib.call("vst_add", _p(a), _p(b), _p(out), a.numel(), _stream())
     return out
 
@@ -848,7 +911,7 @@ def transpose(x, out=None):
     rows, cols = x.shape
     if out is None:
         out = torch.empty((cols, rows), dtype=BF16, device=x.device)
-    _wrote(out)
+    _out(out, (cols, rows), BF16, "out", "transpose")
     with _Rec("transpose", 0.0, 2.0 * 2 * rows * cols):
         _lib.call("vst_transpose", _p(x), _ld(x), rows, cols, _p(out), _ld(out), _stream())
     return out
@@ -899,6 +962,9 @@ def colsum(x, out=None):
     M, N = x.shape
     if out is None:
         out = torch.empty(N, dtype=F32, device=x.device)
+    _wrote(out)
+    if not out.is_cuda or out.dtype != F32 or out.dim() != 1 or out.numel() != N or not out.is_contiguous():
+        raise _lib.VstError(f"colsum: out must be contiguous fp32 [{N}] on device")
     if N % 8 or _ld(x) % 8 or x.data_ptr() % 16:
         n8 = (N + 7) // 8 * 8
         xp = torch.zeros((M, n8), dtype=BF16, device=x.device)
@@ -921,6 +987,7 @@ def geglu_bwd(p, g, out=None):
         raise _lib.VstError(f"geglu_bwd: p {tuple(p.shape)} vs g {tuple(g.shape)}")
     if out is None:
         out = torch.empty((M, 2 * Nh), dtype=BF16, device=p.device)
+    _out(out, (M, 2 * Nh), BF16, "out", "geglu_bwd")
     with _Rec("geglu_bwd", 0.0, 2.0 * 5 * M * Nh):
         _lib.call("vst_geglu_bwd", _p(p), _ld(p), _p(g), _ld(g), M, Nh, _p(out), _ld(out), _stream())
     return out
@@ -942,6 +1009,9 @@ def spatial_attention_bwd(q, k, v, o, dout, lse, nbatch, heads, Nq, Nk, kv_div=1
         dq = torch.empty((nbatch * Nq, C), dtype=BF16, device=q.device)
     if need_dkv and dkv is None:
         dkv = torch.empty((nkv * Nk, 2 * C), dtype=BF16, device=q.device)
+    _out(dq, (nbatch * Nq, C), BF16, "dq", "spatial_attention_bwd")
+    if need_dkv:
+        _out(dkv, (nkv * Nk, 2 * C), BF16, "dkv", "spatial_attention_bwd")
     ws = torch.empty((_lib.load().vst_spatial_attention_bwd_workspace_bytes(nbatch, heads, Nq, Nk) + 3) // 4,
                      dtype=F32, device=q.device)
     scale = 0.125 if scale is None else scale
@@ -966,6 +1036,7 @@ def temporal_attention_bwd(q, k, v, dout, nclip, F, HW, heads, head_dim, scale=N
     rows = nclip * F * HW
     if out is None:
         out = torch.empty((rows, 3 * C), dtype=BF16, device=q.device)
+    _out(out, (rows, 3 * C), BF16, "out", "temporal_attention_bwd")
     scale = head_dim ** -0.5 if scale is None else scale
     with _Rec("temporal_attention_bwd", 0.0, 2.0 * 7 * rows * C):
         _lib.call("vst_temporal_attention_bwd", _p(q), _p(k), _p(v), q.stride(0), _p(dout), _ld(dout), _p(out[:, :C]),
@@ -993,6 +1064,8 @@ def sumpool2x2(x, nimg, h, w):
 
 
 def copy2d(x, out):
+    _dev(x, BF16, "x")
+    _out(out, x.shape, BF16, "out", "copy2d")
     _lib.call("vst_copy2d", _p(x), _ld(x), _p(out), _ld(out), x.shape[0], x.shape[1], _stream())
     return out
 
@@ -1064,6 +1137,7 @@ def conv3x3_down_pad0(x: torch.Tensor, nimg: int, H: int, W: int, w: torch.Tenso
     M = nimg * OH * OW
     if out is None:
         out = torch.empty((M, Cout), dtype=BF16, device=x.device)
+    _out(out, (M, Cout), BF16, "out", "conv3x3_down_pad0")
     if bias is not None and (bias.dtype != F32 or bias.numel() != Cout):
         raise _lib.VstError("conv3x3_down_pad0: bias must be fp32 [Cout]")
     with _Rec("conv3x3", 2.0 * M * Cout * 9 * C, 2.0 * (nimg * H * W * C + Cout * 9 * C + M * Cout),
@@ -1084,8 +1158,7 @@ def gemm_f32out(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor | None = Non
         raise _lib.VstError(f"gemm_f32out: a {tuple(a.shape)} vs w {tuple(w.shape)}")
     if out is None:
         out = torch.empty((M, N), dtype=F32, device=a.device)
-    if out.dtype != F32 or not out.is_contiguous() or out.shape != (M, N):
-        raise _lib.VstError("gemm_f32out: out must be contiguous fp32 [M, N]")
+    _out_flat(out, (M, N), F32, "out", "gemm_f32out")
     with _Rec("gemm_f32out", 2.0 * M * N * K, 2.0 * (M * K + N * K) + 4.0 * M * N,
               lambda: gemm_kernel_name(M, N, K, 0), (M, N, K)):
         _lib.call("vst_gemm_f32out", _p(a), _ld(a), _p(w), _ld(w), M, N, K, _p(out), _stream())
@@ -1099,7 +1172,7 @@ def softmax_rows(s: torch.Tensor, scale: float, out: torch.Tensor | None = None)
     rows, n = s.shape
     if out is None:
         out = torch.empty((rows, n), dtype=BF16, device=s.device)
-    _dev(out, BF16, "out")
+    _out(out, (rows, n), BF16, "out", "softmax_rows")
     with _Rec("softmax", 0.0, 4.0 * rows * n + 2.0 * rows * n):
         _lib.call("vst_softmax_rows", _p(s), _ld(s), rows, n, float(scale), _p(out), _ld(out), _stream())
     return out
