@@ -159,6 +159,21 @@ int vst_sa_self(int on);
 int vst_temporal_attention(const void* q, const void* k, const void* v, int ldqkv, void* o, int ldo, int nclip,
                            int F, int HW, int heads, int head_dim, float scale, void* stream);
 
+/* Frame-axis attention inside sliding windows, for clips longer than the motion modules' trained length (no line of
+ * the reference does this: it stops at 32 frames; the definition is this project's, DESIGN.md "Long clips").  Windows of
+ * L frames start at 0, S, 2S, ... while they fit, plus one at F - L when the last of those does not end the clip; window
+ * position j of the window at s is frame s + j.  Per (clip, pixel, head) and window, q/k/v row j is
+ * bf16(float(q/k/v[s + j]) + pos_q/k/v[j]) and the attention over the window's L frames is vst_temporal_attention's;
+ * o[f] = sum_s w[f-s] O_s[f-s] / sum_s w[f-s] with w[j] = 1 (weighting 0, flat) or min(j + 1, L - j) (1, pyramid),
+ * accumulated in fp32 in ascending window order and rounded to bf16 once.  Rows (b*F + f)*HW + p and the q/k/v/o
+ * alignment rules as vst_temporal_attention; pos_*: fp32 [L][>= heads*head_dim] with row stride ldpos (16-byte aligned,
+ * ldpos % 4 == 0), all NULL = zeros; F >= L, 1 <= L <= 32, 1 <= S <= L; head_dim a multiple of 8 up to 160.  No
+ * workspace, no atomics; every output element is written exactly once. */
+int vst_temporal_attention_windowed(const void* q, const void* k, const void* v, int ldqkv, const float* pos_q,
+                                    const float* pos_k, const float* pos_v, int ldpos, void* o, int ldo, int nclip,
+                                    int F, int HW, int heads, int head_dim, int L, int S, int weighting, float scale,
+                                    void* stream);
+
 /* One attention half of a motion-module BasicTransformerBlock in ONE launch (the fused temporal block of SURVEY
  * §8(d)):  y = x + to_out(softmax_over_frames(q k^T * scale) v),  [q | k | v] = (LayerNorm(x) + pe[frame]) . wqkv^T
  * (+ bqkv), to_out = . wo^T + bo; token (clip b, frame f, pixel p) at row (b*F + f)*HW + p; pe: [F][C] fp32 or NULL.

@@ -35,6 +35,8 @@ SIGNATURES = {
                             _S, _P]),
     "vst_spatial_attention": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P]),
     "vst_temporal_attention": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
+    "vst_temporal_attention_windowed": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F,
+                                             _P]),
     "vst_motion_attention_block": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _F, _P, _P, _I, _P, _P, _I, _P, _F, _P, _I,
                                         _P]),
     "vst_motion_attention_block_supported": (_I, [_I, _I, _I, _I]),

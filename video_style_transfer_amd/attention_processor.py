@@ -199,12 +199,30 @@ def _tattn_operands(attn, ops, heads, head_dim):
     return c[1], c[2]
 
 
+def _context_table(attn, ops, pe, length):
+    """fp32 [length, 3C] = pe[:length] @ Wqkv^T (LoRA factors included, bias not): what the positional term adds to
+    q/k/v by linearity, so the windowed kernel adds it per window position behind ONE projection per frame.  Cached on
+    the module against the fused operand it was made from, like _tattn_operands."""
+    c = attn.__dict__.get("_vst_context_table")
+    if c is None or c[0] is not ops or c[1] != length or c[2] != pe.data_ptr():
+        with torch.no_grad():
+            w = ops.w.float()
+            p = pe[:length].float()
+            t = p @ w[:, :ops.k1].t()
+            if ops.a is not None:
+                t = t + (p @ ops.a.float().t()) @ w[:, ops.k1:].t()
+        c = (ops, length, pe.data_ptr(), t.contiguous())
+        attn.__dict__["_vst_context_table"] = c
+    return c[3]
+
+
 class AttnProcessor2_0:
     """Default (motion-module) processor: self-attention along the frame axis."""
 
     def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None,
                  num_frames: Optional[int] = None, **kwargs):
         fused_residual = kwargs.pop("_vst_residual", None)
+        context = kwargs.pop("_vst_context", None)  # (TemporalContext, fp32 PE table): hidden_states carry no PE
         if encoder_hidden_states is not None or attention_mask is not None:
             raise NotImplementedError("motion-module attention is self-attention without mask")
         batch, N, C = hidden_states.shape
@@ -219,7 +237,16 @@ class AttnProcessor2_0:
         ops = build_ops([attn.to_q, attn.to_k, attn.to_v], 1.0)
         # (HW % (16 P) under K.fusion_world(P): a P-way all-to-all rank holds HW / P pixels and fuses only when that
         # is a multiple of 16, so the unsharded forward it is compared with decides the same way)
-        if num_frames is not None and _tattn_enabled() and ops.a is None and ops.w.shape[1] == C and \
+        if context is not None:
+            # a clip longer than the context: one projection per frame, then the frame attention inside sliding
+            # windows with the positional term added per window position (vst_temporal_attention_windowed); the fused
+            # q/k/v + attention GEMM steps aside (its epilogue attends over whole 16-frame clips)
+            tc, pe = context
+            qkv = run_ops(x, ops)
+            o = K.temporal_attention_windowed(qkv[:, :inner], qkv[:, inner:2 * inner], qkv[:, 2 * inner:],
+                                              _context_table(attn, ops, pe, tc.length), nclip, Fr, HW, heads, D,
+                                              tc.length, tc.stride, tc.weighting)
+        elif num_frames is not None and _tattn_enabled() and ops.a is None and ops.w.shape[1] == C and \
                 HW % (16 * K.fusion_pixel_div()) == 0 and \
                 K.temporal_attention_fusable(batch * N, C, nclip, Fr, HW, heads, D):
             # q/k/v projection + frame attention in one launch (vst_gemm_temporal_attention; 16 frames, heads of 40)

@@ -480,11 +480,21 @@ def transformer2d_train(t2d, x2d, nimg: int, H: int, W: int, enc=None, frames_pe
     return AddFn.apply(x2d, proj_train([t2d.proj_out], h))
 
 
-def motion_module_train(mm, x2d, nclip: int, F: int, HW: int):
+def refuse_context(temporal_context, F: int):
+    """Training with sliding-window frame attention is not built (no windowed backward kernel): a context that would be
+    active on this clip is refused before any launch; one that is not (F <= length) changes nothing."""
+    if temporal_context is not None and F > temporal_context.length:
+        raise NotImplementedError(f"training a clip of {F} frames with context_length {temporal_context.length}: the "
+                                  "windowed frame attention has no backward pass; train on clips of at most "
+                                  "context_length frames")
+
+
+def motion_module_train(mm, x2d, nclip: int, F: int, HW: int, temporal_context=None):
     """Forward of a motion module (unet_motion.MotionModule = diffusers AnimateDiffTransformer3D) built from the
     autograd Functions above, so loss.backward() runs the whole module backward on HIP kernels: GroupNorm over the
     clip, proj_in, [LN+PE -> fused q/k/v (+temporal LoRA) -> frame-axis attention -> to_out (+LoRA) -> +res] x2,
     LN -> GEGLU -> ff.2 -> +res, proj_out -> +x.  Tokens [(b*F + f)*HW + p, C] bf16."""
+    refuse_context(temporal_context, F)
     C = x2d.shape[1]
     h = GroupNormFn.apply(x2d, mm.norm.weight, mm.norm.bias, nclip, F * HW, mm.norm.num_groups, mm.norm.eps, False, F)
     h = proj_train([mm.proj_in], h)
@@ -620,12 +630,14 @@ class SpatialAttentionFn(torch.autograd.Function):
         return dq, dk, dv, None, None, None, None, None
 
 
-def unet_train_tokens(unet, x, B: int, F: int, h: int, w: int, emb_silu, enc2d, scale: float = 1.0):
+def unet_train_tokens(unet, x, B: int, F: int, h: int, w: int, emb_silu, enc2d, scale: float = 1.0,
+                      temporal_context=None):
     """UNetMotionModel.forward_tokens (unet_motion.py) on the autograd Functions: the training forward of
     train_animatediff.py:265-273 whose loss.backward() runs on HIP kernels end to end — frozen spatial path (convs,
     ResnetBlock2D, Transformer2DModel with UnZipLoRA) dX only, motion modules with their trainable parameters.
     x: [B*F*h*w, in] bf16 tokens of the noisy latents; emb_silu: SiLU(time + add embedding) [B, T] (constant);
     enc2d: [B*L, D] text states (constant)."""
+    refuse_context(temporal_context, F)
     temb = unet.batched_temb(emb_silu)
     nimg = B * F
     H, W = h, w

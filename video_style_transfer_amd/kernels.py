@@ -682,6 +682,78 @@ def temporal_attention(q, k, v, nclip, F, HW, heads, head_dim, out=None, scale=N
     return out
 
 
+def context_windows(F: int, L: int, S: int) -> list[int]:
+    """Start frames of the sliding windows over an F-frame clip: 0, S, 2S, ... while start + L <= F, plus F - L when
+    the last of those does not end the clip (every window L frames long, every frame covered); [0] when F <= L."""
+    F, L, S = int(F), int(L), int(S)
+    if not 1 <= L <= 32:
+        raise ValueError(f"context_length {L} outside 1..32")
+    if not 1 <= S <= L:
+        raise ValueError(f"context_stride {S} outside 1..context_length ({L})")
+    if F < 1:
+        raise ValueError(f"F = {F}")
+    if F <= L:
+        return [0]
+    starts = list(range(0, F - L + 1, S))
+    if starts[-1] != F - L:
+        starts.append(F - L)
+    return starts
+
+
+WEIGHTINGS = {"flat": 0, "pyramid": 1}
+
+
+def context_weights(L: int, weighting: str = "pyramid") -> list[float]:
+    """Blend weight of every window position: flat 1, pyramid min(j + 1, L - j)."""
+    if weighting not in WEIGHTINGS:
+        raise ValueError(f"weighting {weighting!r} not in {sorted(WEIGHTINGS)}")
+    if L < 1:
+        raise ValueError(f"context_length {L}")
+    return [float(min(j + 1, L - j)) if weighting == "pyramid" else 1.0 for j in range(L)]
+
+
+def temporal_attention_windowed(q, k, v, pos, nclip, F, HW, heads, head_dim, context_length, context_stride,
+                                weighting="pyramid", out=None, scale=None):
+    """Frame-axis attention inside sliding windows of context_length frames, blended per frame (DESIGN.md "Long
+    clips"); rows (b*F + f)*HW + p.  q/k/v views share one row stride and hold the projections WITHOUT the positional
+    term; pos: fp32 [context_length, 3*heads*head_dim] = pe[:L] @ Wqkv^T (its q | k | v column blocks are added at the
+    position inside each window), or None."""
+    for n, t in (("q", q), ("k", k), ("v", v)):
+        _dev(t, BF16, n)
+    L, S, C = int(context_length), int(context_stride), heads * head_dim
+    context_windows(F, L, S)
+    if weighting not in WEIGHTINGS:
+        raise ValueError(f"weighting {weighting!r} not in {sorted(WEIGHTINGS)}")
+    if F < L:
+        raise _lib.VstError(f"temporal_attention_windowed: F = {F} < context_length {L}")
+    if not (q.stride(0) == k.stride(0) == v.stride(0)):
+        raise _lib.VstError("temporal_attention_windowed: q/k/v must share a row stride")
+    if q.shape[0] != nclip * F * HW:
+        raise _lib.VstError("temporal_attention_windowed: rows != nclip*F*HW")
+    pq = pk = pv = None
+    ldpos = 0
+    if pos is not None:
+        _dev(pos, F32, "pos")
+        if tuple(pos.shape) != (L, 3 * C):
+            raise _lib.VstError(f"temporal_attention_windowed: pos shape {tuple(pos.shape)} != {(L, 3 * C)}")
+        ldpos = pos.stride(0) if L > 1 else 3 * C
+        if pos.data_ptr() % 16 or ldpos % 4:
+            raise _lib.VstError("temporal_attention_windowed: pos must be 16-byte aligned with a row stride % 4 == 0")
+        pq, pk, pv = pos[:, :C], pos[:, C:2 * C], pos[:, 2 * C:]
+    if out is None:
+        out = torch.empty((q.shape[0], C), dtype=BF16, device=q.device)
+    _out(out, (q.shape[0], C), BF16, "out", "temporal_attention_windowed")
+    scale = head_dim ** -0.5 if scale is None else scale
+    T = nclip * F * HW
+    nwin = len(context_windows(F, L, S))
+    with _Rec("temporal_attention_windowed", 4.0 * nclip * HW * nwin * L * L * C, 2.0 * 4 * T * C,
+              lambda: "temporal_attn_windowed_kernel"):
+        _lib.call("vst_temporal_attention_windowed", _p(q), _p(k), _p(v), q.stride(0), _p(pq), _p(pk), _p(pv), ldpos,
+                  _p(out), _ld(out), nclip, F, HW, heads, head_dim, L, S, WEIGHTINGS[weighting], float(scale),
+                  _stream())
+    return out
+
+
 def motion_block_fusable(C, F, HW, heads):
     """vst_motion_attention_block takes this motion-module shape (host policy only)."""
     return bool(_lib.load().vst_motion_attention_block_supported(C, F, HW, heads))

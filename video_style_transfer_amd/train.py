@@ -198,7 +198,7 @@ class TrainStep:
     def __init__(self, unet, optimizer, scheduler, *, reducer: Optional[GradBucketAllReducer] = None,
                  lambda_orth: float = 0.0, spatial_index: Optional[Dict] = None, max_grad_norm: float = 1.0,
                  p_uncond: float = 0.1, resolution: int = 512, seed: int = 0, lr_scheduler=None,
-                 gradient_accumulation_steps: int = 1, num_processes: Optional[int] = None):
+                 gradient_accumulation_steps: int = 1, num_processes: Optional[int] = None, temporal_context=None):
         """`seed` is offset by the process rank: every data-parallel rank draws its own noise, timesteps and
         unconditional-prompt coin (the reference's per-process RNG streams).  `lr_scheduler` (optional) steps after
         the optimizer (train_animatediff.py:318), `num_processes` times per optimizer step (default: the world
@@ -206,6 +206,7 @@ class TrainStep:
         if gradient_accumulation_steps < 1:
             raise ValueError("gradient_accumulation_steps must be >= 1")
         self.unet = unet
+        self.temporal_context = temporal_context  # refused for clips longer than its length (autograd.refuse_context)
         self.opt = optimizer
         self.sched = scheduler
         self.lr_scheduler = lr_scheduler
@@ -274,11 +275,12 @@ class TrainStep:
         """The micro-batch loss (train_animatediff.py:228-312): Euler add_noise, the HIP UNet forward, epsilon MSE in
         fp32 and the orthogonality loss."""
         from . import kernels as K
-        from .autograd import unet_train_tokens
+        from .autograd import refuse_context, unet_train_tokens
         from .temporal_lora import compute_orth_loss
 
         unet = self.unet
         B, Cl, F, h, w = latents.shape
+        refuse_context(self.temporal_context, F)
         dev = latents.device
         # add_noise with the clip's timestep on every frame (:233-236); sigma broadcasts over (C, F, h, w)
         noisy = self.sched.add_noise(latents, noise, t).contiguous()
@@ -287,7 +289,8 @@ class TrainStep:
         K.pack_latents(noisy, x)
         with torch.no_grad():
             emb = unet.embed(t.to(torch.float32), pool, tids, B)
-        pred = unet_train_tokens(unet, x, B, F, h, w, emb, enc)                            # :265-273
+        pred = unet_train_tokens(unet, x, B, F, h, w, emb, enc,                               # :265-273
+                                 temporal_context=self.temporal_context)
         target = noise.permute(0, 2, 3, 4, 1).reshape(-1, Cl)                              # epsilon, :276-277
         loss_mse = torch.mean((pred.float() - target) ** 2)                                # :298-300
         if self.lambda_orth > 0 and self.spatial_index:

@@ -130,6 +130,33 @@ class Linear(LoRACompatibleLinear):
         return run_ops(x, build_ops([self], 1.0), residual=residual, out=out)
 
 
+@dataclass(frozen=True)
+class TemporalContext:
+    """Sliding-window frame attention for clips longer than the motion modules' trained length (DESIGN.md "Long
+    clips"): windows of `length` frames every `stride` frames, blended `flat` or `pyramid`.  Active when a clip has more
+    than `length` frames; shorter clips run exactly as without it."""
+    length: int
+    stride: int = 4
+    weighting: str = "pyramid"
+
+    def __post_init__(self):
+        K.context_windows(self.length, self.length, self.stride)  # 1 <= length <= 32, 1 <= stride <= length
+        K.context_weights(self.length, self.weighting)
+
+    def active(self, F: int) -> bool:
+        return F > self.length
+
+
+def check_clip_length(F: int, max_seq_length: int, tc: Optional[TemporalContext]):
+    """Refuse, before any launch, a clip the motion modules cannot attend over: more frames than positional rows with
+    no context windows, or windows longer than the table."""
+    if tc is not None and tc.length > max_seq_length:
+        raise K._lib.VstError(f"context_length {tc.length} exceeds the motion modules' {max_seq_length} positions")
+    if F > max_seq_length and (tc is None or not tc.active(F)):
+        raise K._lib.VstError(f"a clip of {F} frames exceeds the motion modules' {max_seq_length} positions: pass "
+                              f"context_length (<= {max_seq_length}) to attend inside sliding windows")
+
+
 @dataclass
 class FwdCtx:
     B: int                 # clips in the batch (CFG-batched: 2x)
@@ -139,6 +166,7 @@ class FwdCtx:
     cross_kwargs: dict
     shard: Optional[object] = None  # frame_shard.FrameShard when the clip's frames span ranks (F is per rank)
     temb: Optional[dict] = None     # ResnetBlock2D -> fp32 [B, Cout] view of the batched time_emb_proj output
+    temporal_context: Optional[TemporalContext] = None  # motion attention inside sliding windows when F > length
 
 
 # --------------------------------------------------------------------------------------- blocks
@@ -206,6 +234,18 @@ class BasicTransformerBlock(nn.Module):
         C = x.shape[1]
         if self.temporal:
             pe = f32(self.pos_embed.pe).view(-1, C)
+            tc = ctx.temporal_context
+            check_clip_length(ctx.F, pe.shape[0], tc)
+            if tc is not None and tc.active(ctx.F):
+                # LayerNorm WITHOUT the positional term: the windowed kernel adds pe[position in window] . Wqkv^T per
+                # window behind one projection per frame; the fused q/k/v GEMM and the whole-block kernel step aside
+                kw = dict(num_frames=ctx.F, _vst_context=(tc, pe))
+                n = self.norm1.run(x)
+                x = self.attn1(n.view(nimg, N, C), _vst_residual=x, **kw).view(-1, C)
+                n = self.norm2.run(x)
+                x = self.attn2(n.view(nimg, N, C), _vst_residual=x, **kw).view(-1, C)
+                n = self.norm3.run(x)
+                return self.ff.run(n, residual=x)
             fused = self._fused_motion_ops(C, ctx.F, N)
             if fused is not None:
                 # each attention half (norm + PE, q/k/v, frame attention, to_out, residual) as one launch
@@ -596,17 +636,22 @@ class UNetMotionModel(nn.Module):
         return out
 
     # ---- core (NHWC tokens) -----------------------------------------------------------------
-    def forward_tokens(self, x, B, F, h, w, emb_silu, enc, cross_kwargs=None, shard=None, fusion_world=None):
+    def forward_tokens(self, x, B, F, h, w, emb_silu, enc, cross_kwargs=None, shard=None, fusion_world=None,
+                       temporal_context=None):
         """x: [B*F*h*w, in_channels] bf16 -> noise prediction [B*F*h*w, out_channels] bf16.
         With `shard` (frame_shard.FrameShard), F is this rank's frames of each clip.  `fusion_world` P (default: the
         shard's world size, else 1): take the shape-dependent fusion decisions a P-way frame-sharded rank takes
         (kernels.fusion_world), so an unsharded forward equals a P-way sharded one bit for bit."""
+        if self.config.motion_modules:
+            check_clip_length(F * (shard.world if shard is not None else 1), self.config.motion_max_seq_length,
+                              temporal_context)
         if fusion_world is None:
             fusion_world = shard.world if shard is not None else 1
         # no split-K: a row's bits do not depend on the launch's row count (frame shards)
         K.colstat_reset()
         with K.row_invariant(), K.fusion_world(fusion_world):
-            ctx = FwdCtx(B, F, emb_silu, enc, cross_kwargs or {}, shard, self.batched_temb(emb_silu))
+            ctx = FwdCtx(B, F, emb_silu, enc, cross_kwargs or {}, shard, self.batched_temb(emb_silu),
+                         temporal_context)
             nimg = B * F
             H, W = h, w
             x = self.conv_in.run(x, nimg, H, W)
@@ -622,13 +667,17 @@ class UNetMotionModel(nn.Module):
 
     def forward(self, sample, timestep, encoder_hidden_states, timestep_cond=None, attention_mask=None,
                 cross_attention_kwargs=None, added_cond_kwargs=None, return_dict=True, frame_shard=None,
-                fusion_world=None, **kwargs):
+                fusion_world=None, temporal_context=None, **kwargs):
         """diffusers UNetMotionModel.forward signature (inference_animatediff.py:110-121).  With
         `frame_shard` (frame_shard.FrameShard) `sample` holds this rank's frames of each clip; `fusion_world`: see
-        forward_tokens."""
+        forward_tokens; `temporal_context` (TemporalContext): the motion modules attend inside sliding windows when the
+        clip is longer than its length."""
         if not sample.is_cuda:
             raise K._lib.VstError("UNetMotionModel: sample is on CPU; the HIP path has no CPU fallback")
         B, Cin, F, h, w = sample.shape
+        if self.config.motion_modules:
+            check_clip_length(F * (frame_shard.world if frame_shard is not None else 1),
+                              self.config.motion_max_seq_length, temporal_context)
         dev = sample.device
         t = timestep if torch.is_tensor(timestep) else torch.tensor([timestep])
         t = t.to(device=dev, dtype=torch.float32).reshape(-1)
@@ -642,6 +691,6 @@ class UNetMotionModel(nn.Module):
         x = torch.empty(B * F * h * w, Cin, dtype=BF16, device=dev)
         K.pack_latents(sample.float().contiguous(), x)
         y = self.forward_tokens(x, B, F, h, w, emb_silu, enc, cross_attention_kwargs, shard=frame_shard,
-                                fusion_world=fusion_world)
+                                fusion_world=fusion_world, temporal_context=temporal_context)
         out = y.view(B, F, h, w, -1).permute(0, 4, 1, 2, 3).contiguous().to(sample.dtype)
         return UNetMotionOutput(out) if return_dict else (out,)
