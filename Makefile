@@ -1,4 +1,4 @@
-# Builds the C-ABI HIP library (gfx950) and the C oracle pieces.
+# Builds the C-ABI HIP library (gfx950).
 HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 HIPFLAGS ?= -O3 -fPIC -std=c++17 --offload-arch=$(ARCH) -Wall -Wno-unused-function

@@ -1,8 +1,8 @@
-"""A/B of two builds of libvst_hip.so on the step's GEMM shapes (tools/p8_ph_ab.py's child: us per launch, output
+"""A/B of two builds of libvst_hip.so on the step's GEMM shapes (tools/p8_variant_ab.py's child: us per launch, output
 md5): each build runs in its own child process (VST_LIB_AB), alternated `passes` times, best time kept.
 python tools/lib_ab.py passes name=path [name=path ...]   (path "-" = the in-tree library)
 VST_AB_SHAPES=a,b restricts the shapes.  One JSON line per shape: us and TF/s per build, and whether every build's
-output is bit-identical."""
+output is bit-identical, and the kernel (or in-GEMM LoRA tile width) each build's dispatch chose."""
 import json
 import os
 import subprocess
@@ -18,11 +18,11 @@ def main():
     order = []
     for _ in range(passes):
         for name, path in libs:
-            env = dict(os.environ, VST_PH_CHILD="1", VST_P8_PH="2")
+            env = dict(os.environ, VST_AB_CHILD="1")
             env.pop("VST_LIB_AB", None)
             if path != "-":
                 env["VST_LIB_AB"] = path
-            r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "p8_ph_ab.py")], env=env,
+            r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "p8_variant_ab.py")], env=env,
                                capture_output=True, text=True, timeout=300)
             if r.returncode:
                 print(r.stderr[-3000:], file=sys.stderr)
@@ -41,7 +41,9 @@ def main():
         row = {name: res[(shape, name)] for name, _ in libs}
         md5s = {d["md5"] for d in row.values()}
         print(json.dumps({"shape": shape, **{f"us_{n}": d["us"] for n, d in row.items()},
-                          **{f"tf_{n}": d["tflops"] for n, d in row.items()}, "bitwise_equal": len(md5s) == 1}),
+                          **{f"tf_{n}": d["tflops"] for n, d in row.items()},
+                          **{f"kernel_{n}": d["kernel"] or d["lora_tile"] for n, d in row.items()},
+                          "bitwise_equal": len(md5s) == 1}),
               flush=True)
 
 

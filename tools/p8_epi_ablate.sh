@@ -16,17 +16,18 @@ if [ "$1" = build ]; then
   done
   exit 0
 fi
+mkdir -p abl
 for pass in 1 2; do
   for v in base NOGELU NOEPI; do
     if [ $v = base ]; then lib=""; else lib=abl/libvst_$v.so; fi
-    VST_LIB_AB=$lib VST_PH_CHILD=1 VST_P8_PH=2 timeout -k 10 240 python -u tools/p8_ph_ab.py > gpurun_out/abl_${v}_$pass.jsonl
+    VST_LIB_AB=$lib VST_AB_CHILD=1 timeout -k 10 240 python -u tools/p8_variant_ab.py > abl/abl_${v}_$pass.jsonl
     echo "[abl] $v pass $pass done"
   done
 done
 python - <<'PY'
 import json, glob
 res = {}
-for f in sorted(glob.glob("gpurun_out/abl_*.jsonl")):
+for f in sorted(glob.glob("abl/abl_*.jsonl")):
     v = f.split("abl_")[1].rsplit("_", 1)[0]
     for l in open(f):
         d = json.loads(l)

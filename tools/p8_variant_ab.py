@@ -1,9 +1,12 @@
-"""A/B of the 8-phase GEMM k-loop schedules (VST_P8_PH = 3: three barrier intervals per k-tile; 2: two) on the
-denoise step's GEMM shapes, in isolation: each schedule runs in its own child process (the choice is read once per
-process), alternated `passes` times; the children also hash their outputs, which must be equal (same k order).
-python tools/p8_ph_ab.py [passes] [variant ...]  -> one JSON line per shape with us per launch and TF/s per variant.
-A variant is the schedule, optionally '+320' for the 128x320 tile policy (VST_P8_320=1) and '+persist' for the persistent
-grid (VST_P8_PERSIST=1), '+bn320' / '+bn192' to force the tile width (VST_P8_BN), '+lp' for the persistent LoRA kernels (VST_P8_LORA_PERSIST=1): e.g. 3 2 3+320 2+320 2+persist."""
+"""A/B of the 8-phase GEMM's runtime variants on the denoise step's GEMM shapes, in isolation: each variant runs in
+its own child process (the switches are read once per process), alternated `passes` times; the children also hash their
+outputs, which must be equal (same k order).
+python tools/p8_variant_ab.py [passes] [variant ...]  -> one JSON line per shape with us per launch and TF/s per variant.
+A variant is 'base' (one workgroup per tile, the 256 / 192 tile policy), optionally with '+320' for the 128x320 tile
+policy (VST_P8_320=1), '+persist' for the persistent grid (VST_P8_PERSIST=1), '+bn320' / '+bn192' to force the tile
+width (VST_P8_BN), '+lp' for the persistent LoRA kernels (VST_P8_LORA_PERSIST=1): e.g. base base+320 base+persist
+base+persist+lp.  With VST_AB_CHILD set the script is the child: it times the shapes under the environment it finds
+(tools/lib_ab.py and tools/p8_epi_ablate.sh run it that way)."""
 import hashlib
 import json
 import os
@@ -65,7 +68,7 @@ def child(passes_inner=2):
         try:
             y = fn()
         except K._lib.VstError:  # (the 32x32 q/k/v straddles 256-wide tiles: in-GEMM LoRA only on 128x320 tiles)
-            out.append({"ph": os.environ.get("VST_P8_PH", "3"), "shape": name, "us": 1e9, "tflops": 0.0, "md5": "-",
+            out.append({"shape": name, "us": 1e9, "tflops": 0.0, "md5": "-",
                         "kernel": "unsupported", "lora_tile": 0})
             continue
         torch.cuda.synchronize()
@@ -82,7 +85,7 @@ def child(passes_inner=2):
             e.record()
             torch.cuda.synchronize()
             best = min(best, s.elapsed_time(e) * 1e3 / 20)
-        out.append({"ph": os.environ.get("VST_P8_PH", "3"), "shape": name, "M": M, "N": N, "K": Kd,
+        out.append({"shape": name, "M": M, "N": N, "K": Kd,
                     "lora_tile": K.gemm_lora_tile(M, N, Kd, 32 if kind == "lora1" else 64, N // int(kind[-1]), 16)
                     if kind.startswith("lora") else None,
                     "kernel": "xattn" if kind == "xattn" else None if kind.startswith("lora") else
@@ -93,35 +96,35 @@ def child(passes_inner=2):
 
 
 def main():
-    if os.environ.get("VST_PH_CHILD"):
+    if os.environ.get("VST_AB_CHILD"):
         return child()
     passes = int(sys.argv[1]) if len(sys.argv) > 1 else 2
-    phs = sys.argv[2:] or ["3", "2"]
+    variants = sys.argv[2:] or ["base", "base+persist"]
     res = {}
     for _ in range(passes):
-        for ph in phs:
-            env = dict(os.environ, VST_P8_PH=ph.split("+")[0], VST_PH_CHILD="1", VST_P8_320="1" if "+320" in ph else "0",
-                       VST_P8_PERSIST="1" if "+persist" in ph else "0",
-                       VST_P8_BN="320" if "+bn320" in ph else "192" if "+bn192" in ph else "0",
-                       VST_P8_LORA_PERSIST="1" if "+lp" in ph else "0",
+        for v in variants:
+            env = dict(os.environ, VST_AB_CHILD="1", VST_P8_320="1" if "+320" in v else "0",
+                       VST_P8_PERSIST="1" if "+persist" in v else "0",
+                       VST_P8_BN="320" if "+bn320" in v else "192" if "+bn192" in v else "0",
+                       VST_P8_LORA_PERSIST="1" if "+lp" in v else "0",
                        )
             r = subprocess.run([sys.executable, os.path.abspath(__file__)], env=env, capture_output=True, text=True,
                                timeout=300)
             if r.returncode:
                 print(r.stderr[-3000:], file=sys.stderr)
                 raise SystemExit(r.returncode)
-            print(f"[ab] variant {ph} done", flush=True)
+            print(f"[ab] variant {v} done", flush=True)
             for line in r.stdout.splitlines():
                 d = json.loads(line)
-                key = (d["shape"], ph)
+                key = (d["shape"], v)
                 if key not in res or d["us"] < res[key]["us"]:
                     res[key] = d
     for name, *_ in SHAPES:
-        row = {ph: res[(name, ph)] for ph in phs}
+        row = {v: res[(name, v)] for v in variants}
         md5s = {d["md5"] for d in row.values() if d["md5"] != "-"}
-        print(json.dumps({"shape": name, **{f"us_ph{ph}": d["us"] for ph, d in row.items()},
-                          **{f"tf_ph{ph}": d["tflops"] for ph, d in row.items()},
-                          **{f"kernel_{ph}": d["kernel"] or d["lora_tile"] for ph, d in row.items()},
+        print(json.dumps({"shape": name, **{f"us_{v}": d["us"] for v, d in row.items()},
+                          **{f"tf_{v}": d["tflops"] for v, d in row.items()},
+                          **{f"kernel_{v}": d["kernel"] or d["lora_tile"] for v, d in row.items()},
                           "bitwise_equal": len(md5s) == 1}), flush=True)
 
 

@@ -1149,10 +1149,7 @@ using namespace vst;
 
 static int g_sa_self = -1;  // VST_SA_SELF, or vst_sa_self (tests, A/B)
 static int sa_self_on() {
-  if (g_sa_self < 0) {
-    const char* e = getenv("VST_SA_SELF");
-    g_sa_self = e ? (atoi(e) != 0) : 1;
-  }
+  if (g_sa_self < 0) g_sa_self = env_int("VST_SA_SELF", 1) != 0;
   return g_sa_self;
 }
 
@@ -1177,10 +1174,7 @@ extern "C" int vst_spatial_attention(const void* q, int ldq, const void* k, cons
   if (fit.over) return VST_ERR_ARG;  // past the 32-bit buffer offsets: refuse, never read zeros
   const int nt = (Nk + SA_KT - 1) / SA_KT;
   static int pre_env = -1;  // VST_SA_PRELOAD=0 disables the whole-K/V preload (A/B diagnostics)
-  if (pre_env < 0) {
-    const char* e = getenv("VST_SA_PRELOAD");
-    pre_env = e ? atoi(e) : 1;
-  }
+  if (pre_env < 0) pre_env = env_int("VST_SA_PRELOAD", 1);
   // measured (tools/attn_bench.py, one process, alternating): cross-attention over 77 text keys 33 -> 28.5 us at 32x32
   // and 18 -> 17.3 us at 16x16; the 16x16 self-attention (4 tiles) 29.2 -> 31.2 us (64 KiB of LDS per workgroup
   // drops occupancy from 3 to 2 workgroups per CU), so only up to two tiles are preloaded

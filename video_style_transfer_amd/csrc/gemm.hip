@@ -642,11 +642,7 @@ int launch_gemm_p8_conv(const GemmArgs& a, int bn, hipStream_t s);
 
 // 8-phase 256x256x64 kernel (gemm_p8.hip) for plain / LoRA-augmented projections and GEGLU (see p8_auto).
 static int gemm_p8_env() {
-  static int v = -2;
-  if (v == -2) {
-    const char* e = getenv("VST_GEMM_P8");
-    v = e ? atoi(e) : -1;
-  }
+  static const int v = env_int("VST_GEMM_P8", -1);
   return v;
 }
 
@@ -657,8 +653,7 @@ static int gemm_p8_env() {
 // 9.1 ms per step, profiles/r2_ab_p8_all_k.txt).
 // VST_GEMM_P8 = 0 off, unset / 1 every shape with at least half a wave of 256x256 tiles.
 static int device_cus();
-static bool p8_auto(int M, int N, int K, bool geglu) {
-  (void)geglu;
+static bool p8_auto(int M, int N, int K) {
   const int e = gemm_p8_env();
   if (e == 0) return false;
   const int t256 = ((M + 255) / 256) * ((N + 255) / 256);
@@ -673,10 +668,7 @@ static bool p8_auto(int M, int N, int K, bool geglu) {
 // Forced 8-phase tile width (256 / 192 / 320, 0 = the policy below): VST_P8_BN, or vst_p8_force_bn (tests, A/B).
 static int g_p8_force_bn = -1;
 static int p8_forced_bn() {
-  if (g_p8_force_bn < 0) {
-    const char* e = getenv("VST_P8_BN");
-    g_p8_force_bn = e ? atoi(e) : 0;
-  }
+  if (g_p8_force_bn < 0) g_p8_force_bn = env_int("VST_P8_BN", 0);
   return g_p8_force_bn;
 }
 
@@ -693,10 +685,7 @@ static bool p8_bn192(int M, int N, bool geglu) {
 // gives 224.  A 128x320 tile is 0.625 of a 256x256 one in work.  VST_P8_320 = 1 takes it wherever its round count
 // times 0.7 beats the 256 / 192 choice; VST_P8_BN = 320 wherever it is legal (A/B).
 static bool p8_320_on() {
-  static const int on = [] {
-    const char* e = getenv("VST_P8_320");
-    return e ? atoi(e) : 0;
-  }();
+  static const int on = env_int("VST_P8_320", 0);
   return on != 0;
 }
 
@@ -715,10 +704,7 @@ static bool p8_bn320(int M, int N, bool geglu) {
 
 static int g_p8_conv = -1;  // VST_P8_CONV, or vst_p8_conv (tests, A/B)
 static bool p8_conv_env() {
-  if (g_p8_conv < 0) {
-    const char* e = getenv("VST_P8_CONV");
-    g_p8_conv = e ? atoi(e) : 1;
-  }
+  if (g_p8_conv < 0) g_p8_conv = env_int("VST_P8_CONV", 1);
   return g_p8_conv != 0;
 }
 
@@ -754,8 +740,7 @@ extern "C" int vst_p8_conv(int on) {
 namespace vst {
 
 // tile code 8: AMODE 0, no split-K, a 64-aligned A source split, 256x256 tiles
-static bool p8_applies(int M, int N, int K1, bool two_src) {
-  (void)M; (void)N;
+static bool p8_applies(int K1, bool two_src) {
   return !two_src || (K1 & 63) == 0;
 }
 // Workspace (caller-owned): the fp32 split-K slabs [splits][M][N].
@@ -777,30 +762,20 @@ static int device_cus() {
 
 static int gemm_ablate_env() {
   static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("VST_GEMM_ABLATE");
-    v = e ? atoi(e) : 0;
-  }
+  if (v < 0) v = env_int("VST_GEMM_ABLATE", 0);
   return v;
 }
 
 static int gemm_group_env() {
   static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("VST_GEMM_GROUP_M");
-    v = e ? atoi(e) : 0;
-  }
+  if (v < 0) v = env_int("VST_GEMM_GROUP_M", 0);
   return v;
 }
 
 // Persistent launch: measured (tools/gemm_persist.sh) 4-10 % faster for the GEGLU epilogue and neutral for
 // the others, so it is the default for GEGLU only.  VST_GEMM_PERSIST=1 forces it on, =0 off.
 static int gemm_persist_env() {
-  static int v = -2;
-  if (v == -2) {
-    const char* e = getenv("VST_GEMM_PERSIST");
-    v = e ? atoi(e) : -1;
-  }
+  static const int v = env_int("VST_GEMM_PERSIST", -1);
   return v;
 }
 
@@ -845,10 +820,7 @@ extern "C" size_t vst_gemm_workspace_bytes(int M, int N, int K) {
 // ---- fused base + LoRA projection with the down-projection inside the 8-phase GEMM (gemm_p8.hip LORA) ----
 // VST_LORA_INGEMM=0 turns it off (the host then runs the separate down-projection pass, A/B).
 static bool lora_ingemm_env() {
-  static const int v = [] {
-    const char* e = getenv("VST_LORA_INGEMM");
-    return e ? atoi(e) : 1;
-  }();
+  static const int v = env_int("VST_LORA_INGEMM", 1);
   return v != 0;
 }
 
@@ -923,10 +895,7 @@ extern "C" int vst_gemm_lora(const void* x, int ldx, const void* Acat, int ld_ac
 // ---- attn2: q projection (+ in-GEMM LoRA) with the cross-attention over the text tokens as its epilogue ----
 // VST_XATTN_FUSE=0 turns it off (the host then runs the q GEMM and vst_spatial_attention, A/B).
 static bool xattn_env() {
-  static const int v = [] {
-    const char* e = getenv("VST_XATTN_FUSE");
-    return e ? atoi(e) : 1;
-  }();
+  static const int v = env_int("VST_XATTN_FUSE", 1);
   return v != 0;
 }
 
@@ -1027,7 +996,7 @@ extern "C" const char* vst_gemm_kernel_name(int M, int N, int K, int kind, int t
                                        "gemm_ring<256x160,splitk>", "gemm_ring<192x256,splitk>"};
   if (kind == 3) return "gemm_kernel<conv_in>";
   if (kind == 2 && tile == 0 && splits <= 1 && p8_conv_env() && K % 576 == 0 && N % 64 == 0 &&
-      p8_auto(M, N, K, false)) {
+      p8_auto(M, N, K)) {
     if (conv_ring128(M, N)) return "gemm_ring<256x128,conv>";
     const int bn = N % 320 == 0 ? 320 : p8_bn(M, N, false) == 192 ? 192 : 256;
     return bn == 320 ? "gemm_p8<128x320,conv>" : bn == 192 ? "gemm_p8<256x192,conv>" : "gemm_p8<256x256,conv>";
@@ -1045,7 +1014,7 @@ extern "C" const char* vst_gemm_kernel_name(int M, int N, int K, int kind, int t
   };
   if (tile == 9) return kind == 0 ? p8name(192, false) : "";
   if (tile == 10) return kind == 0 ? p8name(320, false) : "";
-  if (tile == 0 && kind <= 1 && p8_auto(M, N, K, kind == 1)) {
+  if (tile == 0 && kind <= 1 && p8_auto(M, N, K)) {
     if (splits <= 1 && kind == 0 && p8_bn(M, N, false) == 320) return p8name(320, false);
     if (splits <= 1 && kind == 0 && p8_bn192(M, N, false)) return p8name(192, false);
     tile = 8;
@@ -1112,7 +1081,7 @@ extern "C" int vst_gemm_ex(const void* A, int lda, const void* A2, int lda2, int
     }
   }
   if (tile < 0 || tile > 10 || splits < 0) return VST_ERR_ARG;
-  if ((tile == 8 || tile == 9 || tile == 10) && !p8_applies(M, N, K1, A2 != nullptr)) return VST_ERR_ARG;
+  if ((tile == 8 || tile == 9 || tile == 10) && !p8_applies(K1, A2 != nullptr)) return VST_ERR_ARG;
   if ((tile == 9 || tile == 10) && epilogue == 1) return VST_ERR_ARG;  // GEGLU needs the 256-wide tiles
   if (tile == 10 && N % 320) return VST_ERR_ARG;
   const bool skinny_ok = N <= 64 && !A2 && !bias && !row_bias && !R && epilogue == 0;
@@ -1137,7 +1106,7 @@ extern "C" int vst_gemm_ex(const void* A, int lda, const void* A2, int lda2, int
   const size_t slab_bytes = workspace ? ws_bytes : 0;
   // splits 1 = no split-K (a row's bits then never depend on M: the denoise forward's row-invariant policy); the
   // 8-phase kernel, which never splits, is chosen the same way under 0 and 1
-  if (tile == 0 && splits <= 1 && p8_auto(M, N, K, epilogue == 1) && p8_applies(M, N, K1, A2 != nullptr))
+  if (tile == 0 && splits <= 1 && p8_auto(M, N, K) && p8_applies(K1, A2 != nullptr))
     tile = p8_bn(M, N, epilogue == 1) == 320 ? 10 : p8_bn192(M, N, epilogue == 1) ? 9 : 8;
   if (tile == 9 || tile == 10) {  // the 8-phase kernel at 256x192 / 128x320
     a.p8_bn = tile == 9 ? 192 : 320;
@@ -1218,7 +1187,7 @@ static int conv3x3_impl(const void* x1, int C1, const void* x2, int C2, int nimg
   // 3x3 convs with both sources a multiple of 64 channels run on the 8-phase kernel (implicit im2col; 128x320 tiles
   // where Cout is a multiple of 320, else the projection policy's width); VST_P8_CONV=0 restores the ring kernel
   bool p8 = vec && tile == 0 && splits <= 1 && p8_conv_env() && !(C1 & 63) && !((x2 ? C2 : 0) & 63) &&
-            !(a.N & 63) && p8_auto(a.M, a.N, a.K, false);
+            !(a.N & 63) && p8_auto(a.M, a.N, a.K);
   if (p8 && !colstat && conv_ring128(a.M, a.N)) {
     p8 = false;
     tile = 4;

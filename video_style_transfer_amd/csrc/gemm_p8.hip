@@ -13,15 +13,33 @@
 // ds_read_b128 fragment reads), filled by `buffer_load ... lds` (16 B per lane, lane-linear 1-KiB pieces, the
 // inverse permutation applied to the source address).
 //
-// 8 waves = 2 (M) x 4 (N), wave tile 128 x 64 = 8 x 4 accumulators (16x16).  A k-tile is three barrier intervals
-// over the quadrants Q(mq, nq) of the wave tile (16 MFMAs of 16x16x32 per quadrant):
-//   I0: read A(mq0) + B(nq0), Q(0,0) + Q(0,1)      I1: read A(mq1), Q(1,1)      I2: read B(nq1) of t+1, Q(1,0)
+// 8 waves = 2 (M) x 4 (N), wave tile 128 x 64 = 8 x 4 accumulators (16x16).  A k-tile is two barrier intervals over
+// the quadrants Q(mq, nq) of the wave tile (16 MFMAs of 16x16x32 per quadrant; 32 per interval, 24 at BN = 192), so
+// every load segment of one wave group runs beside a full-length MFMA segment of the other and each wave's DMAs split
+// evenly over the two:
+//   J0(t) = {read A0(t), B0(t), Acat(t); wait A1(t), B1(t+1); issue A1(t+1)}        | Q(0,0) + Q(0,1)
+//   J1(t) = {read A1(t); wait A0/B0(t+1); issue B1(t+2), A0(t+2) (+Acat), B0(t+2)} | Q(1,1), read B1(t+1), Q(1,0)
 // Each interval = {fragment reads, counted vmcnt wait, LDS-DMA issue} barrier {MFMAs} barrier; waves 4-7 run one
 // barrier behind waves 0-3, so on every SIMD one wave's MFMAs overlap its partner's reads and DMA issue.
-// A slot is refilled two intervals after the one that reads it (every wave's reads retired: WAR) and waited for
-// (counted s_waitcnt vmcnt, 2 DMAs per slot per wave) in the interval before its first read (RAW).  Past the last
-// k-tile the same DMAs are issued with out-of-range offsets (zeros), so the counts are the same in every interval;
-// they are drained before the epilogue reuses the LDS.
+// B1E (every kernel but GEGLU and the in-GEMM LoRA ones): B1's fragments are read inside J1's MFMA segment, after
+// Q(1,1) frees fb1 (rounds 2-4 read them in J0's load segment, 16 ds_reads against J1's 8; the loop ablations showed the
+// load segments, not the waits, idling the matrix core: profiles/r4_p8_loop_ablation.txt); so B1(t+1) is issued one
+// interval earlier (J1(t-1), first of that segment's DMAs) and waited with A1(t) in J0(t), before both groups' J1(t)
+// MFMA segments.  GEGLU keeps
+//   J0(t) = {read A0(t), B0(t), B1(t); wait A1(t); issue B1(t+1), A1(t+1)}
+//   J1(t) = {read A1(t); wait A0/B0/B1(t+1); issue A0(t+2), B0(t+2)}
+// as do the LoRA kernels: in the step GEGLU measured 0.9 % slower with B1 moved and the LoRA kernels 1 %, the plain
+// GEMMs and the convs 2-4 % faster (profiles/r4_ab_b1_j1.txt).
+// Every segment that reads LDS ends with its reads retired (lgkmcnt(0)) before its barrier, so a slot read in interval
+// X is refilled from interval X + 1 on (WAR); a slot is waited for (counted s_waitcnt vmcnt) in interval X and read in
+// X + 1 (RAW: both groups' waits precede the barrier the later reader passes).  Past the last k-tile the same DMAs are
+// issued with out-of-range offsets (zeros), so the counts are the same in every interval; they are drained before the
+// epilogue reuses the LDS.
+// Removed, with their evidence kept under profiles/: the rounds 2-3 schedule of three intervals per k-tile (16-MFMA
+// intervals beside 4-DMA load segments; 2-5 % slower per launch, r4_p8_ph_ab.txt), the LDS-DMAs issued inside the MFMA
+// segments (plain GEMMs 1-22 % slower per launch, r5_ab_dma_in_mfma_negative.txt; on the LoRA kernels alone the step
+// 0.2 ms slower, r5_ab_dma_in_mfma_lora_negative.txt), and the LoRA kernels on the plain GEMMs' B1 placement (+1 %,
+// r4_ab_b1_j1.txt).
 #include "attn_common.h"
 #include "gemm_common.h"
 #include "gemm_epilogue.h"
@@ -52,8 +70,9 @@ struct P8Cfg {  // the epilogue's view of the tile (same wave tiling as RingCfg<
   static constexpr int BUF = 2 * SLOT_A + SLOT_B0 + SLOT_B1;
   static constexpr int EPI_BYTES = BM * (BN * 2 + 16);
   static constexpr int LDS = 2 * BUF > EPI_BYTES ? 2 * BUF : EPI_BYTES;
-  // LORA: two 2-KiB Acat slots ([16 u columns][64 k] per k-tile) + 1 KiB sink for the waves without a piece, then
-  // the tile's up-projection columns V [BN rows][16] (32-B rows), staged once in the prologue
+  // LORA: two 2-KiB Acat slots ([16 u columns][64 k] per k-tile) + 1 KiB unused (the sink of rounds 3-4's zero pieces;
+  // kept so V_OFF and with it every LoRA kernel's address immediates stay put), then the tile's up-projection columns
+  // V [BN rows][16] (32-B rows), staged once in the prologue
   static constexpr int LORA_OFF = 2 * BUF, V_OFF = 2 * BUF + 5 * 1024, LORA_END = V_OFF + BN * 32;
   static constexpr int LDS_LORA = LORA_END > EPI_BYTES ? LORA_END : EPI_BYTES;
   // PERSIST: the epilogue stages through the LDS past the ring (the ring holds the next tile's first k-tiles)
@@ -90,19 +109,6 @@ __device__ __forceinline__ void p8_dma16(__amdgpu_buffer_rsrc_t r, char* lds_pie
 }
 
 __device__ __forceinline__ int p8_off(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-
-// scheduling hint for an MFMA segment that also issues NV LDS-DMAs (VMEM) among its NM MFMAs: one DMA after every
-// NM / (NV + 1) MFMAs, the rest of the MFMAs after the last one
-template <int NM, int NV>
-__device__ __forceinline__ void p8_interleave_dma() {
-  constexpr int PER = NM / (NV + 1) > 0 ? NM / (NV + 1) : 1;
-#pragma unroll
-  for (int g = 0; g < NV; ++g) {
-    __builtin_amdgcn_sched_group_barrier(0x008, PER, 0);  // MFMA
-    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);    // VMEM read (buffer_load ... lds)
-  }
-  __builtin_amdgcn_sched_group_barrier(0x008, NM, 0);
-}
 
 __device__ __forceinline__ void p8_barrier() {
   __builtin_amdgcn_sched_barrier(0);
@@ -559,9 +565,10 @@ __device__ __forceinline__ void tattn_epilogue(const GemmArgs& p, char* smem, co
 
 // LORA (vst_gemm_lora, UnZipLoRA / LoRA projections): the down-projection u = x . Acat^T is accumulated inside the
 // k-loop from the A fragments already in registers, so no separate pass over x produces it.  Each k-tile also
-// stages Acat's 16 u columns of this tile ([16][64] bf16, one extra DMA per wave issued with slot Amq0: waves 0-1
-// move the two 1-KiB pieces, the others a zero piece into a sink, so every wave's vmcnt counts stay uniform); in I0
-// and I1 every wave adds one 16-row block of u (row block wc of the current row quadrant: 2 MFMAs each).  After the
+// stages Acat's 16 u columns of this tile ([16][64] bf16, two 1-KiB pieces issued with slot Amq0 by waves 0-1, one
+// each; waves 2-7 issue nothing, so the counted vmcnt waits that cover the piece are one higher on waves 0-1:
+// VST_P8_VMWAIT_LX); in J0 and J1 every wave adds one 16-row block of u (row block wc of the current row quadrant: 2
+// MFMAs each).  After the
 // loop u is rounded to bf16 (the reference's rounding point of lora_layer's down output), exchanged through LDS and
 // multiplied by the tile's up-projection columns of W (K + ub0 ...) as one extra 16x16x32 step per accumulator —
 // the same operands, in the same order, as the [x | u] . [W | V]^T k-tile it replaces.
@@ -570,15 +577,15 @@ __device__ __forceinline__ void tattn_epilogue(const GemmArgs& p, char* smem, co
 // so a 64-deep k-tile is one tap of one source.  Each A slot's DMAs are issued for consecutive k-tiles, so a (tap,
 // channel) cursor per slot advances by 64 per issue and its pieces' row bases are recomputed only when the tap or the
 // source changes (padding rows read out of range: zeros).  Same k order as the ring kernel's conv: same bits.
-template <int EPI, int BN, bool LORA = false, int PH = 3, int BM = 256, bool CONV = false, bool PERSIST = false>
+template <int EPI, int BN, bool LORA = false, int BM = 256, bool CONV = false, bool PERSIST = false>
 __global__ __launch_bounds__(512, 1) void gemm_p8_kernel(GemmArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   using Cfg = P8Cfg<BN, BM>;
   static_assert(!CONV || (!LORA && EPI == 0), "conv: plain epilogue");
   static_assert(EPI != 1 || BN == 256, "GEGLU needs 64-column [hidden | gate] blocks");
   static_assert(!LORA || EPI != 1, "in-GEMM LoRA: linear epilogue");
-  static_assert(!PERSIST || (!CONV && EPI != 4 && EPI != 5 && PH == 2 && (!LORA || (EPI == 0 && BN == 320))),
-                "persistent tiles: plain / GEGLU / GELU, and the in-GEMM LoRA on 128x320 tiles; PH 2");
+  static_assert(!PERSIST || (!CONV && EPI != 4 && EPI != 5 && (!LORA || (EPI == 0 && BN == 320))),
+                "persistent tiles: plain / GEGLU / GELU, and the in-GEMM LoRA on 128x320 tiles");
   static_assert(!(PERSIST && LORA) || Cfg::U_END <= 160 * 1024, "LoRA persistent LDS");
   static_assert(EPI != 5 || (BN == 256 && BM == 256 && !LORA && !CONV), "temporal attention epilogue: 256x256 tiles");
   static_assert(EPI != 4 || (BN == 192 && BM == 256), "cross-attention epilogue: 256 x 192 tiles (3 heads)");
@@ -593,24 +600,8 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_kernel(GemmArgs p) {
   // one A source (the launchers of the persistent, LoRA, cross- and temporal-attention variants pass no A2): the
   // loader's per-k-tile source selection is compiled out
   constexpr bool ONE_A = PERSIST || LORA || EPI == 4 || EPI == 5;
-  // DMM (A/B build VST_P8_DMM): a k-tile interval's LDS-DMAs issued inside the wave's MFMA segment, interleaved with
-  // its MFMAs, instead of in its load segment after the fragment reads (an LDS-DMA costs its wave ~60 cycles among
-  // bare MFMAs and 100-185 in a segment that carries 16 ds_read_b128, MI355X_MICROARCH.md constants table; the loop
-  // ablations put the load segments, not the MFMAs, on the critical path).  Same DMAs in the same order per wave, so
-  // every counted wait keeps its count; the slots they refill were read one interval earlier still.
-  // Off: in isolation the LoRA kernels gained 1-2 % per launch with it and the plain GEMMs lost 1-22 %
-  // (profiles/r5_ab_dma_in_mfma_negative.txt); on the LoRA kernels alone the whole step was 0.2 ms slower in two
-  // alternations (profiles/r5_ab_dma_in_mfma_lora_negative.txt).  VST_P8_DMM builds it everywhere (A/B).
-#if defined(VST_P8_DMM)
-  constexpr bool DMM = true;
-#else
-  constexpr bool DMM = false;
-#endif
-#ifdef VST_P8_LORA_B1E  // (A/B build: the in-GEMM LoRA kernels with the B1 placement of the plain GEMMs)
-  constexpr bool B1E = EPI != 1;
-#else
-  constexpr bool B1E = EPI != 1 && !LORA;  // PH = 2: B1 fragments read in J1's MFMA segment (run_segment2)
-#endif
+  // B1's fragments read in J1's MFMA segment (the header's B1E rule): every kernel but GEGLU and the in-GEMM LoRA ones
+  constexpr bool B1E = EPI != 1 && !LORA;
   constexpr int BUF = Cfg::BUF, RB1 = Cfg::RB1, NJ1 = Cfg::NJ1, NPB1 = Cfg::NPB1, NPA = Cfg::NPA;
   constexpr int HALF = Cfg::HALF, MQR = Cfg::MQR;
   // slot offsets inside a buffer: A0, A1, B0, B1
@@ -859,101 +850,9 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_kernel(GemmArgs p) {
         __builtin_amdgcn_mfma_f32_16x16x32_bf16(FB[j][h], fa[i][h], acc[(MQ) * MQR + i][(NQ) * 2 + j], 0, 0, 0); \
   }
 
-  // k-tiles [kb, ke) of the current tile into acc (zeroed here); ends with the LDS drained and free for reuse
-  auto run_segment = [&](int kb, int ke) {
-#pragma unroll
-    for (int i = 0; i < Cfg::MI; ++i)
-#pragma unroll
-      for (int j = 0; j < Cfg::NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    acc_u[0] = acc_u[1] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // Three barrier intervals per k-tile: I0 = {read Amq0, Bnq0} | Q(0,0) + Q(0,1) (32 MFMAs, fb1 = Bnq1(t) read in
-    // I2 of t-1); I1 = {read Amq1} | Q(1,1); I2 = {read Bnq1(t+1)} | Q(1,0).  (Four phases of 16 MFMAs, one per
-    // quadrant, measured 0.3 ms per step slower: 8 barriers per k-tile instead of 6, profiles/r2_ab_p8_3ph.txt.)  A slot read in interval I is refilled
-    // in interval I+2 (both halves' reads retired), and waited for in the interval before its first read:
-    //   I0(t): wait Amq1(t), issue Amq1(t+1);  I1(t): wait Bnq1(t+1), issue Bnq1(t+2);
-    //   I2(t): wait Amq0/Bnq0(t+1), issue Amq0/Bnq0(t+2).   (2 DMAs per slot per wave)
-    if constexpr (LORA) {  // V [BN][16] of this tile (older than every slot DMA: the first wait below covers it)
-      const int row = wid * 32 + (lane >> 1), n = n0_tile + row;
-      const bool ok = row < BN && n < p.N;
-      p8_dma16(make_rsrc(p.Wt, p.wtail_bytes), smem + Cfg::V_OFF + wid * 1024,
-               ok ? (int)(((uint32_t)n * p.ldw + p.K + ub0 + 8 * (lane & 1)) * 2u) : kOOB);
-      if constexpr (BN > 256) {  // rows 256 .. BN - 1 (waves 0-1; older than every slot DMA like the first piece)
-        const int row2 = 256 + row, n2 = n0_tile + row2;
-        if (wid < 2)
-          p8_dma16(make_rsrc(p.Wt, p.wtail_bytes), smem + Cfg::V_OFF + (8 + wid) * 1024,
-                   row2 < BN && n2 < p.N ? (int)(((uint32_t)n2 * p.ldw + p.K + ub0 + 8 * (lane & 1)) * 2u) : kOOB);
-      }
-    }
-    dma_slot(0, kb, ke, 0); dma_lora(kb, ke, true, 0); dma_slot(2, kb, ke, 0); dma_slot(3, kb, ke, 0);
-    dma_slot(1, kb, ke, 0); dma_slot(3, kb + 1, ke, 0); dma_slot(0, kb + 1, ke, 0); dma_lora(kb + 1, ke, true, 0);
-    dma_slot(2, kb + 1, ke, 0);
-    VST_P8_VMWAIT_LX(2 * NPA + 2 + NPB1);  // A0, (Acat,) B0, B1 of kb landed
-    p8_barrier();
-    VST_P8_STAMP(1)
-    read_b(kb & 1, 1, fb1);
-    if (late) p8_barrier();
-    if (late) __builtin_amdgcn_s_setprio(1);
-    auto ktile = [&](int t, auto fast_tag) {
-      constexpr bool FAST = decltype(fast_tag)::value;
-      auto dma = [&](int s_, int kt) {
-        if constexpr (FAST) dma_fast(s_, kt); else dma_slot(s_, kt, ke, 0);
-      };
-      const int buf = t & 1;
-      // I0
-      read_a(buf, 0);
-      read_b(buf, 0, fb0);
-      read_l(buf);
-      if (!(abl & 4)) VST_P8_VMWAIT_LX(NPA + 2 + NPB1);  // A1(t) landed
-      dma(1, t + 1);
-      p8_barrier();
-      lora_mfma(acc_u[0], 0);
-      VST_P8_QUAD(0, 0, fb0)
-      VST_P8_QUAD(0, 1, fb1)
-      lora_mfma(acc_u[0], 1);
-      p8_barrier();
-      // I1
-      read_a(buf, 1);
-      if (!(abl & 4)) VST_P8_VMWAIT_LX(2 * NPA + 2);  // B1(t+1) landed
-      dma(3, t + 2);
-      p8_barrier();
-      lora_mfma(acc_u[1], 0);
-      VST_P8_QUAD(1, 1, fb1)
-      lora_mfma(acc_u[1], 1);
-      p8_barrier();
-      // I2
-      read_b(buf ^ 1, 1, fb1);
-      if (!(abl & 4)) p8_vmwait<NPA + NPB1>();  // A0(t+1), B0(t+1) landed
-      dma(0, t + 2);
-      dma_lora(t + 2, ke, !FAST, 0);
-      dma(2, t + 2);
-      p8_barrier();
-      VST_P8_QUAD(1, 0, fb0)
-      p8_barrier();
-    };
-    int t = kb;
-    const int ke_fast = ke - 2 - (ktail ? 1 : 0);
-    for (; t < ke_fast; ++t) ktile(t, std::true_type{});
-    for (; t < ke; ++t) ktile(t, std::false_type{});
-    if (!late) p8_barrier();
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // the trailing zero DMAs land before LDS reuse
-    p8_barrier();
-  };
-  // PH = 2: two barrier intervals of 32 MFMAs per k-tile (24 at BN = 192), so every load segment of one wave group
-  // runs beside a full-length MFMA segment of the other, and each wave's DMAs split evenly over the two (the 3-interval
-  // schedule pairs its 4-DMA interval with a 16-MFMA one):
-  //   J0(t) = {read A0(t), B0(t), Acat(t); wait A1(t), B1(t+1); issue A1(t+1)}        | Q(0,0) + Q(0,1)
-  //   J1(t) = {read A1(t); wait A0/B0(t+1); issue B1(t+2), A0(t+2) (+Acat), B0(t+2)} | Q(1,1), read B1(t+1), Q(1,0)
-  // B1E (every kernel but GEGLU and the in-GEMM LoRA ones): B1's fragments are read inside J1's MFMA segment, after Q(1,1) frees fb1 (rounds
-  // 2-4 read them in J0's load segment, 16 ds_reads against J1's 8; the loop ablations showed the load segments, not
-  // the waits, idling the matrix core: profiles/r4_p8_loop_ablation.txt); so B1(t+1) is issued one interval earlier
-  // (J1(t-1), first of that segment's DMAs) and waited with A1(t) in J0(t), before both groups' J1(t) MFMA segments.
-  // GEGLU keeps   J0(t) = {read A0(t), B0(t), B1(t); wait A1(t); issue B1(t+1), A1(t+1)},  J1(t) = {read A1(t);
-  // wait A0/B0/B1(t+1); issue A0(t+2), B0(t+2)}, as do the LoRA kernels: in the step GEGLU measured 0.9 % slower
-  // with B1 moved and the LoRA kernels 1 %, the plain GEMMs and the convs 2-4 % faster (profiles/r4_ab_b1_j1.txt).  Every segment that reads
-  // LDS ends with its reads retired (lgkmcnt(0)) before its barrier, so a slot read in interval X is refilled from
-  // interval X + 1 on (WAR); a slot waited for in interval X is read in X + 1 (RAW, both groups' waits precede the
-  // barrier the later reader passes).  Same k order per accumulator as PH = 3: bitwise-equal results.
-  auto run_segment2 = [&](int kb, int ke, bool first) {
+  // k-tiles [kb, ke) of the current tile into acc (zeroed here), in the J0 / J1 schedule of the header; ends with the
+  // LDS drained and free for reuse (PERSIST: with the next tile's first k-tiles in flight instead)
+  auto run_segment = [&](int kb, int ke, bool first) {
 #pragma unroll
     for (int i = 0; i < Cfg::MI; ++i)
 #pragma unroll
@@ -989,7 +888,7 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_kernel(GemmArgs p) {
     VST_P8_STAMP(1)
     if (late) p8_barrier();
     if (late) __builtin_amdgcn_s_setprio(1);
-    auto ktile2 = [&](int t, auto fast_tag) {
+    auto ktile = [&](int t, auto fast_tag) {
       constexpr bool FAST = decltype(fast_tag)::value;
       auto dma = [&](int s_, int kt) {
         if constexpr (FAST) {
@@ -1018,21 +917,21 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_kernel(GemmArgs p) {
                    wid == 0 && p.bias && c < p.N ? c * 4 : kOOB);
         }
       }
+      // (J0's and J1's DMA issue stay lambdas: written out in line, the same statements compile to another register
+      // allocation in half of the kernels)
       auto dma_j0 = [&] {
         if (!(handed && t == kb)) {
           if constexpr (!B1E) dma(3, t + 1);
           dma(1, t + 1);
         }
       };
-      if constexpr (!DMM) dma_j0();
+      dma_j0();
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       p8_barrier();
       lora_mfma(acc_u[0], 0);
       VST_P8_QUAD(0, 0, fb0)
-      if constexpr (DMM) dma_j0();
       VST_P8_QUAD(0, 1, fb1)
       lora_mfma(acc_u[0], 1);
-      if constexpr (DMM) p8_interleave_dma<(2 + NJ1) * MQR * 2 + (LORA ? 2 : 0), (B1E ? 0 : NPB1) + NPA>();
       p8_barrier();
       // J1
       read_a(buf, 1);
@@ -1040,40 +939,31 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_kernel(GemmArgs p) {
       // PERSIST: every slot has issued its last DMA of this tile (A0 / B0 (B1E: B1) at J1(ke - 3), A1 (!B1E: B1) at
       // J0(ke - 2)), so the slots' source bases switch to the next tile here
       if (PERSIST && !FAST && t == ke - 2 && has_next) setup_tile(nm0, nn0);
-      // (DMM: the Acat piece, issued by waves 0-1 only, stays in the load segment, ahead of A0 / B0: a wave-dependent
-      // branch inside the MFMA segment would split it; every wait that counts it counts A0 and B0 as well)
-      static_assert(!(DMM && LORA && B1E), "DMM + LoRA: the Acat piece must stay younger than B1");
-      // the Acat piece of k-tile t + 2: past this tile's end (PERSIST) the next tile's first two (bases switched above)
-      auto dma_l = [&] {
-        if (PERSIST && !FAST && t + 2 >= ke && has_next) dma_lora(t + 2 - ke, ke, true, kofs + ke);
-        else dma_lora(t + 2, ke, !FAST, kofs);
-      };
       auto dma_j1 = [&] {
         if constexpr (B1E) dma(3, t + 2);
         dma(0, t + 2);
-        if constexpr (!DMM) dma_l();
+        // the Acat piece of k-tile t + 2: past this tile's end (PERSIST) the next tile's first two (bases switched above)
+        if (PERSIST && !FAST && t + 2 >= ke && has_next) dma_lora(t + 2 - ke, ke, true, kofs + ke);
+        else dma_lora(t + 2, ke, !FAST, kofs);
         dma(2, t + 2);
       };
-      if constexpr (DMM) dma_l();
-      if constexpr (!DMM) dma_j1();
+      dma_j1();
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       p8_barrier();
       lora_mfma(acc_u[1], 0);
       VST_P8_QUAD(1, 1, fb1)
-      if constexpr (DMM) dma_j1();
       if constexpr (B1E) {
         if (t + 1 < ke) read_b(buf ^ 1, 1, fb1);  // B1(t + 1), waited by both groups in J0(t)
       }
       VST_P8_QUAD(1, 0, fb0)
       lora_mfma(acc_u[1], 1);
-      if constexpr (DMM) p8_interleave_dma<(2 + NJ1) * MQR * 2 + (LORA ? 2 : 0), (B1E ? NPB1 : 0) + NPA + 2>();
       if constexpr (B1E) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       p8_barrier();
     };
     int t = kb;
     const int ke_fast = ke - 2 - (ktail ? 1 : 0);
-    for (; t < ke_fast; ++t) ktile2(t, std::true_type{});
-    for (; t < ke; ++t) ktile2(t, std::false_type{});
+    for (; t < ke_fast; ++t) ktile(t, std::true_type{});
+    for (; t < ke; ++t) ktile(t, std::false_type{});
     if (!late) p8_barrier();
     if constexpr (PERSIST) {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the next tile's k-tiles stay in flight
@@ -1135,7 +1025,7 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_kernel(GemmArgs p) {
       has_next = jn < cnt;
       if (has_next) tile_origin(beg + jn, nm0, nn0);
       bias_n0 = n0;
-      run_segment2(0, nk, first);
+      run_segment(0, nk, first);
 #ifdef VST_ABL_NOEPI  // diagnostics build only: no epilogue (a guarded store of every accumulator's first lane
                       // element keeps all the MFMAs live)
       {
@@ -1176,8 +1066,7 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_kernel(GemmArgs p) {
   }
   tile_origin(xcd_remap(blockIdx.x, ntiles), m0, n0);
   setup_tile(m0, n0);
-  if constexpr (PH == 2) run_segment2(0, nk, true);
-  else run_segment(0, nk);
+  run_segment(0, nk, true);
   VST_P8_STAMP(2)
   if constexpr (LORA) lora_post(smem);  // (the drained ring)
 #ifdef VST_ABL_NOEPI  // diagnostics build only: no epilogue of any kind (attention epilogues included)
@@ -1199,43 +1088,31 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_kernel(GemmArgs p) {
   VST_P8_STAMP(3)
 }
 
-// The k-loop schedule: 2 (two 32-MFMA intervals per k-tile, run_segment2; default) or 3 (three intervals,
-// run_segment; VST_P8_PH=3).  Measured (tools/p8_ph_ab.py, profiles/r4_p8_ph_ab.txt): 2-5 % faster in isolation on
-// the step's GEMM shapes, -0.4 ms per denoise step in two alternations; outputs bit-identical.
-static int p8_ph_env() {
-  static const int v = [] {
-    const char* e = getenv("VST_P8_PH");
-    return e ? atoi(e) : 2;
-  }();
-  return v;
-}
-
-template <int EPI, int BN, bool LORA, int PH, int BM, bool CONV = false>
-static int launch_p8_ph(const GemmArgs& a, hipStream_t s) {
+// One workgroup per tile: every conv, cross- and temporal-attention launch, and the shapes the persistent grid does not
+// take (p8_persist_applies).
+template <int EPI, int BN, bool LORA, int BM, bool CONV = false>
+static int launch_p8_tile_per_wg(const GemmArgs& a, hipStream_t s) {
   static bool attr = false;
   using Cfg = P8Cfg<BN, BM>;
   constexpr int lds = EPI == 4 ? 160 * 1024 : (LORA ? Cfg::LDS_LORA : Cfg::LDS);
   if (!attr) {
-    (void)hipFuncSetAttribute((const void*)gemm_p8_kernel<EPI, BN, LORA, PH, BM, CONV>,
+    (void)hipFuncSetAttribute((const void*)gemm_p8_kernel<EPI, BN, LORA, BM, CONV>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     attr = true;
   }
   const int nwg = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
-  hipLaunchKernelGGL((gemm_p8_kernel<EPI, BN, LORA, PH, BM, CONV>), dim3(nwg), dim3(512), lds, s, a);
+  hipLaunchKernelGGL((gemm_p8_kernel<EPI, BN, LORA, BM, CONV>), dim3(nwg), dim3(512), lds, s, a);
   return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
 }
 
 // Persistent tiles (default; VST_P8_PERSIST=0 restores one workgroup per tile): a grid of one workgroup per CU walks
 // the tiles; each tile's last two k-tiles stream the next tile's first two into the ring, so a tile's fill overlaps
-// the previous tile's epilogue.  Same bits.  Measured (tools/p8_ph_ab.py, profiles/r4_p8_persist_ab.txt): 0-15 %
+// the previous tile's epilogue.  Same bits.  Measured (tools/p8_variant_ab.py, profiles/r4_p8_persist_ab.txt): 0-15 %
 // faster per launch on the step's multi-round shapes (K = 320 / 640 most), the denoise step -0.9 ms same-box; the
 // convs stay on one workgroup per tile (their persistent variant spilled SGPRs and ran 2 % slower).
 static int g_p8_persist = -1;  // VST_P8_PERSIST, or vst_p8_persist (tests, A/B)
 static int p8_persist_env() {
-  if (g_p8_persist < 0) {
-    const char* e = getenv("VST_P8_PERSIST");
-    g_p8_persist = e ? atoi(e) : 1;
-  }
+  if (g_p8_persist < 0) g_p8_persist = env_int("VST_P8_PERSIST", 1);
   return g_p8_persist;
 }
 static int p8_cus() {
@@ -1249,11 +1126,11 @@ static int p8_cus() {
   return v;
 }
 
-// whether launch_gemm_p8 runs the persistent kernel for this shape: the 2-interval schedule, at least two tiles per
-// workgroup, K a multiple of 64 and >= 128 (the stream hands over two whole k-tiles), whole 8-column output chunks
-// (and one A source: launch_p8_epi)
+// whether launch_gemm_p8 runs the persistent kernel for this shape: at least two tiles per workgroup, K a multiple of
+// 64 and >= 128 (the stream hands over two whole k-tiles), whole 8-column output chunks (and one A source:
+// launch_p8_epi)
 bool p8_persist_applies(int M, int N, int K, int epi, int bn) {
-  if (!p8_persist_env() || p8_ph_env() != 2 || (epi != 0 && epi != 1 && epi != 3)) return false;
+  if (!p8_persist_env() || (epi != 0 && epi != 1 && epi != 3)) return false;
   const int bm = bn == 320 ? 128 : 256;
   const long tiles = (long)((M + bm - 1) / bm) * ((N + bn - 1) / bn);
   return tiles >= 2L * p8_cus() && K >= 128 && (K & 63) == 0 && (N % (epi == 1 ? 16 : 8)) == 0;
@@ -1263,14 +1140,14 @@ template <int EPI, int BN, int BM, bool LORA = false>
 static int launch_p8_persist(const GemmArgs& a, hipStream_t s) {
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute((const void*)gemm_p8_kernel<EPI, BN, LORA, 2, BM, false, true>,
+    (void)hipFuncSetAttribute((const void*)gemm_p8_kernel<EPI, BN, LORA, BM, false, true>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr = true;
   }
   const int ntiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
   const int grid = ntiles < p8_cus() ? (ntiles & ~7) : p8_cus();
   if (grid < 8) return VST_ERR_ARG;
-  hipLaunchKernelGGL((gemm_p8_kernel<EPI, BN, LORA, 2, BM, false, true>), dim3(grid), dim3(512), 160 * 1024, s, a);
+  hipLaunchKernelGGL((gemm_p8_kernel<EPI, BN, LORA, BM, false, true>), dim3(grid), dim3(512), 160 * 1024, s, a);
   return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
 }
 
@@ -1279,13 +1156,10 @@ static int launch_p8_persist(const GemmArgs& a, hipStream_t s) {
 // and out-projection 48 -> 43 us per launch, bitwise equal (profiles/r5_ab_lora_persist.txt).  VST_P8_LORA_PERSIST=0
 // restores one workgroup per tile (A/B).
 static int p8_lora_persist_env() {
-  static const int v = [] {
-    const char* e = getenv("VST_P8_LORA_PERSIST");
-    return e ? atoi(e) : 1;
-  }();
+  static const int v = env_int("VST_P8_LORA_PERSIST", 1);
   return v;
 }
-bool p8_lora_persist_on() { return p8_persist_env() && p8_ph_env() == 2 && p8_lora_persist_env(); }
+bool p8_lora_persist_on() { return p8_persist_env() && p8_lora_persist_env(); }
 
 // BN = 320 runs 128-row tiles (P8Cfg)
 template <int EPI, int BN, bool LORA = false>
@@ -1298,7 +1172,7 @@ static int launch_p8_epi(const GemmArgs& a, hipStream_t s) {
     if (p8_lora_persist_on() && !a.A2 && (size_t)a.M * a.ldc * 2 < 0x7fff0000u &&
         p8_persist_applies(a.M, a.N, a.K, EPI, BN))
       return launch_p8_persist<EPI, BN, BM, true>(a, s);
-  return p8_ph_env() == 2 ? launch_p8_ph<EPI, BN, LORA, 2, BM>(a, s) : launch_p8_ph<EPI, BN, LORA, 3, BM>(a, s);
+  return launch_p8_tile_per_wg<EPI, BN, LORA, BM>(a, s);
 }
 
 // in-GEMM LoRA down-projection (a.la set): epilogue 0 (bias / residual), bn 256 or 192
@@ -1323,11 +1197,10 @@ int launch_gemm_p8_xattn(const GemmArgs& a, hipStream_t s) {
 // implicit-GEMM 3x3 conv (GemmArgs conv geometry, Ctot % 64 == 0), epilogue 0; bn: 256, 192 or 320
 int launch_gemm_p8_conv(const GemmArgs& a, int bn, hipStream_t s) {
   if ((a.C1 & 63) || (a.C2 & 63) || a.K != 9 * (a.C1 + a.C2)) return VST_ERR_ARG;
-  const bool ph2 = p8_ph_env() == 2;
   switch (bn) {
-    case 256: return ph2 ? launch_p8_ph<0, 256, false, 2, 256, true>(a, s) : launch_p8_ph<0, 256, false, 3, 256, true>(a, s);
-    case 192: return ph2 ? launch_p8_ph<0, 192, false, 2, 256, true>(a, s) : launch_p8_ph<0, 192, false, 3, 256, true>(a, s);
-    case 320: return ph2 ? launch_p8_ph<0, 320, false, 2, 128, true>(a, s) : launch_p8_ph<0, 320, false, 3, 128, true>(a, s);
+    case 256: return launch_p8_tile_per_wg<0, 256, false, 256, true>(a, s);
+    case 192: return launch_p8_tile_per_wg<0, 192, false, 256, true>(a, s);
+    case 320: return launch_p8_tile_per_wg<0, 320, false, 128, true>(a, s);
     default: return VST_ERR_ARG;
   }
 }

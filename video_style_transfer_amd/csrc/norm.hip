@@ -17,6 +17,8 @@
 // (motion-module blocks add the PE to the normed input before attn1 and attn2).
 #include "vst_common.h"
 
+#include <limits.h>
+
 namespace vst {
 
 // Launch geometry shared by the stats and apply passes: grid (nchunk, nsamples), each workgroup owns
@@ -888,10 +890,7 @@ static inline int gn_rpc_rows(int rows_per_sample) {
   return std::max(8, std::min(256, (rows_per_sample + 7) / 8));
 }
 static inline int gn_rpc(int nsamples, int rows_per_sample) {
-  static const long long target = [] {
-    const char* e = getenv("VST_GN_TARGET");  // tuning only (tools/norm_bench.py)
-    return e ? std::max(1LL, atoll(e)) : 256LL;
-  }();
+  static const long long target = std::max(1, env_int("VST_GN_TARGET", 256));  // tuning only (tools/norm_bench.py)
   const long long total = (long long)nsamples * rows_per_sample;
   return (int)std::max<long long>(8, std::min<long long>(256, (total + target - 1) / target));
 }
@@ -1036,15 +1035,13 @@ extern "C" int vst_layernorm(const void* x, int ldx, int C, int rows, const floa
 #define VST_LNG(LPR, RIT)                                                                                      \
   hipLaunchKernelGGL((layernorm_g_kernel<LPR, RIT>), dim3((rows + 4 * (64 / LPR) * RIT - 1) / (4 * (64 / LPR) * RIT)), \
                      blk, 0, s, (const bf16_t*)x, ldx, C, rows, gamma, beta, eps, pe, pe_div, pe_mod, (bf16_t*)y, ldy)
-  static const bool generic_only = getenv("VST_LN_GENERIC") != nullptr;  // A/B switch (tools/ab_bench.sh)
+  // A/B switch (tools/ab_bench.sh): on when the variable is set at all, whatever its value
+  static const bool generic_only = env_int("VST_LN_GENERIC", INT_MIN) != INT_MIN;
   const bool g16 = !generic_only && ((uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)pe) % 16 == 0;
   // RIT = row passes per wave whose loads are all in flight before the first reduction.  C = 1280 (M = 8192 rows in the
   // step): 1 pass, 1024 workgroups: 9.8 -> 9.2 us per launch graph-timed, step -0.15..-0.2 ms same-box
   // (profiles/r3_ab_ln_rit.txt); VST_LN_RIT (1 / 2 / 4) overrides every width for A/B.
-  static const int rit_env = [] {
-    const char* e = getenv("VST_LN_RIT");
-    return e ? atoi(e) : 0;
-  }();
+  static const int rit_env = env_int("VST_LN_RIT", 0);
 #define VST_LNG_RIT(LPR, DEF)                                        \
   {                                                                  \
     const int rit = rit_env ? rit_env : (DEF);                       \

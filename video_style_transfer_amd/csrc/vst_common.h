@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 namespace vst {
 
@@ -32,6 +33,13 @@ struct Fit31 {
     return (uint32_t)bytes;
   }
 };
+
+// Host side: the integer value of environment variable `name`, `dflt` when it is unset.  Not cached: every runtime
+// switch keeps its own static (or its settable global) at the call site.
+inline int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, uint32_t bytes) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)bytes, 0x00020000);
