@@ -154,6 +154,18 @@ int vst_spatial_attention(const void* q, int ldq, const void* k, const void* v, 
  * bits either way (tests / A/B). */
 int vst_sa_self(int on);
 
+/* Cross-frame (extended) spatial self-attention, head_dim 64 (no line of the reference does this; the definition is
+ * this project's, DESIGN.md "Cross-frame spatial self-attention").  Token (clip b, frame f, pixel p) at row
+ * (b*F + f)*N + p.  The keys/values of query frame f are the N tokens of the frames [f, s1(f), s2(f)] of the same
+ * clip, in that order, under ONE softmax per head; src >= 0 is that frame, -2 the previous frame max(f - 1, 0), -1
+ * none; an entry equal to an earlier entry of the list is dropped.  Arithmetic and rounding points are
+ * vst_spatial_attention's self-attention (every frame of the list walked in 64-key tiles of its own).  Returns 1
+ * before any launch for head_dim != 64, a stride that is no multiple of 8, a NULL pointer, src >= F or < -2,
+ * src1 == -1 with src2 != -1, two equal sources, or byte extents past 2^31 - 1.  No workspace, no atomics, no lse. */
+int vst_spatial_attention_frames(const void* q, int ldq, const void* k, const void* v, int ldkv, void* o, int ldo,
+                                 int nclip, int F, int heads, int N, int src1, int src2, int head_dim, float scale,
+                                 void* stream);
+
 /* Frame-axis attention (motion module / TemporalTransformerBlock, animatediff/temporal_transformer.py:66-68):
  * token (clip b, frame f, pixel p) at row (b*F + f)*HW + p; F <= 32; head_dim in {8,16,32,40,64,80,160}. */
 int vst_temporal_attention(const void* q, const void* k, const void* v, int ldqkv, void* o, int ldo, int nclip,

@@ -97,6 +97,7 @@ class AnimateDiffAttnProcessor2_0:
                  **kwargs):
         fused_residual = kwargs.pop("_vst_residual", None)
         lora_u = kwargs.pop("_vst_lora_u", None)  # x @ Acat^T of the q(/k/v) ops, from K.layer_norm_lora
+        cross_frame = kwargs.pop("_vst_cross_frame", None)  # attn1 only: (CrossFrameAttention, frames per clip)
         if attn.spatial_norm is not None or attn.group_norm is not None or attn.norm_cross:
             raise NotImplementedError("spatial_norm/group_norm/norm_cross are inert for SDXL (attention_processor.py:30-60)")
         if attention_mask is not None:
@@ -111,9 +112,19 @@ class AnimateDiffAttnProcessor2_0:
         hd = inner // heads
         x = hidden_states.reshape(batch * N, C)
         if encoder_hidden_states is None:
+            if cross_frame is not None and hd != 64:
+                raise K._lib.VstError("cross_frame: the cross-frame attention kernel is specialised for head_dim 64")
             qkv = run_ops(x, build_ops([attn.to_q, attn.to_k, attn.to_v], s), u=lora_u)
-            o = K.spatial_attention(qkv[:, :inner], qkv[:, inner:2 * inner], qkv[:, 2 * inner:], batch, heads, N, N,
-                                    1, scale=hd ** -0.5) if hd == 64 else _generic_attention(qkv, batch, heads, N)
+            if cross_frame is not None:
+                # the frame's own tokens plus those of the source frames of the same clip, read in place
+                cf, Fr = cross_frame
+                o = K.spatial_attention_frames(qkv[:, :inner], qkv[:, inner:2 * inner], qkv[:, 2 * inner:],
+                                               batch // Fr, Fr, heads, N, cf.sources, scale=hd ** -0.5)
+            elif hd == 64:
+                o = K.spatial_attention(qkv[:, :inner], qkv[:, inner:2 * inner], qkv[:, 2 * inner:], batch, heads, N,
+                                        N, 1, scale=hd ** -0.5)
+            else:
+                o = _generic_attention(qkv, batch, heads, N)
         else:
             enc = encoder_hidden_states
             be, L, D = enc.shape

@@ -22,10 +22,6 @@
 
 namespace vst {
 
-constexpr int SA_KT = 64;                         // keys per tile
-constexpr int SA_TILE = SA_KT * 64 * 2;           // 8 KiB
-constexpr int SA_LDS = 4 * SA_TILE;               // K,V double-buffered
-
 typedef __attribute__((address_space(3))) void sa_lds_void;
 
 // One 1-KiB LDS-DMA piece: 64 lanes x 16 B, lane-linear in LDS at `lds_piece` (wave-uniform).

@@ -38,6 +38,11 @@ __device__ __forceinline__ bf16x8 pack_p8(float a0, float a1, float a2, float a3
   return __builtin_bit_cast(bf16x8, u);
 }
 
+// K/V tile geometry of the head_dim-64 spatial attention kernels (attention.hip, attention_frames.hip)
+constexpr int SA_KT = 64;                // keys per tile
+constexpr int SA_TILE = SA_KT * 64 * 2;  // 8 KiB
+constexpr int SA_LDS = 4 * SA_TILE;      // K,V double-buffered
+
 // K tile: [64 keys][64 d] bf16, 128-B rows, GEMM swizzle (ds_read_b128 row reads)
 __device__ __forceinline__ int k_off(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
 // V tile: [64 keys][64 d], swizzle chosen for conflict-free ds_read_b64_tr_b16 over 8-row groups

@@ -55,6 +55,8 @@ class _Rec:
         return self
 
     def __exit__(self, *a):
+        if a and a[0] is not None:
+            return  # the library refused the call (VstError): nothing was launched, nothing is recorded
         if _PROF is not None and self.s is not None:
             e = torch.cuda.Event(enable_timing=True)
             e.record()
@@ -660,6 +662,62 @@ def spatial_attention(q, k, v, nbatch, heads, Nq, Nk, kv_div=1, out=None, scale=
               2.0 * 64 * heads * (2 * nbatch * Nq + 2 * (nbatch // kv_div) * Nk), None, (nbatch * heads, Nq, Nk)):
         _lib.call("vst_spatial_attention", _p(q), _ld(q), _p(k), _p(v), k.stride(0), _p(out), _ld(out), nbatch,
                   heads, Nq, Nk, kv_div, 64, float(scale), _p(lse), _stream())
+    return out
+
+
+def frame_source(src) -> int:
+    """The scalar the C ABI takes for one cross-frame source: "first" -> 0, "prev" -> -2, a frame index -> itself."""
+    if src == "first":
+        return 0
+    if src == "prev":
+        return -2
+    if isinstance(src, bool) or not isinstance(src, int) or src < 0:
+        raise ValueError(f"cross-frame source {src!r}: expected \"first\", \"prev\" or a frame index >= 0")
+    return src
+
+
+def frame_list(f: int, F: int, sources) -> list[int]:
+    """Key/value frames of query frame f of an F-frame clip under `sources` (DESIGN.md "Cross-frame spatial
+    self-attention"): [f, src1(f), src2(f)] with "prev" = max(f - 1, 0), minus every entry equal to an earlier one."""
+    if not 0 <= f < F:
+        raise ValueError(f"frame {f} outside 0..{F - 1}")
+    out = [f]
+    for src in sources:
+        s = frame_source(src)
+        if s >= F:
+            raise ValueError(f"cross-frame source {s} >= F = {F}")
+        s = max(f - 1, 0) if s == -2 else s
+        if s not in out:
+            out.append(s)
+    return out
+
+
+def spatial_attention_frames(q, k, v, nclip, F, heads, N, sources, scale=None, out=None):
+    """Cross-frame spatial self-attention, head_dim 64: rows (b*F + f)*N + p; frame f of a clip attends to the tokens
+    of frame_list(f, F, sources) of the same clip under one softmax.  q/k/v: [nclip*F*N, >= heads*64] views (k and v
+    share a row stride); sources: up to two of "first", "prev" or a frame index.  Bad sources reach the library, which
+    refuses them before any launch (VstError, status 1)."""
+    for n, t in (("q", q), ("k", k), ("v", v)):
+        _dev(t, BF16, n)
+    rows = nclip * F * N
+    if q.shape[0] != rows or k.shape[0] != rows or v.shape[0] != rows:
+        raise _lib.VstError("spatial_attention_frames: rows != nclip*F*N")
+    if k.stride(0) != v.stride(0):
+        raise _lib.VstError("spatial_attention_frames: k and v must share a row stride")
+    src = [frame_source(s) for s in sources]
+    if len(src) > 2:
+        raise _lib.VstError(f"spatial_attention_frames: {len(src)} sources; at most two")
+    src1, src2 = (src + [-1, -1])[:2]
+    if out is None:
+        out = torch.empty((rows, heads * 64), dtype=BF16, device=q.device)
+    _out(out, (rows, heads * 64), BF16, "out", "spatial_attention_frames")
+    scale = 0.125 if scale is None else scale
+    ok = all(s < F for s in src) and len(set(src)) == len(src)  # else the library refuses; nothing to count
+    keys = sum(len(frame_list(f, F, sources)) for f in range(F)) * N if ok else 0
+    with _Rec("spatial_attention_frames", 4.0 * 64 * heads * N * nclip * keys, 2.0 * 64 * heads * 4 * rows,
+              lambda: "sa_frames_kernel", (nclip * F * heads, N, keys // F)):
+        _lib.call("vst_spatial_attention_frames", _p(q), _ld(q), _p(k), _p(v), k.stride(0), _p(out), _ld(out), nclip,
+                  F, heads, N, src1, src2, 64, float(scale), _stream())
     return out
 
 

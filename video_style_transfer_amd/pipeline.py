@@ -20,7 +20,7 @@ import torch
 
 from . import kernels as K
 from .scheduler import EulerDiscreteScheduler
-from .unet_motion import TemporalContext, UNetMotionModel, check_clip_length
+from .unet_motion import TemporalContext, UNetMotionModel, as_cross_frame, check_clip_length, check_cross_frame
 
 BF16 = torch.bfloat16
 
@@ -30,7 +30,7 @@ class AnimateDiffDenoiser:
                  num_inference_steps: int = 50, guidance_scale: float = 7.5, device=None,
                  scheduler: Optional[EulerDiscreteScheduler] = None, use_graph: bool = True, shard=None,
                  num_clips: int = 1, context_length: Optional[int] = None, context_stride: int = 4,
-                 context_weighting: str = "pyramid"):
+                 context_weighting: str = "pyramid", cross_frame=None):
         """`num_clips` clips are denoised together (the reference loop is one clip, B=1).
         `shard` (frame_shard.FrameShard): this process denoises frames [f0, f0 + F/P) of every clip and
         exchanges with the other ranks inside every motion module.
@@ -38,11 +38,16 @@ class AnimateDiffDenoiser:
         forked streams measured slower, 76.6 vs 72.8 ms per step, profiles/r3_ab_cfg_streams.txt; removed).
         `context_length` (with `context_stride`, `context_weighting`): clips of more than context_length frames run
         their motion modules inside sliding windows of that many frames (unet_motion.TemporalContext, DESIGN.md "Long
-        clips"); without it a clip longer than the motion modules' positional table is refused here."""
+        clips"); without it a clip longer than the motion modules' positional table is refused here.
+        `cross_frame` (e.g. ("first",) or ("first", "prev"); unet_motion.CrossFrameAttention, DESIGN.md "Cross-frame
+        spatial self-attention"): every frame's spatial self-attention also attends to those frames of its clip.  It
+        is static, so a captured step replays it unchanged."""
         self.context = None if context_length is None else TemporalContext(int(context_length), int(context_stride),
                                                                            context_weighting)
         if unet.config.motion_modules:
             check_clip_length(num_frames, unet.config.motion_max_seq_length, self.context)
+        self.cross_frame = as_cross_frame(cross_frame)
+        check_cross_frame(unet, num_frames, self.cross_frame, shard)
         self.unet = unet
         self.nclips = num_clips
         self.shard = shard
@@ -96,7 +101,7 @@ class AnimateDiffDenoiser:
         K.pack_latents(self.lat, self.x, sigmas=self.sigmas, step_idx=self.step_idx, ncopy=self.ncopy)
         emb = self.unet.embed(self.timesteps, self.pooled, self.time_ids, B, step_idx=self.step_idx)
         noise = self.unet.forward_tokens(self.x, B, self.F, self.h, self.w, emb, self.enc, shard=self.shard,
-                                         temporal_context=self.context)
+                                         temporal_context=self.context, cross_frame=self.cross_frame)
         K.euler_cfg_step(noise, self.lat, self.sigmas, self.step_idx, guidance=self.guidance, ncopy=self.ncopy)
         K.step_advance(self.step_idx, self.num_steps)
 

@@ -157,6 +157,52 @@ def check_clip_length(F: int, max_seq_length: int, tc: Optional[TemporalContext]
                               f"context_length (<= {max_seq_length}) to attend inside sliding windows")
 
 
+@dataclass(frozen=True)
+class CrossFrameAttention:
+    """Cross-frame (extended) spatial self-attention (DESIGN.md "Cross-frame spatial self-attention"): attn1 of every
+    spatial transformer block attends to its own frame's tokens plus those of the `sources` frames of the same clip,
+    under one softmax.  One or two distinct sources, each "first" (frame 0), "prev" (frame max(f - 1, 0)) or a frame
+    index.  Inactive on single-frame clips, which run exactly as without it."""
+    sources: tuple = ("first",)
+
+    def __post_init__(self):
+        src = (self.sources,) if isinstance(self.sources, (str, int)) else tuple(self.sources)
+        object.__setattr__(self, "sources", src)
+        if not 1 <= len(src) <= 2:
+            raise ValueError(f"cross_frame: {len(src)} sources; one or two")
+        if len({K.frame_source(s) for s in src}) != len(src):
+            raise ValueError(f"cross_frame: sources {src} are not distinct")
+
+    def active(self, F: int) -> bool:
+        return F > 1
+
+
+def as_cross_frame(cf) -> Optional[CrossFrameAttention]:
+    """None, a CrossFrameAttention, or its sources (("first",), "prev", 3, ...)."""
+    return cf if cf is None or isinstance(cf, CrossFrameAttention) else CrossFrameAttention(cf)
+
+
+def check_cross_frame(model, F: int, cf: Optional[CrossFrameAttention], shard=None):
+    """Refuse, before any launch, a cross_frame option the spatial self-attention cannot honour on a clip of F
+    frames (all ranks' frames together)."""
+    if cf is None or not cf.active(F):
+        return
+    if shard is not None and shard.world > 1:
+        raise K._lib.VstError("cross_frame: a source frame's keys/values live on another rank under frame sharding "
+                              f"(world {shard.world}); run the clip unsharded")
+    for s in cf.sources:
+        if isinstance(s, int) and s >= F:
+            raise K._lib.VstError(f"cross_frame: source frame {s} >= F = {F}")
+    bad = model.__dict__.get("_vst_cross_frame_bad")
+    if bad is None:  # head sizes are fixed at construction: scanned once per model
+        bad = [n for n, m in model.named_modules()
+               if isinstance(m, BasicTransformerBlock) and not m.temporal and m.attn1.dim_head != 64]
+        model.__dict__["_vst_cross_frame_bad"] = bad
+    if bad:
+        raise K._lib.VstError(f"cross_frame: the cross-frame attention kernel is specialised for head_dim 64; "
+                              f"{bad[0]}.attn1 has another")
+
+
 @dataclass
 class FwdCtx:
     B: int                 # clips in the batch (CFG-batched: 2x)
@@ -167,6 +213,7 @@ class FwdCtx:
     shard: Optional[object] = None  # frame_shard.FrameShard when the clip's frames span ranks (F is per rank)
     temb: Optional[dict] = None     # ResnetBlock2D -> fp32 [B, Cout] view of the batched time_emb_proj output
     temporal_context: Optional[TemporalContext] = None  # motion attention inside sliding windows when F > length
+    cross_frame: Optional[CrossFrameAttention] = None   # spatial attn1 also attends to source frames when F > 1
 
 
 # --------------------------------------------------------------------------------------- blocks
@@ -262,7 +309,9 @@ class BasicTransformerBlock(nn.Module):
         else:
             scale = ctx.cross_kwargs.get("scale", 1.0)
             n, u = self.norm1.run_lora(x, input_lora_ops(self.attn1, True, scale))
-            x = self.attn1(n.view(nimg, N, C), _vst_residual=x, _vst_lora_u=u, **ctx.cross_kwargs).view(-1, C)
+            cf = ctx.cross_frame
+            kw = dict(_vst_cross_frame=(cf, ctx.F)) if cf is not None and cf.active(ctx.F) else {}
+            x = self.attn1(n.view(nimg, N, C), _vst_residual=x, _vst_lora_u=u, **kw, **ctx.cross_kwargs).view(-1, C)
             n, u = self.norm2.run_lora(x, input_lora_ops(self.attn2, False, scale))
             x = self.attn2(n.view(nimg, N, C), encoder_hidden_states=ctx.enc, _vst_residual=x, _vst_lora_u=u,
                            **ctx.cross_kwargs).view(-1, C)
@@ -637,11 +686,15 @@ class UNetMotionModel(nn.Module):
 
     # ---- core (NHWC tokens) -----------------------------------------------------------------
     def forward_tokens(self, x, B, F, h, w, emb_silu, enc, cross_kwargs=None, shard=None, fusion_world=None,
-                       temporal_context=None):
+                       temporal_context=None, cross_frame=None):
         """x: [B*F*h*w, in_channels] bf16 -> noise prediction [B*F*h*w, out_channels] bf16.
         With `shard` (frame_shard.FrameShard), F is this rank's frames of each clip.  `fusion_world` P (default: the
         shard's world size, else 1): take the shape-dependent fusion decisions a P-way frame-sharded rank takes
-        (kernels.fusion_world), so an unsharded forward equals a P-way sharded one bit for bit."""
+        (kernels.fusion_world), so an unsharded forward equals a P-way sharded one bit for bit.  `cross_frame`
+        (CrossFrameAttention or its sources): attn1 of the spatial transformer blocks also attends to the source
+        frames of the same clip."""
+        cross_frame = as_cross_frame(cross_frame)
+        check_cross_frame(self, F * (shard.world if shard is not None else 1), cross_frame, shard)
         if self.config.motion_modules:
             check_clip_length(F * (shard.world if shard is not None else 1), self.config.motion_max_seq_length,
                               temporal_context)
@@ -651,7 +704,7 @@ class UNetMotionModel(nn.Module):
         K.colstat_reset()
         with K.row_invariant(), K.fusion_world(fusion_world):
             ctx = FwdCtx(B, F, emb_silu, enc, cross_kwargs or {}, shard, self.batched_temb(emb_silu),
-                         temporal_context)
+                         temporal_context, cross_frame)
             nimg = B * F
             H, W = h, w
             x = self.conv_in.run(x, nimg, H, W)
@@ -667,14 +720,18 @@ class UNetMotionModel(nn.Module):
 
     def forward(self, sample, timestep, encoder_hidden_states, timestep_cond=None, attention_mask=None,
                 cross_attention_kwargs=None, added_cond_kwargs=None, return_dict=True, frame_shard=None,
-                fusion_world=None, temporal_context=None, **kwargs):
+                fusion_world=None, temporal_context=None, cross_frame=None, **kwargs):
         """diffusers UNetMotionModel.forward signature (inference_animatediff.py:110-121).  With
         `frame_shard` (frame_shard.FrameShard) `sample` holds this rank's frames of each clip; `fusion_world`: see
         forward_tokens; `temporal_context` (TemporalContext): the motion modules attend inside sliding windows when the
-        clip is longer than its length."""
+        clip is longer than its length; `cross_frame` (CrossFrameAttention or its sources, e.g. ("first",)): attn1 of the
+        spatial transformer blocks also attends to the source frames of the same clip."""
         if not sample.is_cuda:
             raise K._lib.VstError("UNetMotionModel: sample is on CPU; the HIP path has no CPU fallback")
         B, Cin, F, h, w = sample.shape
+        cross_frame = as_cross_frame(cross_frame)
+        check_cross_frame(self, F * (frame_shard.world if frame_shard is not None else 1), cross_frame,
+                          frame_shard)
         if self.config.motion_modules:
             check_clip_length(F * (frame_shard.world if frame_shard is not None else 1),
                               self.config.motion_max_seq_length, temporal_context)
@@ -691,6 +748,7 @@ class UNetMotionModel(nn.Module):
         x = torch.empty(B * F * h * w, Cin, dtype=BF16, device=dev)
         K.pack_latents(sample.float().contiguous(), x)
         y = self.forward_tokens(x, B, F, h, w, emb_silu, enc, cross_attention_kwargs, shard=frame_shard,
-                                fusion_world=fusion_world, temporal_context=temporal_context)
+                                fusion_world=fusion_world, temporal_context=temporal_context,
+                                cross_frame=cross_frame)
         out = y.view(B, F, h, w, -1).permute(0, 4, 1, 2, 3).contiguous().to(sample.dtype)
         return UNetMotionOutput(out) if return_dict else (out,)
