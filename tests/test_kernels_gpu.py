@@ -474,6 +474,35 @@ def test_sa_self_bitwise_equals_spatial_attn(cuda, K, nb, heads, Nq, Nk, qs):
     assert torch.equal(outs[1][2], outs[0][2])
 
 
+@pytest.mark.parametrize("N", [77, 130])
+def test_causal_attention(cuda, K, N):
+    """vst_causal_attention (the text encoders' attention, called as text_encoder.py calls it: q/k/v column views of one
+    fused buffer).  Row q equals, bit for bit, row q of the unmasked kernel over the first q + 1 keys: a wholly masked
+    tile leaves the running state alone (alpha = exp2(0) = 1, P = 0).  N = 130: three key tiles with a 2-key tail.
+    The whole output is also held against an fp32 causal softmax."""
+    from video_style_transfer_amd import _lib
+    nb, heads = 2, 2
+    C = heads * 64
+    g = torch.Generator().manual_seed(N)
+    qkv = rnd(nb * N, 3 * C, gen=g)
+    qd = qkv.to(cuda)
+    out = torch.empty((nb * N, C), dtype=torch.bfloat16, device=cuda)
+    _lib.call("vst_causal_attention", qd.data_ptr(), qd.stride(0), qd[:, C:].data_ptr(), qd[:, 2 * C:].data_ptr(),
+              qd.stride(0), out.data_ptr(), out.stride(0), nb, heads, N, 64, 0.125, K._stream())
+    for qi in [0, 63, 64, N - 1] + ([127, 128] if N == 130 else []):
+        kv = qd.view(nb, N, 3 * C)[:, :qi + 1, C:].reshape(nb * (qi + 1), 2 * C).contiguous()
+        part = K.spatial_attention(qd[:, :C], kv[:, :C], kv[:, C:], nb, heads, N, qi + 1)
+        assert torch.equal(out.view(nb, N, C)[:, qi], part.view(nb, N, C)[:, qi]), qi
+
+    def heads_of(t):
+        return t.float().view(nb, N, heads, 64).transpose(1, 2)
+
+    s = heads_of(qkv[:, :C]) @ heads_of(qkv[:, C:2 * C]).transpose(-1, -2) / 8.0
+    s = s.masked_fill(torch.ones(N, N, dtype=torch.bool).triu(1), float("-inf"))
+    ref = torch.softmax(s, -1) @ heads_of(qkv[:, 2 * C:])
+    check(out, ref.transpose(1, 2).reshape(nb * N, C), name="causal")
+
+
 @pytest.mark.parametrize("nclip,Fr,HW,C", [(2, 16, 64, 320), (1, 32, 16, 640), (1, 16, 8, 1280), (1, 32, 4, 1280), (3, 5, 7, 64),
                                            (2, 16, 1, 128)])
 @pytest.mark.parametrize("qs", [1.0, 3.0])

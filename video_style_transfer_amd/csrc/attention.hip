@@ -18,7 +18,10 @@
 //    Tokens stay in the spatial layout [(b*F + f)*HW + p, C]; the kernel reads the frame
 //    axis with stride HW rows, so no permute/contiguous copies are made on either side.
 //    One wave per (b, p, head); F <= 32; head_dim = C/8 (40/80/160 for SDXL).
-#include "attn_common.h"
+//
+// The tile step of the two head_dim-64 forward kernels here and the softmax / P / V^T pieces of the two frame-axis
+// forwards (here and temporal_window.hip) are in attn_fwd.h.
+#include "attn_fwd.h"
 
 namespace vst {
 
@@ -31,7 +34,7 @@ __device__ __forceinline__ void sa_dma16(__amdgpu_buffer_rsrc_t r, char* lds_pie
 }
 
 // PRE = 0: K/V tiles of 64 keys double-buffered through registers (long key ranges: the 32x32 / 64x64 levels).
-// PRE = n (1..4, Nk <= 64 n): the whole K/V of the (batch, head) is brought into LDS up front by LDS-DMA -- every
+// PRE = n (1 or 2, Nk <= 64 n): the whole K/V of the (batch, head) is brought into LDS up front by LDS-DMA -- every
 // load of the workgroup in flight at once, no per-tile barrier -- for the 77 text tokens of cross-attention, where
 // the short key loop left one HBM latency exposed per tile (dispatch: up to two tiles, see vst_spatial_attention).  The DMA writes each
 // 8-row piece lane-linearly, so each lane fetches the global chunk that the tile's swizzle (k_off / v_off) puts at
@@ -48,68 +51,25 @@ __global__ __launch_bounds__(256, 2) void spatial_attn_kernel(
   const int qblk = wg % nqb;
   const int bh = wg / nqb;
   const int h = bh % heads, b = bh / heads;
-  const int bkv = b / kv_div;
-  const int fr = lane & 15, g = lane >> 4;
+  const int kvrow0 = (b / kv_div) * Nk;
 
   const auto rq = make_rsrc(Q, q_bytes);
   const auto rk = make_rsrc(K, kv_bytes);
   const auto rv = make_rsrc(V, kv_bytes);
 
-  // Q^T fragments (B operand of S^T = K.Q^T): lane (col q, group g) holds Q[q][32kk + 8g .. +7]
   bf16x8 qf[2][2];
   const int qbase = qblk * 128 + wid * 32;
-#pragma unroll
-  for (int qb = 0; qb < 2; ++qb) {
-    const int q = qbase + qb * 16 + fr;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      const int off = q < Nq ? ((b * Nq + q) * ldq + h * 64 + kk * 32 + g * 8) * 2 : kOOB;
-      qf[qb][kk] = __builtin_bit_cast(bf16x8, buf_load16(rq, off));
-    }
-  }
-
-  // K/V staging: 64 rows x 8 chunks = 512 chunks per tile; 2 per thread per operand
-  const int sc = tid & 7, sr = tid >> 3;  // rows sr, sr+32
-  u32x4 kreg[2], vreg[2];
-  auto load_kv = [&](int t) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int key = t * SA_KT + sr + 32 * i;
-      const int off = key < Nk ? ((bkv * Nk + key) * ldkv + h * 64 + sc * 8) * 2 : kOOB;
-      kreg[i] = buf_load16(rk, off);
-      vreg[i] = buf_load16(rv, off);
-    }
-  };
-  auto store_kv = [&](int buf) {
-    char* Ks = smem + buf * 2 * SA_TILE;
-    char* Vs = Ks + SA_TILE;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int row = sr + 32 * i;
-      *reinterpret_cast<u32x4*>(Ks + k_off(row, sc)) = kreg[i];
-      *reinterpret_cast<u32x4*>(Vs + v_off(row, sc)) = vreg[i];
-    }
-  };
-
-  f32x4 o[4][2];  // O^T accumulators [d-block][q-block]: lane col q, rows d = 16db + 4g + i
-#pragma unroll
-  for (int d = 0; d < 4; ++d)
-#pragma unroll
-    for (int qb = 0; qb < 2; ++qb) o[d][qb] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float mrun[2] = {-INFINITY, -INFINITY};
-  float lrun[2] = {0.f, 0.f};
+  sa_load_q(qf, rq, b * Nq, qbase, Nq, ldq, h, lane);
+  SaStage stg;
+  SaState st;
+  sa_init(st);
+  int voff[4];
+  sa_voffs(voff, lane);
 
   const int nt = (Nk + SA_KT - 1) / SA_KT;
-  // V^T fragment reads: lane 4q'+p' of group g reads row 4g + q' (+16, +32, +48), cols 16db + 4p'
-  int voff[4];
-#pragma unroll
-  for (int db = 0; db < 4; ++db) {
-    const int li = lane & 15, r0 = g * 4 + (li >> 2), col = db * 16 + (li & 3) * 4;
-    voff[db] = v_off(r0, col >> 3) + (col & 7) * 2;
-  }
   if constexpr (PRE == 0) {
-    load_kv(0);
-    store_kv(0);
+    stg.load(rk, rv, kvrow0, 0, Nk, ldkv, h, tid);
+    stg.store(smem, 0, tid);
   } else {
     // pieces: tile t, operand (K, V), 8-row piece p; wave w issues p = w and p = w + 4 of every tile and operand
     const int prow = lane >> 3, pslot = lane & 7;
@@ -120,7 +80,7 @@ __global__ __launch_bounds__(256, 2) void spatial_attn_kernel(
         const int row = (wid + 4 * pp) * 8 + prow;
         const int key = t * SA_KT + row;
         const int ck = pslot ^ ((row >> 1) & 7), cv = pslot ^ (((row >> 1) & 3) << 1);
-        const int base = (bkv * Nk + key) * ldkv + h * 64;
+        const int base = (kvrow0 + key) * ldkv + h * 64;
         char* dst = smem + t * 2 * SA_TILE + (wid + 4 * pp) * 1024;
         sa_dma16(rk, dst, key < Nk ? (base + ck * 8) * 2 : kOOB);
         sa_dma16(rv, dst + SA_TILE, key < Nk ? (base + cv * 8) * 2 : kOOB);
@@ -131,119 +91,25 @@ __global__ __launch_bounds__(256, 2) void spatial_attn_kernel(
 
   for (int t = 0; t < nt; ++t) {
     const int cur = PRE ? t : (t & 1);
-    if (PRE == 0 && t + 1 < nt) load_kv(t + 1);
+    if (PRE == 0 && t + 1 < nt) stg.load(rk, rv, kvrow0, t + 1, Nk, ldkv, h, tid);
     const char* Ks = smem + cur * 2 * SA_TILE;
-    const char* Vs = Ks + SA_TILE;
-
-    // ---- S^T = K Q^T : s[kt][qb], lane col q, rows key = 16kt + 4g + i ----
-    f32x4 s[4][2];
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt) {
-      bf16x8 kf[2];
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk)
-        kf[kk] = *reinterpret_cast<const bf16x8*>(Ks + k_off(kt * 16 + fr, kk * 4 + g));
-#pragma unroll
-      for (int qb = 0; qb < 2; ++qb) {
-        f32x4 a{0.f, 0.f, 0.f, 0.f};
-        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[0], qf[qb][0], a, 0, 0, 0);
-        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[1], qf[qb][1], a, 0, 0, 0);
-        s[kt][qb] = a;
-      }
-    }
-    // ---- mask keys beyond Nk (last tile); causal: keys after the query (CLIP text self-attention) ----
-    if ((t + 1) * SA_KT > Nk || causal) {
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int key = t * SA_KT + kt * 16 + g * 4 + i;
-#pragma unroll
-          for (int qb = 0; qb < 2; ++qb)
-            if (key >= Nk || (causal && key > qbase + qb * 16 + fr)) s[kt][qb][i] = -INFINITY;
-        }
-    }
-    // ---- online softmax (lane-local rows; reduce over the 4 g-lanes) ----
-    float alpha[2];
-#pragma unroll
-    for (int qb = 0; qb < 2; ++qb) {
-      float mx = -INFINITY;
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) mx = fmaxf(mx, s[kt][qb][i]);
-      mx = group_max(mx);
-      const float mnew = fmaxf(mrun[qb], mx);
-      alpha[qb] = fast_exp2((mrun[qb] - mnew) * scale_log2);
-      mrun[qb] = mnew;
-      const float mb = mnew * scale_log2;
-      float ls = 0.f;
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float pv = fast_exp2(s[kt][qb][i] * scale_log2 - mb);
-          s[kt][qb][i] = pv;
-          ls += pv;
-        }
-      lrun[qb] = lrun[qb] * alpha[qb] + ls;
-    }
-#pragma unroll
-    for (int d = 0; d < 4; ++d)
-#pragma unroll
-      for (int qb = 0; qb < 2; ++qb) o[d][qb] *= alpha[qb];
-
-    // ---- O^T += V^T P^T: two 32-key k-steps st (P tiles 2st -> elements 0-3, 2st+1 -> 4-7) ----
-    bf16x8 pf[2][2];
-#pragma unroll
-    for (int st = 0; st < 2; ++st)
-#pragma unroll
-      for (int qb = 0; qb < 2; ++qb)
-        pf[st][qb] = pack_p8(s[2 * st][qb][0], s[2 * st][qb][1], s[2 * st][qb][2], s[2 * st][qb][3],
-                             s[2 * st + 1][qb][0], s[2 * st + 1][qb][1], s[2 * st + 1][qb][2], s[2 * st + 1][qb][3]);
-#pragma unroll
-    for (int db = 0; db < 4; ++db) {
-      const char* vp = Vs + voff[db];  // rows +16 / +32 keep the swizzle: immediate offsets 2048 / 4096
-#pragma unroll
-      for (int st = 0; st < 2; ++st) {
-        const bf16x8 vf = cat_tr(ds_read_tr(vp + st * 4096), ds_read_tr(vp + st * 4096 + 2048));
-#pragma unroll
-        for (int qb = 0; qb < 2; ++qb)
-          o[db][qb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[st][qb], o[db][qb], 0, 0, 0);
-      }
-    }
+    // keys beyond Nk (last tile); causal: keys after the query
+    sa_tile(Ks, Ks + SA_TILE, qf, voff, scale_log2, st, lane, [&](f32x4(&s)[4][2]) {
+      if ((t + 1) * SA_KT > Nk || causal) sa_mask(s, t, Nk, lane, causal ? qbase : -1);
+    });
     if constexpr (PRE == 0) {
-      if (t + 1 < nt) store_kv(cur ^ 1);
+      if (t + 1 < nt) stg.store(smem, cur ^ 1, tid);
       __syncthreads();
     }
   }
-
-  // ---- finalize: O[q][d] = O^T[d][q] / l ----
-#pragma unroll
-  for (int qb = 0; qb < 2; ++qb) {
-    float l = lrun[qb];
-    l += __shfl_xor(l, 16);
-    l += __shfl_xor(l, 32);
-    const float inv = 1.0f / l;
-    const int q = qbase + qb * 16 + fr;
-    if (q >= Nq) continue;
-    if (lse && g == 0) lse[(size_t)bh * Nq + q] = mrun[qb] * scale_log2 + __log2f(l);  // training: P = exp2(s sl2 - lse)
-    bf16_t* orow = O + (size_t)(b * Nq + q) * ldo + h * 64;
-#pragma unroll
-    for (int db = 0; db < 4; ++db) {
-      const f32x4 v = o[db][qb] * inv;
-      u32x2 w{pack2bf(v[0], v[1]), pack2bf(v[2], v[3])};
-      *reinterpret_cast<u32x2*>(orow + db * 16 + g * 4) = w;
-    }
-  }
+  sa_finish(st, O, ldo, b * Nq, qbase, Nq, h, lse, (size_t)bh * Nq, scale_log2, lane);
 }
 
 // ---------------------------------------------------------------------------------
 // Self-attention over long key ranges (the 16x16 and 32x32 levels: 256 / 1024 keys), the default for
-// vst_spatial_attention's self-attention: spatial_attn_kernel<0>'s arithmetic (S^T = K.Q^T with the query on the lane,
-// online softmax against the running max, P rounded to bf16 unnormalised, O^T = V^T.P^T from transposed V reads, K/V
-// tiles double-buffered through registers, 4 waves x 32 queries) without its causal mask, whose code spilled 31 SGPRs
-// into VGPR lanes (~29 v_readlane / v_writelane per 64-key tile).  32x32: 148-156 -> 145-147 us, 16x16: 26.2-26.6 ->
+// vst_spatial_attention's self-attention: spatial_attn_kernel<0>'s loop (the same sa_tile, K/V tiles double-buffered
+// through registers) without kv_div and without the causal mask, whose code in the general kernel spilled 31 SGPRs into
+// VGPR lanes (~29 v_readlane / v_writelane per 64-key tile).  32x32: 148-156 -> 145-147 us, 16x16: 26.2-26.6 ->
 // 25.4 us (profiles/r5_ab_sa_self.txt).  At head_dim 64 the softmax VALU, not the MFMA, bounds the loop (per tile and
 // wave 32 MFMAs = 512 cycles against ~700-1,100 cycles of vector issue).  Not kept (same file):
 //  - a deferred rescale (the running max moves only when a tile's max exceeds it by 2^8; the alpha exp2s and the 32 O
@@ -253,194 +119,48 @@ __global__ __launch_bounds__(256, 2) void spatial_attn_kernel(
 //  - 8 waves x 32 queries (one K/V fill per 256 queries): 128 VGPRs with spills, or one workgroup per CU; 16x16 31 us;
 //  - S_{t+1} issued before tile t's softmax (software pipelining inside the wave): 208 VGPRs, 2 waves per SIMD, 32x32
 //    169 us.
-template <int NW>
-__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(3))) void sa_self_kernel(
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void sa_self_kernel(
     const bf16_t* __restrict__ Q, int ldq, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V, int ldkv,
     bf16_t* __restrict__ O, int ldo, int nbatch, int heads, int Nq, int Nk, float scale_log2, uint32_t q_bytes,
     uint32_t kv_bytes, float* __restrict__ lse) {
-  constexpr int NCH = 512 / (NW * 64);  // 16-B chunks per thread and operand per tile (64 rows x 8 chunks)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int nqb = (Nq + NW * 32 - 1) / (NW * 32);
+  const int nqb = (Nq + 127) / 128;
   const int wg = xcd_remap(blockIdx.x, nqb * heads * nbatch);
   const int qblk = wg % nqb;
   const int bh = wg / nqb;
   const int h = bh % heads, b = bh / heads;
-  const int fr = lane & 15, g = lane >> 4;
+  const int kvrow0 = b * Nk;
 
   const auto rq = make_rsrc(Q, q_bytes);
   const auto rk = make_rsrc(K, kv_bytes);
   const auto rv = make_rsrc(V, kv_bytes);
 
   bf16x8 qf[2][2];
-  const int qbase = qblk * (NW * 32) + wid * 32;
-#pragma unroll
-  for (int qb = 0; qb < 2; ++qb) {
-    const int q = qbase + qb * 16 + fr;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      const int off = q < Nq ? ((b * Nq + q) * ldq + h * 64 + kk * 32 + g * 8) * 2 : kOOB;
-      qf[qb][kk] = __builtin_bit_cast(bf16x8, buf_load16(rq, off));
-    }
-  }
-
-  const int sc = tid & 7, sr = tid >> 3;  // rows sr + NW * 8 * i
-  u32x4 kreg[NCH], vreg[NCH];
-  const int kvrow0 = b * Nk;
-  auto load_kv = [&](int t) {
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-      const int key = t * SA_KT + sr + NW * 8 * i;
-      const int off = key < Nk ? ((kvrow0 + key) * ldkv + h * 64 + sc * 8) * 2 : kOOB;
-      kreg[i] = buf_load16(rk, off);
-      vreg[i] = buf_load16(rv, off);
-    }
-  };
-  auto store_kv = [&](int buf) {
-    char* Ks = smem + buf * 2 * SA_TILE;
-    char* Vs = Ks + SA_TILE;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-      const int row = sr + NW * 8 * i;
-      *reinterpret_cast<u32x4*>(Ks + k_off(row, sc)) = kreg[i];
-      *reinterpret_cast<u32x4*>(Vs + v_off(row, sc)) = vreg[i];
-    }
-  };
-
-  f32x4 o[4][2];
-#pragma unroll
-  for (int d = 0; d < 4; ++d)
-#pragma unroll
-    for (int qb = 0; qb < 2; ++qb) o[d][qb] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float mrun[2] = {-INFINITY, -INFINITY};
-  float mb[2] = {0.f, 0.f};  // mrun * scale_log2
-  float lrun[2] = {0.f, 0.f};
+  const int qbase = qblk * 128 + wid * 32;
+  sa_load_q(qf, rq, b * Nq, qbase, Nq, ldq, h, lane);
+  SaStage stg;
+  SaState st;
+  sa_init(st);
+  int voff[4];
+  sa_voffs(voff, lane);
 
   const int nt = (Nk + SA_KT - 1) / SA_KT;
-  int voff[4];
-#pragma unroll
-  for (int db = 0; db < 4; ++db) {
-    const int li = lane & 15, r0 = g * 4 + (li >> 2), col = db * 16 + (li & 3) * 4;
-    voff[db] = v_off(r0, col >> 3) + (col & 7) * 2;
-  }
-  load_kv(0);
-  store_kv(0);
+  stg.load(rk, rv, kvrow0, 0, Nk, ldkv, h, tid);
+  stg.store(smem, 0, tid);
   __syncthreads();
 
   for (int t = 0; t < nt; ++t) {
     const int cur = t & 1;
-    if (t + 1 < nt) load_kv(t + 1);
+    if (t + 1 < nt) stg.load(rk, rv, kvrow0, t + 1, Nk, ldkv, h, tid);
     const char* Ks = smem + cur * 2 * SA_TILE;
-    const char* Vs = Ks + SA_TILE;
-
-    f32x4 s[4][2];
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt) {
-      bf16x8 kf[2];
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk)
-        kf[kk] = *reinterpret_cast<const bf16x8*>(Ks + k_off(kt * 16 + fr, kk * 4 + g));
-#pragma unroll
-      for (int qb = 0; qb < 2; ++qb) {
-        f32x4 a{0.f, 0.f, 0.f, 0.f};
-        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[0], qf[qb][0], a, 0, 0, 0);
-        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[1], qf[qb][1], a, 0, 0, 0);
-        s[kt][qb] = a;
-      }
-    }
-    if ((t + 1) * SA_KT > Nk) {
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const bool dead = t * SA_KT + kt * 16 + g * 4 + i >= Nk;
-#pragma unroll
-          for (int qb = 0; qb < 2; ++qb)
-            if (dead) s[kt][qb][i] = -INFINITY;
-        }
-    }
-    // The softmax is written expression for expression as spatial_attn_kernel's (max from -inf, P = exp2(s sl2 - mb),
-    // l = l alpha + sum P), so both kernels round alike and their outputs are bit-identical
-    // (test_kernels_gpu.py::test_sa_self_bitwise_equals_spatial_attn): one forward arithmetic for inference and
-    // training.  (Round 5 wrote P with an explicit fmaf and l as two roundings; that moved outputs by ulps.)
-    float mx[2], alpha[2];
-#pragma unroll
-    for (int qb = 0; qb < 2; ++qb) {
-      float m = -INFINITY;
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) m = fmaxf(m, s[kt][qb][i]);
-      mx[qb] = group_max(m);
-    }
-#pragma unroll
-    for (int qb = 0; qb < 2; ++qb) {
-      const float mnew = fmaxf(mrun[qb], mx[qb]);
-      alpha[qb] = fast_exp2((mrun[qb] - mnew) * scale_log2);
-      mrun[qb] = mnew;
-      mb[qb] = mnew * scale_log2;
-#ifdef VST_SA_SCALAR
-#pragma unroll
-      for (int d = 0; d < 4; ++d)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[d][qb][e] = o[d][qb][e] * alpha[qb];
-#else
-#pragma unroll
-      for (int d = 0; d < 4; ++d) o[d][qb] *= alpha[qb];
-#endif
-    }
-#pragma unroll
-    for (int qb = 0; qb < 2; ++qb) {
-      float ls = 0.f;
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float pv = fast_exp2(s[kt][qb][i] * scale_log2 - mb[qb]);
-          s[kt][qb][i] = pv;
-          ls += pv;
-        }
-      lrun[qb] = lrun[qb] * alpha[qb] + ls;
-    }
-    bf16x8 pf[2][2];
-#pragma unroll
-    for (int st = 0; st < 2; ++st)
-#pragma unroll
-      for (int qb = 0; qb < 2; ++qb)
-        pf[st][qb] = pack_p8(s[2 * st][qb][0], s[2 * st][qb][1], s[2 * st][qb][2], s[2 * st][qb][3],
-                             s[2 * st + 1][qb][0], s[2 * st + 1][qb][1], s[2 * st + 1][qb][2], s[2 * st + 1][qb][3]);
-#pragma unroll
-    for (int db = 0; db < 4; ++db) {
-      const char* vp = Vs + voff[db];
-#pragma unroll
-      for (int st = 0; st < 2; ++st) {
-        const bf16x8 vf = cat_tr(ds_read_tr(vp + st * 4096), ds_read_tr(vp + st * 4096 + 2048));
-#pragma unroll
-        for (int qb = 0; qb < 2; ++qb)
-          o[db][qb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[st][qb], o[db][qb], 0, 0, 0);
-      }
-    }
-    if (t + 1 < nt) store_kv(cur ^ 1);
+    sa_tile(Ks, Ks + SA_TILE, qf, voff, scale_log2, st, lane, [&](f32x4(&s)[4][2]) {
+      if ((t + 1) * SA_KT > Nk) sa_mask(s, t, Nk, lane);
+    });
+    if (t + 1 < nt) stg.store(smem, cur ^ 1, tid);
     __syncthreads();
   }
-
-#pragma unroll
-  for (int qb = 0; qb < 2; ++qb) {
-    float l = lrun[qb];
-    l += __shfl_xor(l, 16);
-    l += __shfl_xor(l, 32);
-    const float inv = 1.0f / l;
-    const int q = qbase + qb * 16 + fr;
-    if (q >= Nq) continue;
-    if (lse && g == 0) lse[(size_t)bh * Nq + q] = mrun[qb] * scale_log2 + __log2f(l);  // training: P = exp2(s sl2 - lse)
-    bf16_t* orow = O + (size_t)(b * Nq + q) * ldo + h * 64;
-#pragma unroll
-    for (int db = 0; db < 4; ++db) {
-      const f32x4 v = o[db][qb] * inv;
-      u32x2 w{pack2bf(v[0], v[1]), pack2bf(v[2], v[3])};
-      *reinterpret_cast<u32x2*>(orow + db * 16 + g * 4) = w;
-    }
-  }
+  sa_finish(st, O, ldo, b * Nq, qbase, Nq, h, lse, (size_t)bh * Nq, scale_log2, lane);
 }
 
 // ---------------------------------------------------------------------------------
@@ -511,62 +231,18 @@ __global__ __launch_bounds__(512) void temporal_attn_kernel(
 #pragma unroll
   for (int j = 0; j < NV; ++j)  // chunk idx = f * CPR + c sits at byte idx * 16; the pad chunks get zeros
     *reinterpret_cast<u32x4*>(vs + (lane + 64 * j) * 16) = vreg[j];
-  // mask keys >= F
-#pragma unroll
-  for (int a = 0; a < NT; ++a)
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (a * 16 + g * 4 + i >= F) {
-#pragma unroll
-        for (int c = 0; c < NT; ++c) s[a][c][i] = -INFINITY;
-      }
-  // softmax per query column
+  // keys >= F masked; softmax per query column
   float inv[NT];
-#pragma unroll
-  for (int c = 0; c < NT; ++c) {
-    float mx = -INFINITY;
-#pragma unroll
-    for (int a = 0; a < NT; ++a)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) mx = fmaxf(mx, s[a][c][i]);
-    mx = fmaxf(mx, __shfl_xor(mx, 16));
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
-    const float mb = mx * scale_log2;
-    float ls = 0.f;
-#pragma unroll
-    for (int a = 0; a < NT; ++a)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const float pv = fast_exp2(s[a][c][i] * scale_log2 - mb);
-        s[a][c][i] = pv;
-        ls += pv;
-      }
-    ls += __shfl_xor(ls, 16);
-    ls += __shfl_xor(ls, 32);
-    inv[c] = 1.0f / ls;
-  }
+  ta_softmax<NT>(s, F, scale_log2, inv, lane);
   // V staging stores (this wave only) complete before the transposed reads
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
 
-  // ---- O^T = V^T P^T (one 32-key k-step; for NT=1 the upper 16 keys are zero) ----
+  // ---- O^T = V^T P^T (one 32-key k-step) ----
   bf16x8 pf[NT];
-#pragma unroll
-  for (int c = 0; c < NT; ++c) {
-    if (NT == 2)
-      pf[c] = pack_p8(s[0][c][0], s[0][c][1], s[0][c][2], s[0][c][3], s[NT - 1][c][0], s[NT - 1][c][1],
-                      s[NT - 1][c][2], s[NT - 1][c][3]);
-    else
-      pf[c] = pack_p8(s[0][c][0], s[0][c][1], s[0][c][2], s[0][c][3], 0.f, 0.f, 0.f, 0.f);
-  }
-  const int li = lane & 15;
+  ta_pack_p<NT>(s, pf);
 #pragma unroll
   for (int db = 0; db < DB; ++db) {
-    const int r0 = g * 4 + (li >> 2);
-    const int colb = (db * 16 + (li & 3) * 4) * 2;
-    const s16x4 lo = ds_read_tr(vs + r0 * VROW + colb);
-    s16x4 hi = s16x4{0, 0, 0, 0};
-    if (NT == 2) hi = ds_read_tr(vs + (r0 + 16) * VROW + colb);
-    const bf16x8 vf = cat_tr(lo, hi);
+    const bf16x8 vf = ta_vt_frag<NT>(vs, VROW, db, lane);
 #pragma unroll
     for (int c = 0; c < NT; ++c) {
       f32x4 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[c], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
@@ -1186,16 +862,13 @@ extern "C" int vst_spatial_attention(const void* q, int ldq, const void* k, cons
   // sa_self_kernel, bit-identical to spatial_attn_kernel<0>; vst_sa_self(0) / VST_SA_SELF=0 restores the latter
   if (pre == 0 && kv_div == 1 && sa_self_on()) {
     const dim3 g2(((Nq + 127) / 128) * heads * nbatch);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(sa_self_kernel<4>), g2, dim3(256), SA_LDS, st, (const bf16_t*)q, ldq,
-                       (const bf16_t*)k, (const bf16_t*)v, ldkv, (bf16_t*)o, ldo, nbatch, heads, Nq, Nk, sl2, qb,
-                       kvb_v, lse);
+    hipLaunchKernelGGL(sa_self_kernel, g2, dim3(256), SA_LDS, st, (const bf16_t*)q, ldq, (const bf16_t*)k,
+                       (const bf16_t*)v, ldkv, (bf16_t*)o, ldo, nbatch, heads, Nq, Nk, sl2, qb, kvb_v, lse);
     return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
   }
   switch (pre) {
     case 1: VST_SA_LAUNCH(1); break;
     case 2: VST_SA_LAUNCH(2); break;
-    case 3: VST_SA_LAUNCH(3); break;
-    case 4: VST_SA_LAUNCH(4); break;
     default: VST_SA_LAUNCH(0); break;
   }
 #undef VST_SA_LAUNCH

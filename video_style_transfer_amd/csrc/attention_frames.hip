@@ -7,9 +7,14 @@
 // (frame 0 with source 0 attends to itself only).  No line of the reference does this; the definition is this
 // project's.
 //
-// sa_frames_kernel is sa_self_kernel's loop (attention.hip), expression for expression: 4 waves x 32 queries, 64-key
-// K/V tiles double-buffered through registers into LDS, S^T = K.Q^T with the query on the lane, online softmax from
-// -inf against the running max, P rounded to bf16 unnormalised, O^T = V^T.P^T from transposed V reads.  The only change
+// sa_frames_kernel is sa_self_kernel's loop (attention.hip; its tile step is sa_tile, attn_fwd.h), expression for
+// expression: 4 waves x 32 queries, 64-key K/V tiles double-buffered through registers into LDS, S^T = K.Q^T with the
+// query on the lane, online softmax from -inf against the running max, P rounded to bf16 unnormalised, O^T = V^T.P^T
+// from transposed V reads.  It keeps a copy of that step instead of calling sa_tile: as a shell over attn_fwd.h
+// (same registers and occupancy, 150 VGPRs, no spills) it measured 0.7 % / 1.1 % slower at the 32^2 level with one /
+// two sources, outside the parent's own 0.3 % run-to-run range (profiles/attn_core_2026-10-19.json); the compiler then
+// keeps the load cursor's tile index in a VGPR and forms the K/V addresses in 5 VALU instructions instead of 2.  A
+// change to sa_tile's arithmetic must be repeated here; test_frames_bits_equal_plain_kernel fails otherwise.  The only change
 // is where a tile's rows come from: the key-tile loop walks the frames of the list one after the other, every frame in
 // 64-key tiles of its own (keys are not packed across frames, so with N % 64 != 0 every frame's last tile is masked
 // separately), and the running max, sum and O carry across a frame boundary exactly as across two tiles of one frame.

@@ -6,8 +6,8 @@
 // frame WITHOUT the positional term; the kernel adds the fp32 table row of the position INSIDE the window
 // (pos_*[j] = pe[j] . W^T) and rounds to bf16, so one q/k/v GEMM serves every window a frame belongs to.
 //
-// One wave per (clip, pixel, head), as in temporal_attn_kernel, whose S^T = K Q^T / softmax / O^T = V^T P^T core this
-// repeats instruction for instruction (same scale_log2 / fast_exp2 softmax, P rounded to bf16, fp32 accumulation).
+// One wave per (clip, pixel, head), as in temporal_attn_kernel, with which it shares the softmax, the P packing and the
+// transposed V read (attn_fwd.h), so a window's attention rounds as that kernel's does.
 // The wave walks its windows in ascending order.  Its lane layout ties a lane to a position j inside the window, not
 // to a frame, so
 //   - the table rows a lane adds are the same in every window: they are loaded once into registers;
@@ -17,7 +17,7 @@
 //     the others go back to the ring.
 // The q/k/v rows that consecutive windows share are read again; the same wave touched them one window earlier.
 // No workspace, no atomics.
-#include "attn_common.h"
+#include "attn_fwd.h"
 
 namespace vst {
 
@@ -160,40 +160,9 @@ __global__ __launch_bounds__((64 * TW<NT, D>::WAVES)) void temporal_attn_windowe
 #pragma unroll
     for (int j = 0; j < NV; ++j)  // chunk idx = f * CPR + c sits at byte idx * 16; the pad chunks get zeros
       *reinterpret_cast<u32x4*>(vs + (lane + 64 * j) * 16) = add_pos(vreg[j], tv[j]);
-    // mask keys >= L
-#pragma unroll
-    for (int a = 0; a < NT; ++a)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (a * 16 + g * 4 + i >= L) {
-#pragma unroll
-          for (int c = 0; c < NT; ++c) s[a][c][i] = -INFINITY;
-        }
-    // softmax per query column
+    // keys >= L masked; softmax per query column
     float inv[NT];
-#pragma unroll
-    for (int c = 0; c < NT; ++c) {
-      float mx = -INFINITY;
-#pragma unroll
-      for (int a = 0; a < NT; ++a)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) mx = fmaxf(mx, s[a][c][i]);
-      mx = fmaxf(mx, __shfl_xor(mx, 16));
-      mx = fmaxf(mx, __shfl_xor(mx, 32));
-      const float mb = mx * scale_log2;
-      float ls = 0.f;
-#pragma unroll
-      for (int a = 0; a < NT; ++a)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float pv = fast_exp2(s[a][c][i] * scale_log2 - mb);
-          s[a][c][i] = pv;
-          ls += pv;
-        }
-      ls += __shfl_xor(ls, 16);
-      ls += __shfl_xor(ls, 32);
-      inv[c] = 1.0f / ls;
-    }
+    ta_softmax<NT>(s, L, scale_log2, inv, lane);
     // the blend weight of this lane's query positions, and 1 / sum w for those that finish in this window
     float wj[NT], rws[NT];
 #pragma unroll
@@ -205,25 +174,12 @@ __global__ __launch_bounds__((64 * TW<NT, D>::WAVES)) void temporal_attn_windowe
     // V staging stores (this wave only) complete before the transposed reads
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
 
-    // ---- O^T = V^T P^T (one 32-key k-step; for NT=1 the upper 16 keys are zero) ----
+    // ---- O^T = V^T P^T (one 32-key k-step) ----
     bf16x8 pf[NT];
-#pragma unroll
-    for (int c = 0; c < NT; ++c) {
-      if (NT == 2)
-        pf[c] = pack_p8(s[0][c][0], s[0][c][1], s[0][c][2], s[0][c][3], s[NT - 1][c][0], s[NT - 1][c][1],
-                        s[NT - 1][c][2], s[NT - 1][c][3]);
-      else
-        pf[c] = pack_p8(s[0][c][0], s[0][c][1], s[0][c][2], s[0][c][3], 0.f, 0.f, 0.f, 0.f);
-    }
-    const int li = lane & 15;
+    ta_pack_p<NT>(s, pf);
 #pragma unroll
     for (int db = 0; db < DB; ++db) {
-      const int r0 = g * 4 + (li >> 2);
-      const int colb = (db * 16 + (li & 3) * 4) * 2;
-      const s16x4 lo = ds_read_tr(vs + r0 * VROW + colb);
-      s16x4 hi = s16x4{0, 0, 0, 0};
-      if (NT == 2) hi = ds_read_tr(vs + (r0 + 16) * VROW + colb);
-      const bf16x8 vf = cat_tr(lo, hi);
+      const bf16x8 vf = ta_vt_frag<NT>(vs, VROW, db, lane);
 #pragma unroll
       for (int c = 0; c < NT; ++c) {
         f32x4 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[c], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
