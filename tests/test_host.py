@@ -279,6 +279,27 @@ def test_gemm_kernel_policy_host_only():
     assert name(32768, 640, 5760, 2) == "gemm_p8<128x320,conv>"
 
 
+def test_gemm_policy_table():
+    """The dispatch plan against a recorded table (tests/golden/gemm_policy.json, made by tools/gemm_policy_table.py
+    from the library of the commit before the plan function existed): every launch of the denoise step and the VAE
+    at the default policy, every forced tile code at a small and a full-grid shape per kind, and the settable knobs
+    crossed at five shapes.  Rows with a "was" field are the corrected ones ("GEMM dispatch").  The
+    queries run in a child process without the VST_GEMM_* / VST_P8_* variables, which the library reads once."""
+    import json
+    import subprocess
+    import sys
+    golden = os.path.join(ROOT, "tests", "golden", "gemm_policy.json")
+    rows = json.load(open(golden))
+    assert 500 <= len(rows) <= 1500
+    env = {k: v for k, v in os.environ.items() if not k.startswith(("VST_GEMM_", "VST_P8_", "VST_LIB_AB"))}
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "gemm_policy_table.py"), "--rows", golden],
+                         env=env, check=True, capture_output=True, text=True, timeout=120).stdout
+    got = json.loads(out.splitlines()[-1])
+    assert len(got) == len(rows)
+    bad = [(r, g) for r, g in zip(rows, got) if r["name"] != g]
+    assert not bad, f"{len(bad)} of {len(rows)} rows differ, first: {bad[:3]}"
+
+
 def test_text_encoder_surface_cpu():
     """The SDXL text towers keep transformers' module tree / state-dict keys (a checkpoint's text_encoder and
     text_encoder_2 load unchanged, with or without the "text_model." prefix recent transformers drop), and refuse

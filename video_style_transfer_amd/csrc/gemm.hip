@@ -24,9 +24,13 @@
 // reads); XCD-aware tile order; fp32 LDS-staged epilogue with 16-byte coalesced stores.
 // Host-side heuristic (vst_gemm): BN=64 when the 128x128 grid would run in few waves on
 // 256 CUs (tail effect), split-K (blockIdx.z) when even that grid cannot fill the chip.
+#include <cstdio>
 #include <cstdlib>
+#include <mutex>
+#include <set>
+#include <string>
 
-#include "gemm_common.h"
+#include "gemm_plan.h"
 
 namespace vst {
 
@@ -565,12 +569,41 @@ static int launch_one(const GemmArgs& a, hipStream_t s, int splits) {
   return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
 }
 
+// ---------------- dispatch: one query -> one plan (gemm_plan.h) ----------------
+// Everything the choice of a kernel depends on.  vst_gemm_ex and conv3x3_impl fill it from their arguments;
+// vst_gemm_kernel_name, which sees sizes only, assumes one A source, a packed C inside the 32-bit offsets (a larger
+// one is launched as row chunks), for convs C1 = K / 9 and C2 = 0, and for kind 0 no epilogue at all.
+struct GemmQuery {
+  int M, N, K, K1;
+  bool two_src;       // A split along K into two sources (convs: channel concat)
+  int epi;            // GemmPlan::epi
+  bool no_epi;        // one source, no bias / row bias / residual / activation: all the skinny kernel can do
+  int tile, splits;   // the caller's: public tile code 0-10 (0 auto), splits 0 auto / >= 1 forced
+  size_t slab_bytes;  // usable split-K workspace
+  size_t c_bytes;     // byte extent of C (M * ldc * 2)
+  bool conv, vec, colstat;  // 3x3 conv; its channels allow 16-byte loads; column statistics requested
+  int C1, C2;
+};
 
-constexpr int kCUs = 256;
+GemmKnobs& gemm_knobs() {
+  static GemmKnobs k = {env_int("VST_GEMM_P8", -1),      env_int("VST_P8_BN", 0),        env_int("VST_P8_320", 0),
+                        env_int("VST_P8_CONV", 1),       env_int("VST_P8_PERSIST", 1),   env_int("VST_P8_LORA_PERSIST", 1),
+                        env_int("VST_LORA_INGEMM", 1),   env_int("VST_XATTN_FUSE", 1),   env_int("VST_GEMM_PERSIST", -1),
+                        env_int("VST_GEMM_GROUP_M", 0),  env_int("VST_GEMM_ABLATE", 0)};
+  return k;
+}
 
-// tile / split choice.  tile: 0 auto, 1 = 128x128, 2 = 128x64.  splits: 0 auto, >=1 forced.
-// tile codes: 1 = 128x128, 2 = 128x64 (gemm_kernel, 4 waves, up to 2 WG/CU);
-//             3 = 256x256, 4 = 256x128 (gemm_big_kernel, 8 waves, LDS-DMA staging, 1 WG/CU)
+constexpr int kCUs = 256;  // the CU count choose() and p8_auto were tuned against
+
+int device_cus() {
+  static int n = 0;
+  if (n <= 0) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = kCUs;
+  }
+  return n;
+}
 
 // 256x160 ring tiles for Cout = 320 / 640 convs on full grids: Cout splits into 160-column tiles without the
 // 256-wide tiles' padding (Cout = 320: 37.5 % of the MFMA work wasted, 640: 17 %).  Measured in the denoise step
@@ -585,14 +618,14 @@ static bool t160_auto(int M, int N, bool geglu, bool conv) {
   return n_ok && mb * ((N + 255) / 256) >= kCUs / 2;
 }
 
-static void choose(int M, int N, int K, int geglu, int conv, size_t ws_bytes, int& tile, int& splits) {
-  const int mt = (M + BM - 1) / BM;
-  const int t128 = mt * ((N + 127) / 128);
-  const int t64 = mt * ((N + 63) / 64);
+// Ring tile (when p.bm == 0: none forced) and split-K count of a ring plan.  splits: 0 auto, >= 1 forced.
+static void choose(const GemmQuery& q, int splits, GemmPlan& p) {
+  const int M = q.M, N = q.N, K = q.K;
+  const bool geglu = q.epi == 1;
   const int nk = (K + BK - 1) / BK;
-  const int mb = (M + 255) / 256;
-  const int t256 = mb * ((N + 255) / 256), t256n = mb * ((N + 127) / 128);
+  const int t256 = ((M + 255) / 256) * ((N + 255) / 256);
   const int nk32 = (K + 31) / 32;  // ring kernel k-tiles
+  auto set = [&p](int bm, int bn) { p.bm = bm, p.bn = bn; };
   // Tile policy (MI355X, measured in one process per comparison: tools/gemm_ablate.py TILES=..., bench.py):
   // the 256x256 ping-pong ring wins every projection / FF / GEGLU / conv shape of the path with at least a
   // quarter-wave of tiles, including the under-filled M = 8192, N = 1280 grids (160 tiles on 256 CUs:
@@ -600,21 +633,17 @@ static void choose(int M, int N, int K, int geglu, int conv, size_t ws_bytes, in
   // tiny-M GEMMs (text states, temb) use 128x128 with split-K; conv_out (Cout = 4) 128x64.
   // Below half a wave of 256x256 tiles (the training step's 16x16 level: M = 4096, N = 1280 -> 80 tiles) the
   // 128x128 tile's 4x larger grid wins (tools/tile_ab.py: 4096x1280x1312 44.6 -> 30.7 us, x5120 112 -> 82 us).
-  if (tile == 0) {
-    if (conv && N <= 64) tile = 2;
-    else if (t160_auto(M, N, geglu, conv)) tile = 6;
+  if (p.bm == 0) {
+    if (q.conv && N <= 64) set(128, 64);
+    else if (t160_auto(M, N, geglu, q.conv)) set(256, 160);
     // under-filled conv grids (the 16x16 level's Cout = 1280 convs: 160 tiles of 256x256): 192x256 tiles, 215 of
     // them, 4.12 -> 3.85 ms per step (profiles/r2_ab_conv_192x256.txt)
-    else if (conv && t256 >= kCUs / 2 && t256 < kCUs) tile = 7;
-    else if (t256 >= kCUs / 2) tile = 3;
-    else tile = 1;
+    else if (q.conv && t256 >= kCUs / 2 && t256 < kCUs) set(192, 256);
+    else if (t256 >= kCUs / 2) set(256, 256);
+    else set(128, 128);
   }
-  if (tile == 8 && conv) tile = 3;
-  if (geglu && (tile == 2 || tile == 6)) tile = 1;
-  const int t160 = mb * ((N + 159) / 160);
-  const int t192 = ((M + 191) / 192) * ((N + 255) / 256);
-  const int tiles = tile == 1 ? t128 : tile == 2 ? t64 : (tile == 3 || tile == 8) ? t256 : tile == 6 ? t160
-                    : tile == 7 ? t192 : t256n;
+  if (geglu && (p.bn == 64 || p.bn == 160)) set(128, 128);
+  const int tiles = ((M + p.bm - 1) / p.bm) * ((N + p.bn - 1) / p.bn);
   if (splits == 0) {
     splits = 1;
     if (tiles < kCUs / 2 && nk32 >= 8) {
@@ -622,28 +651,13 @@ static void choose(int M, int N, int K, int geglu, int conv, size_t ws_bytes, in
       if (splits < 2) splits = 1;
     }
   }
-  if (tile == 8) splits = 1;  // the 8-phase kernel has no split-K slab epilogue
   if (splits > nk32) splits = nk32;
   if (splits > 1) {
     const size_t need = (size_t)splits * M * N * sizeof(float);
-    if (need > ws_bytes) splits = 1;
+    if (need > q.slab_bytes) splits = 1;
     if (splits > nk) splits = nk;
   }
-}
-
-int launch_gemm_ring(const GemmArgs& a, int amode, int epi, int tile, int splits, hipStream_t s);
-int launch_gemm_p8(const GemmArgs& a, int epi, int bn, hipStream_t s);
-bool p8_persist_applies(int M, int N, int K, int epi, int bn);
-bool p8_lora_persist_on();
-int launch_gemm_p8_tattn(const GemmArgs& a, hipStream_t s);
-int launch_gemm_p8_lora(const GemmArgs& a, int bn, hipStream_t s);
-int launch_gemm_p8_xattn(const GemmArgs& a, hipStream_t s);
-int launch_gemm_p8_conv(const GemmArgs& a, int bn, hipStream_t s);
-
-// 8-phase 256x256x64 kernel (gemm_p8.hip) for plain / LoRA-augmented projections and GEGLU (see p8_auto).
-static int gemm_p8_env() {
-  static const int v = env_int("VST_GEMM_P8", -1);
-  return v;
+  p.splits = splits;
 }
 
 // Automatic choice of the 8-phase kernel (tile 0).  Measured in the denoise step (tools/ab_bench.sh, VST_BENCH_SHAPES,
@@ -652,10 +666,8 @@ static int gemm_p8_env() {
 // the 64x64 level 3-7 %), and since its loop lost the per-piece K checks also at K >= 2048 (ff.net.2: ring 10.6 ->
 // 9.1 ms per step, profiles/r2_ab_p8_all_k.txt).
 // VST_GEMM_P8 = 0 off, unset / 1 every shape with at least half a wave of 256x256 tiles.
-static int device_cus();
 static bool p8_auto(int M, int N, int K) {
-  const int e = gemm_p8_env();
-  if (e == 0) return false;
+  if (gemm_knobs().p8 == 0) return false;
   const int t256 = ((M + 255) / 256) * ((N + 255) / 256);
   return t256 >= kCUs / 2 && K >= 128;
 }
@@ -666,14 +678,8 @@ static bool p8_auto(int M, int N, int K) {
 // epilogue do not shrink with it), so it is taken when ceil(tiles192 / CUs) * 0.8 beats ceil(tiles256 / CUs).
 // VST_P8_BN=256 keeps every shape on 256x256 (A/B).
 // Forced 8-phase tile width (256 / 192 / 320, 0 = the policy below): VST_P8_BN, or vst_p8_force_bn (tests, A/B).
-static int g_p8_force_bn = -1;
-static int p8_forced_bn() {
-  if (g_p8_force_bn < 0) g_p8_force_bn = env_int("VST_P8_BN", 0);
-  return g_p8_force_bn;
-}
-
 static bool p8_bn192(int M, int N, bool geglu) {
-  const int env = p8_forced_bn();
+  const int env = gemm_knobs().p8_bn;
   if (geglu || env == 256 || env == 320) return false;
   const int mb = (M + 255) / 256, cus = device_cus();
   const int r256 = (mb * ((N + 255) / 256) + cus - 1) / cus, r192 = (mb * ((N + 191) / 192) + cus - 1) / cus;
@@ -684,16 +690,11 @@ static bool p8_bn192(int M, int N, bool geglu) {
 // 320-column tiles without padding, and M = 8192 gives exactly one full round (256 tiles on 256 CUs) where 256x192
 // gives 224.  A 128x320 tile is 0.625 of a 256x256 one in work.  VST_P8_320 = 1 takes it wherever its round count
 // times 0.7 beats the 256 / 192 choice; VST_P8_BN = 320 wherever it is legal (A/B).
-static bool p8_320_on() {
-  static const int on = env_int("VST_P8_320", 0);
-  return on != 0;
-}
-
 static bool p8_bn320(int M, int N, bool geglu) {
-  const int env = p8_forced_bn();
+  const int env = gemm_knobs().p8_bn;
   if (geglu || N % 320) return false;
   if (env == 320) return true;
-  if (!p8_320_on() || env == 256 || env == 192) return false;
+  if (!gemm_knobs().p8_320 || env == 256 || env == 192) return false;
   const int cus = device_cus();
   const int mb = (M + 255) / 256;
   const int r256 = (mb * ((N + 255) / 256) + cus - 1) / cus, r192 = (mb * ((N + 191) / 192) + cus - 1) / cus;
@@ -702,16 +703,9 @@ static bool p8_bn320(int M, int N, bool geglu) {
   return 0.7 * r320 < 0.97 * best;
 }
 
-static int g_p8_conv = -1;  // VST_P8_CONV, or vst_p8_conv (tests, A/B)
-static bool p8_conv_env() {
-  if (g_p8_conv < 0) g_p8_conv = env_int("VST_P8_CONV", 1);
-  return g_p8_conv != 0;
-}
-
 static int p8_bn(int M, int N, bool geglu) {
   return p8_bn320(M, N, geglu) ? 320 : p8_bn192(M, N, geglu) ? 192 : 256;
 }
-
 
 // Convs whose Cout is a multiple of 128 (not of 320) on which the 8-phase policy would take 192-wide tiles -- the VAE's
 // Cout = 128 convs at 512^2 (a third of every 192-wide tile padding) and its Cout = 512 convs at 64^2 (256x128 tiles fill
@@ -719,111 +713,156 @@ static int p8_bn(int M, int N, bool geglu) {
 // per launch (tools/vae_conv_ab.py, profiles/r6_vae_conv_ab.txt).  No UNet conv qualifies (Cout 320 / 640 / 1280 / 4).
 static bool conv_ring128(int M, int N) { return N % 128 == 0 && N % 320 != 0 && p8_bn(M, N, false) == 192; }
 
-}  // namespace vst
-
-// Force the 8-phase kernel's tile width for every later GEMM of this process (256 / 192 / 320 where legal; 0 = the
-// automatic policy); returns the previous setting.  For tests and A/B runs.
-extern "C" int vst_p8_force_bn(int bn) {
-  const int prev = vst::p8_forced_bn();
-  vst::g_p8_force_bn = (bn == 256 || bn == 192 || bn == 320) ? bn : 0;
-  return prev;
-}
-
-// Route 3x3 convs with 64-multiple channel sources to the 8-phase kernel (1) or the ring kernel (0) for every later
-// conv of this process; returns the previous setting.  For tests and A/B runs.
-extern "C" int vst_p8_conv(int on) {
-  const int prev = vst::p8_conv_env() ? 1 : 0;
-  vst::g_p8_conv = on ? 1 : 0;
-  return prev;
-}
-
-namespace vst {
-
-// tile code 8: AMODE 0, no split-K, a 64-aligned A source split, 256x256 tiles
+// the 8-phase kernel: AMODE 0, no split-K, a 64-aligned A source split
 static bool p8_applies(int K1, bool two_src) {
   return !two_src || (K1 & 63) == 0;
 }
-// Workspace (caller-owned): the fp32 split-K slabs [splits][M][N].
 
-static int device_cus() {
-  static int n = 0;
-  if (n <= 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = kCUs;
-  }
-  return n;
+// Whether the 8-phase kernel runs on its persistent grid (gemm_p8.hip launch_p8_persist; VST_P8_PERSIST=0: never):
+// at least two tiles per workgroup, K a multiple of 64 and >= 128 (the stream hands over two whole k-tiles), whole
+// 8-column output chunks, one A source, and a C the epilogue's buffer descriptor can address.
+static bool p8_persist_applies(int M, int N, int K, int epi, int bn, bool two_src = false, size_t c_bytes = 0) {
+  if (!gemm_knobs().p8_persist || (epi != 0 && epi != 1 && epi != 3) || two_src || c_bytes >= 0x7fff0000u) return false;
+  const int bm = bn == 320 ? 128 : 256;
+  const long tiles = (long)((M + bm - 1) / bm) * ((N + bn - 1) / bn);
+  return tiles >= 2L * p8_cus() && K >= 128 && (K & 63) == 0 && (N % (epi == 1 ? 16 : 8)) == 0;
 }
+
+// The in-GEMM LoRA kernels on the persistent grid (128x320 tiles only: a pass of the staged epilogue must hold whole
+// row quadrants of the rotated LoRA accumulators), wherever p8_persist_applies: the 32x32 level's q/k/v 123 -> 108 us
+// and out-projection 48 -> 43 us per launch, bitwise equal (profiles/r5_ab_lora_persist.txt).  VST_P8_LORA_PERSIST=0
+// restores one workgroup per tile (A/B).
+static bool p8_lora_persist_on() { return gemm_knobs().p8_persist && gemm_knobs().p8_lora_persist; }
 
 // Stream-K (one workgroup per CU over equal shares of the (tile, k-step) space, partial tiles summed by their
 // owner) was built for both the ring and the 8-phase kernel in rounds 1-3 and measured slower on every shape of this
 // path (8192x1280x1312: 8.56 -> 11.1 ms per step).  Its cross-workgroup hand-off also depended on
 // every workgroup being resident at once, which concurrent streams do not guarantee, so it was removed.
 
-static int gemm_ablate_env() {
-  static int v = -1;
-  if (v < 0) v = env_int("VST_GEMM_ABLATE", 0);
-  return v;
+// The one place a kernel is chosen.  family == kNone: the request is not legal.
+static GemmPlan plan_gemm(const GemmQuery& q) {
+  // public tile codes (include/vst.h); 0 = the policy below
+  static const GemmPlan codes[11] = {{kNone},          {kRing, 128, 128}, {kRing, 128, 64},  {kRing, 256, 256},
+                                     {kRing, 256, 128}, {kSkinny},         {kRing, 256, 160}, {kRing, 192, 256},
+                                     {kP8, 256, 256},   {kP8, 256, 192},   {kP8, 128, 320}};
+  if (q.tile < 0 || q.tile > 10 || q.splits < 0) return {};
+  const int M = q.M, N = q.N, K = q.K;
+  const bool any = q.tile == 0, geglu = q.epi == 1;
+  GemmPlan p = codes[q.tile];
+  p.epi = q.epi, p.splits = 1, p.conv = q.conv;
+  // splits 1 = no split-K (a row's bits then never depend on M: the denoise forward's row-invariant policy); the
+  // 8-phase kernel, which never splits, is chosen the same way under 0 and 1
+  const bool p8_ok = any && q.splits <= 1 && q.epi != 2 && p8_auto(M, N, K);
+  auto p8_tile = [&p](int family, int bn) { p.family = family, p.bm = bn == 320 ? 128 : 256, p.bn = bn; };
+  if (q.conv) {
+    if (p.family == kP8 || p.family == kSkinny) return {};  // convs take the ring's tile codes only
+    if (!q.vec) {
+      p.family = kGather, p.bm = BM, p.bn = 64;  // (conv_in): register-staged kernel, no split
+    } else {
+      // 3x3 convs with both sources a multiple of 64 channels run on the 8-phase kernel (implicit im2col; 128x320
+      // tiles where Cout is a multiple of 320, else the projection policy's width); VST_P8_CONV=0 restores the ring
+      const bool p8 = p8_ok && gemm_knobs().p8_conv && !(q.C1 & 63) && !(q.C2 & 63) && !(N & 63) &&
+                      K == 9 * (q.C1 + q.C2);
+      const bool ring128 = p8 && !q.colstat && conv_ring128(M, N);
+      if (ring128) p.bm = 256, p.bn = 128;
+      if (p8 && !ring128) p8_tile(kP8Conv, N % 320 == 0 ? 320 : p8_bn(M, N, false));
+      else p.family = kRing, choose(q, ring128 ? 1 : q.splits, p);
+    }
+    // column statistics come from the 128x320 tiles' epilogue only
+    if (q.colstat && !(p.family == kP8Conv && p.bn == 320)) return {};
+    return p;
+  }
+  if (p.family == kP8 && (!p8_applies(q.K1, q.two_src) || (geglu && p.bn != 256) || (p.bn == 320 && N % 320))) return {};
+  if (p.family == kSkinny && !(q.no_epi && N <= 64)) return {};
+  if (any) {
+    if (!q.two_src && (q.epi == 0 || q.epi == 3) && rows_applies(M, N, K)) p.family = kRows;
+    else if (q.no_epi && N <= 64 && M >= 1024) p.family = kSkinny;  // LoRA down-projection
+    else if (p8_ok && p8_applies(q.K1, q.two_src)) p8_tile(kP8, p8_bn(M, N, geglu));
+  }
+  if (p.family == kP8) p.persist = p8_persist_applies(M, N, K, q.epi, p.bn, q.two_src, q.c_bytes);
+  if (p.family == kNone || p.family == kRing) p.family = kRing, choose(q, q.splits, p);
+  return p;
 }
 
-static int gemm_group_env() {
-  static int v = -1;
-  if (v < 0) v = env_int("VST_GEMM_GROUP_M", 0);
-  return v;
+// The plan as the name bench.py and tools/pmc_traffic.py group launches by:
+// <family><BMxBN[,geglu][,splitk|,persist|,conv]>, "" for no plan
+static const char* plan_name(const GemmPlan& p) {
+  static const char* const fixed[] = {"", "gemm_rows", "gemm_skinny", "gemm_kernel<conv_in>"};
+  if (p.family <= kGather) return fixed[p.family];
+  const bool split = p.splits > 1;
+  char buf[64];
+  snprintf(buf, sizeof buf, "%s<%dx%d%s%s>", p.family == kRing ? "gemm_ring" : "gemm_p8", p.bm, p.bn,
+           p.epi == 1 && !split ? ",geglu" : "", split ? ",splitk" : p.persist ? ",persist" : p.conv ? ",conv" : "");
+  static std::mutex mu;
+  static std::set<std::string> names;  // (the returned pointer stays valid: set nodes do not move)
+  std::lock_guard<std::mutex> lock(mu);
+  return names.insert(buf).first->c_str();
 }
 
-// Persistent launch: measured (tools/gemm_persist.sh) 4-10 % faster for the GEGLU epilogue and neutral for
-// the others, so it is the default for GEGLU only.  VST_GEMM_PERSIST=1 forces it on, =0 off.
-static int gemm_persist_env() {
-  static const int v = env_int("VST_GEMM_PERSIST", -1);
-  return v;
-}
-
-static int run_gemm(GemmArgs& a, int amode, int geglu, int tile, int splits, hipStream_t s) {
-  a.ablate = gemm_ablate_env();
-  a.group_m = gemm_group_env();
-  const int pe = gemm_persist_env();
-  a.persist = (pe > 0 || (pe < 0 && geglu)) ? device_cus() : 0;
-  if (tile == 5) return launch_skinny(a, s);
-  if (tile == 8) {
-    if (amode != 0 || splits > 1) return VST_ERR_ARG;
-    a.splits = 1;
-    return launch_gemm_p8(a, geglu ? 1 : (a.act ? 3 : 0), a.p8_bn == 192 || a.p8_bn == 320 ? a.p8_bn : 256, s);
+static int launch_plan(GemmArgs& a, const GemmPlan& p, hipStream_t s) {
+  const GemmKnobs& k = gemm_knobs();
+  a.ablate = p.family == kP8Conv ? 0 : k.ablate;
+  a.group_m = k.group_m;
+  // Ring kernel's persistent launch: measured (tools/gemm_persist.sh) 4-10 % faster for the GEGLU epilogue and neutral
+  // for the others, so it is the default for GEGLU only.  VST_GEMM_PERSIST=1 forces it on, =0 off.
+  a.persist = (k.ring_persist > 0 || (k.ring_persist < 0 && p.epi == 1)) ? device_cus() : 0;
+  a.splits = p.splits;
+  switch (p.family) {
+    case kRows: return launch_rows(a, s);
+    case kSkinny: return launch_skinny(a, s);
+    case kGather: return launch_one<2, 0, 64>(a, s, 1);
+    case kP8: return launch_gemm_p8(a, p, s);
+    case kP8Conv: return launch_gemm_p8_conv(a, p, s);
+    case kRing: break;
+    default: return VST_ERR_ARG;
   }
-  if (amode == 2) {  // scalar-gather conv (conv_in): register-staged kernel, no split
-    a.splits = 1;
-    return launch_one<2, 0, 64>(a, s, 1);
-  }
-  a.splits = splits;
-  if (splits > 1) {
-    const int rc = launch_gemm_ring(a, amode, 2, tile, splits, s);
-    if (rc) return rc;
-    const int Nout = geglu ? a.N / 2 : a.N;
-    const size_t chunks = (size_t)a.M * ((Nout + 7) / 8);
-    const int grid = (int)std::min<size_t>((chunks + 255) / 256, 4096);
-    hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3(grid), dim3(256), 0, s, a, geglu);
-    return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
-  }
-  return launch_gemm_ring(a, amode, geglu ? 1 : (a.act ? 3 : 0), tile, 1, s);
+  const int rc = launch_gemm_ring(a, p, s);
+  if (rc || p.splits <= 1) return rc;
+  const int Nout = p.epi == 1 ? a.N / 2 : a.N;
+  const size_t chunks = (size_t)a.M * ((Nout + 7) / 8);
+  const int grid = (int)std::min<size_t>((chunks + 255) / 256, 4096);
+  hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3(grid), dim3(256), 0, s, a, p.epi == 1 ? 1 : 0);
+  return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
 }
 
 }  // namespace vst
 
 using namespace vst;
 
+// Force the 8-phase kernel's tile width for every later GEMM of this process (256 / 192 / 320 where legal; 0 = the
+// automatic policy); returns the previous setting.  For tests and A/B runs.
+extern "C" int vst_p8_force_bn(int bn) {
+  const int prev = gemm_knobs().p8_bn;
+  gemm_knobs().p8_bn = (bn == 256 || bn == 192 || bn == 320) ? bn : 0;
+  return prev;
+}
+
+// Route 3x3 convs with 64-multiple channel sources to the 8-phase kernel (1) or the ring kernel (0) for every later
+// conv of this process; returns the previous setting.  For tests and A/B runs.
+extern "C" int vst_p8_conv(int on) {
+  const int prev = gemm_knobs().p8_conv ? 1 : 0;
+  gemm_knobs().p8_conv = on ? 1 : 0;
+  return prev;
+}
+
+// The 8-phase kernel's persistent grid (1) or one workgroup per tile (0) for every later GEMM of this process; returns
+// the previous setting.  For tests and A/B runs.
+extern "C" int vst_p8_persist(int on) {
+  const int prev = gemm_knobs().p8_persist ? 1 : 0;
+  gemm_knobs().p8_persist = on ? 1 : 0;
+  return prev;
+}
+
+// Workspace (caller-owned): the fp32 split-K slabs [splits][M][N] of a ring launch of this shape.
 extern "C" size_t vst_gemm_workspace_bytes(int M, int N, int K) {
-  int tile = 0, splits = 0;
-  choose(M, N, K, 0, 0, (size_t)-1, tile, splits);
+  GemmQuery q{};
+  q.M = M, q.N = N, q.K = q.K1 = K, q.epi = 2, q.slab_bytes = (size_t)-1;
+  const int splits = plan_gemm(q).splits;
   return splits > 1 ? (size_t)splits * M * N * sizeof(float) : 0;
 }
 
 // ---- fused base + LoRA projection with the down-projection inside the 8-phase GEMM (gemm_p8.hip LORA) ----
 // VST_LORA_INGEMM=0 turns it off (the host then runs the separate down-projection pass, A/B).
-static bool lora_ingemm_env() {
-  static const int v = env_int("VST_LORA_INGEMM", 1);
-  return v != 0;
-}
-
 // 0 = not supported (the host falls back to u = x.Acat^T + vst_gemm_ex), else the 8-phase tile width (256 / 192 /
 // 320).  Every tile's output columns must need u columns inside one 16-aligned block of 16.  Whether the in-GEMM
 // path is taken depends on the SHAPE only (N, K, the projection groups), never on M: it runs whenever some tile width
@@ -841,7 +880,7 @@ static bool lora_tiles_ok(int N, int P, int gn, int gr, int bn) {
 }
 
 static int lora_ingemm_bn(int M, int N, int K, int P, int gn, int gr, int force_bn = 0) {
-  if (!lora_ingemm_env() || M <= 0 || N <= 0 || K < 128 || (K & 7) || P <= 0 || (P & 15) || P > 256 || gn <= 0 ||
+  if (!gemm_knobs().lora_ingemm || M <= 0 || N <= 0 || K < 128 || (K & 7) || P <= 0 || (P & 15) || P > 256 || gn <= 0 ||
       gr <= 0 || N % gn || (N / gn) * gr > P)
     return 0;
   if (force_bn) return lora_tiles_ok(N, P, gn, gr, force_bn) && (force_bn != 320 || N % 320 == 0) ? force_bn : 0;
@@ -853,7 +892,7 @@ static int lora_ingemm_bn(int M, int N, int K, int P, int gn, int gr, int force_
       break;
     }
   // a multi-round grid of 256-row tiles (the 32x32 out-projection) moves to the persistent LoRA grid, which runs
-  // 128x320 tiles only (gemm_p8.hip, p8_lora_persist_env); a grid under two rounds keeps its tiles (the 16x16 q/k/v:
+  // 128x320 tiles only (p8_lora_persist_on); a grid under two rounds keeps its tiles (the 16x16 q/k/v:
   // 480 tiles of 256x256, 76 us against 89 on 128x320 persistent, profiles/r5_ab_lora_persist.txt)
   if (bn && bn != 320 && p8_lora_persist_on() && N % 320 == 0 && lora_tiles_ok(N, P, gn, gr, 320) &&
       (long)((M + 255) / 256) * ((N + bn - 1) / bn) >= 2L * device_cus() && p8_persist_applies(M, N, K, 0, 320))
@@ -886,22 +925,17 @@ extern "C" int vst_gemm_lora(const void* x, int ldx, const void* Acat, int ld_ac
   a.la_bytes = fit((size_t)P * ld_acat * 2);
   if (fit.over) return VST_ERR_ARG;  // past the 32-bit buffer offsets (not chunked here): refuse
   a.stride = 1; a.splits = 1;
-  a.p8_bn = bn;
-  a.ablate = gemm_ablate_env();  // (reaches the kernel in the diagnostics build only, -DVST_P8_TRACE)
-  a.group_m = gemm_group_env();
-  return launch_gemm_p8_lora(a, bn, (hipStream_t)stream);
+  a.ablate = gemm_knobs().ablate;  // (reaches the kernel in the diagnostics build only, -DVST_P8_TRACE)
+  a.group_m = gemm_knobs().group_m;
+  const bool persist = bn == 320 && p8_lora_persist_on() && p8_persist_applies(M, N, K, 0, bn, false, (size_t)M * ldc * 2);
+  return launch_gemm_p8_lora(a, bn, persist, (hipStream_t)stream);
 }
 
 // ---- attn2: q projection (+ in-GEMM LoRA) with the cross-attention over the text tokens as its epilogue ----
 // VST_XATTN_FUSE=0 turns it off (the host then runs the q GEMM and vst_spatial_attention, A/B).
-static bool xattn_env() {
-  static const int v = env_int("VST_XATTN_FUSE", 1);
-  return v != 0;
-}
-
 // Shape-only decision (not M: a frame-sharded rank fuses exactly where the unsharded forward does).
 static bool xattn_ok(int M, int N, int K, const void* Acat, int P, int gn, int gr, int Nq, int Nk) {
-  if (!xattn_env() || M <= 0 || N <= 0 || N % 64 || K < 128 || (K & 7) || Nq <= 0 || Nq % 256 || M % Nq || Nk < 1 ||
+  if (!gemm_knobs().xattn_fuse || M <= 0 || N <= 0 || N % 64 || K < 128 || (K & 7) || Nq <= 0 || Nq % 256 || M % Nq || Nk < 1 ||
       Nk > 80)
     return false;
   return !Acat || lora_ingemm_bn(M, N, K, P, gn, gr, 192) == 192;
@@ -938,8 +972,8 @@ extern "C" int vst_gemm_cross_attention(const void* x, int ldx, const void* Acat
   a.xa_kvdiv = kv_div; a.xa_scale_log2 = scale * 1.4426950408889634f;
   a.xa_kv_bytes = fit(((size_t)(nkv_rows - 1) * ldkv + N) * 2);
   if (fit.over) return VST_ERR_ARG;  // past the 32-bit buffer offsets (not chunked here): refuse
-  a.stride = 1; a.splits = 1; a.p8_bn = 192;
-  a.ablate = gemm_ablate_env();  // (diagnostics build only)
+  a.stride = 1; a.splits = 1;
+  a.ablate = gemm_knobs().ablate;  // (diagnostics build only)
   return launch_gemm_p8_xattn(a, (hipStream_t)stream);
 }
 
@@ -951,7 +985,7 @@ static bool tattn_ok(int M, int K, int nclip, int F, int HW, int heads, int head
   const int hpt = tattn_hpt(head_dim);
   if (!hpt || F != 16 || heads <= 0 || heads % hpt || HW <= 0 || (HW & 15) || nclip <= 0) return false;
   // (shape-only, like the other fused paths: a frame-sharded rank decides as the unsharded forward does)
-  return (long)M == (long)nclip * F * HW && !(K & 63) && K >= 128 && gemm_p8_env() != 0;
+  return (long)M == (long)nclip * F * HW && !(K & 63) && K >= 128 && gemm_knobs().p8 != 0;
 }
 
 extern "C" int vst_gemm_temporal_attention_supported(int M, int K, int nclip, int F, int HW, int heads,
@@ -975,7 +1009,7 @@ extern "C" int vst_gemm_temporal_attention(const void* x, int ldx, const void* W
   a.w_bytes = fit(((size_t)(N - 1) * ldw + K) * 2);
   if (fit.over) return VST_ERR_ARG;  // past the 32-bit buffer offsets (not chunked here): refuse
   a.ta_hw = HW; a.ta_heads = heads; a.ta_d = head_dim; a.ta_scale_log2 = scale * 1.4426950408889634f;
-  a.stride = 1; a.splits = 1; a.p8_bn = 256;
+  a.stride = 1; a.splits = 1;
   return launch_gemm_p8_tattn(a, (hipStream_t)stream);
 }
 
@@ -983,46 +1017,11 @@ extern "C" int vst_gemm_temporal_attention(const void* x, int ldx, const void* W
 // symbol rocprofv3 reports), so per-launch timings can be attributed to kernels.  kind: 0 linear,
 // 1 GEGLU linear, 2 vectorized conv, 3 scalar-gather conv.  Returns a static string.
 extern "C" const char* vst_gemm_kernel_name(int M, int N, int K, int kind, int tile, int splits, size_t ws_bytes) {
-  static const char* names[7][3] = {
-      {"gemm_ring<128x128>", "gemm_ring<128x128,geglu>", "gemm_ring<128x128,conv>"},
-      {"gemm_ring<128x64>", "gemm_ring<128x64,geglu>", "gemm_ring<128x64,conv>"},
-      {"gemm_ring<256x256>", "gemm_ring<256x256,geglu>", "gemm_ring<256x256,conv>"},
-      {"gemm_ring<256x128>", "gemm_ring<256x128,geglu>", "gemm_ring<256x128,conv>"},
-      {"", "", ""},
-      {"gemm_ring<256x160>", "", "gemm_ring<256x160,conv>"},
-      {"gemm_ring<192x256>", "gemm_ring<192x256,geglu>", "gemm_ring<192x256,conv>"}};
-  static const char* split_names[7] = {"gemm_ring<128x128,splitk>", "gemm_ring<128x64,splitk>",
-                                       "gemm_ring<256x256,splitk>", "gemm_ring<256x128,splitk>", "",
-                                       "gemm_ring<256x160,splitk>", "gemm_ring<192x256,splitk>"};
-  if (kind == 3) return "gemm_kernel<conv_in>";
-  if (kind == 2 && tile == 0 && splits <= 1 && p8_conv_env() && K % 576 == 0 && N % 64 == 0 &&
-      p8_auto(M, N, K)) {
-    if (conv_ring128(M, N)) return "gemm_ring<256x128,conv>";
-    const int bn = N % 320 == 0 ? 320 : p8_bn(M, N, false) == 192 ? 192 : 256;
-    return bn == 320 ? "gemm_p8<128x320,conv>" : bn == 192 ? "gemm_p8<256x192,conv>" : "gemm_p8<256x256,conv>";
-  }
-  if (kind == 0 && tile == 0 && rows_applies(M, N, K)) return "gemm_rows";
-  if (kind == 0 && (tile == 5 || (tile == 0 && N <= 64 && M >= 1024))) return "gemm_skinny";  // no-epilogue calls
-  if (kind < 0 || kind > 3 || tile < 0 || tile > 10 || tile == 5 || splits < 0) return "";
-  // the 8-phase kernel, persistent where p8_persist_applies (kind 0 is reported with its plain epilogue)
-  auto p8name = [&](int bn, bool geglu) -> const char* {
-    const bool pe = p8_persist_applies(M, N, K, geglu ? 1 : 0, bn);
-    if (bn == 320) return pe ? "gemm_p8<128x320,persist>" : "gemm_p8<128x320>";
-    if (bn == 192) return pe ? "gemm_p8<256x192,persist>" : "gemm_p8<256x192>";
-    if (geglu) return pe ? "gemm_p8<256x256,geglu,persist>" : "gemm_p8<256x256,geglu>";
-    return pe ? "gemm_p8<256x256,persist>" : "gemm_p8<256x256>";
-  };
-  if (tile == 9) return kind == 0 ? p8name(192, false) : "";
-  if (tile == 10) return kind == 0 ? p8name(320, false) : "";
-  if (tile == 0 && kind <= 1 && p8_auto(M, N, K)) {
-    if (splits <= 1 && kind == 0 && p8_bn(M, N, false) == 320) return p8name(320, false);
-    if (splits <= 1 && kind == 0 && p8_bn192(M, N, false)) return p8name(192, false);
-    tile = 8;
-  }
-  choose(M, N, K, kind == 1, kind == 2, ws_bytes, tile, splits);
-  if (tile == 8) return p8name(256, kind == 1);
-  if (splits > 1) return split_names[tile - 1];
-  return names[tile - 1][kind == 2 ? 2 : kind];
+  if (kind < 0 || kind > 3) return "";
+  GemmQuery q{};
+  q.M = M, q.N = N, q.K = q.K1 = K, q.epi = kind == 1, q.no_epi = kind == 0, q.tile = tile, q.splits = splits;
+  q.slab_bytes = ws_bytes, q.conv = kind >= 2, q.vec = kind == 2, q.C1 = K / 9;
+  return plan_name(plan_gemm(q));
 }
 
 // The kernels address A, A2 and the residual through buffer descriptors with 32-bit byte offsets (Fit31): an
@@ -1080,12 +1079,12 @@ extern "C" int vst_gemm_ex(const void* A, int lda, const void* A2, int lda2, int
       return VST_OK;
     }
   }
-  if (tile < 0 || tile > 10 || splits < 0) return VST_ERR_ARG;
-  if ((tile == 8 || tile == 9 || tile == 10) && !p8_applies(K1, A2 != nullptr)) return VST_ERR_ARG;
-  if ((tile == 9 || tile == 10) && epilogue == 1) return VST_ERR_ARG;  // GEGLU needs the 256-wide tiles
-  if (tile == 10 && N % 320) return VST_ERR_ARG;
-  const bool skinny_ok = N <= 64 && !A2 && !bias && !row_bias && !R && epilogue == 0;
-  if (tile == 5 && !skinny_ok) return VST_ERR_ARG;
+  GemmQuery q{};
+  q.M = M, q.N = N, q.K = K, q.K1 = K1, q.two_src = A2 != nullptr, q.epi = epilogue == 2 ? 3 : epilogue;
+  q.no_epi = !A2 && !bias && !row_bias && !R && epilogue == 0;
+  q.tile = tile, q.splits = splits, q.slab_bytes = workspace ? ws_bytes : 0, q.c_bytes = (size_t)M * ldc * 2;
+  const GemmPlan plan = plan_gemm(q);
+  if (plan.family == kNone) return VST_ERR_ARG;
   GemmArgs a{};
   a.A1 = (const bf16_t*)A; a.A2 = (const bf16_t*)A2; a.lda1 = lda; a.lda2 = lda2; a.K1 = K1;
   a.Wt = (const bf16_t*)W; a.ldw = ldw; a.M = M; a.N = N; a.K = K;
@@ -1099,21 +1098,7 @@ extern "C" int vst_gemm_ex(const void* A, int lda, const void* A2, int lda2, int
   if (fit.over) return VST_ERR_ARG;  // (A / R / C are chunked above; a weight past 2^31 - 1 bytes is refused)
   a.C1 = 0; a.C2 = 0; a.stride = 1; a.up = 0;
   a.act = epilogue == 2 ? 1 : 0;
-  if (epilogue == 2) epilogue = 0;
-  if (tile == 0 && !A2 && epilogue != 1 && rows_applies(M, N, K)) return launch_rows(a, (hipStream_t)stream);
-  if (tile == 0 && skinny_ok && M >= 1024) tile = 5;  // LoRA down-projection: skinny kernel
-  if (tile == 5) return run_gemm(a, 0, 0, 5, 1, (hipStream_t)stream);
-  const size_t slab_bytes = workspace ? ws_bytes : 0;
-  // splits 1 = no split-K (a row's bits then never depend on M: the denoise forward's row-invariant policy); the
-  // 8-phase kernel, which never splits, is chosen the same way under 0 and 1
-  if (tile == 0 && splits <= 1 && p8_auto(M, N, K) && p8_applies(K1, A2 != nullptr))
-    tile = p8_bn(M, N, epilogue == 1) == 320 ? 10 : p8_bn192(M, N, epilogue == 1) ? 9 : 8;
-  if (tile == 9 || tile == 10) {  // the 8-phase kernel at 256x192 / 128x320
-    a.p8_bn = tile == 9 ? 192 : 320;
-    return run_gemm(a, 0, 0, 8, 1, (hipStream_t)stream);
-  }
-  choose(M, N, K, epilogue == 1, 0, slab_bytes, tile, splits);
-  return run_gemm(a, 0, epilogue == 1, tile, splits, (hipStream_t)stream);
+  return launch_plan(a, plan, (hipStream_t)stream);
 }
 
 extern "C" int vst_gemm(const void* A, int lda, const void* A2, int lda2, int K1, const void* W, int ldw, int M, int N,
@@ -1136,7 +1121,6 @@ static int conv3x3_impl(const void* x1, int C1, const void* x2, int C2, int nimg
   if (pad0 && (stride != 2 || H < 2 || W < 2)) return VST_ERR_ARG;
   if (stride != 1 && stride != 2) return VST_ERR_ARG;
   if (upsample && stride != 1) return VST_ERR_ARG;
-  if (tile < 0 || tile > 7 || tile == 5 || splits < 0) return VST_ERR_ARG;
   const int Ct = C1 + (x2 ? C2 : 0);
   const bool vec = (Ct % BK == 0) && (C1 % 8 == 0);
   if (x2 && !vec) return VST_ERR_ARG;
@@ -1183,29 +1167,14 @@ static int conv3x3_impl(const void* x1, int C1, const void* x2, int C2, int nimg
   a.r_bytes = R ? fit(((size_t)(a.M - 1) * ldr + Cout) * 2) : 0;
   if (fit.over) return VST_ERR_ARG;  // (A / R / C are chunked above; a weight past 2^31 - 1 bytes is refused)
   if ((ldc & 7) && Cout >= 8) return VST_ERR_ARG;
-  if (!vec) { tile = 2; splits = 1; }
-  // 3x3 convs with both sources a multiple of 64 channels run on the 8-phase kernel (implicit im2col; 128x320 tiles
-  // where Cout is a multiple of 320, else the projection policy's width); VST_P8_CONV=0 restores the ring kernel
-  bool p8 = vec && tile == 0 && splits <= 1 && p8_conv_env() && !(C1 & 63) && !((x2 ? C2 : 0) & 63) &&
-            !(a.N & 63) && p8_auto(a.M, a.N, a.K);
-  if (p8 && !colstat && conv_ring128(a.M, a.N)) {
-    p8 = false;
-    tile = 4;
-    splits = 1;
-  }
-  if (colstat) {  // column statistics come from the 128x320 tiles' epilogue only
-    if (!p8 || a.N % 320) return VST_ERR_UNSUPPORTED;
-    a.colstat = colstat;
-  }
-  if (p8) {
-    a.splits = 1;
-    a.ablate = 0;
-    a.group_m = gemm_group_env();
-    return launch_gemm_p8_conv(a, a.N % 320 == 0 ? 320 : p8_bn(a.M, a.N, false), (hipStream_t)stream);
-  }
-  const size_t slab_bytes = workspace ? ws_bytes : 0;
-  choose(a.M, a.N, a.K, 0, 1, slab_bytes, tile, splits);
-  return run_gemm(a, vec ? 1 : 2, 0, tile, splits, (hipStream_t)stream);
+  GemmQuery q{};
+  q.M = a.M, q.N = a.N, q.K = a.K, q.K1 = a.K1, q.two_src = x2 != nullptr, q.tile = tile, q.splits = splits;
+  q.slab_bytes = workspace ? ws_bytes : 0, q.c_bytes = (size_t)a.M * ldc * 2;
+  q.conv = true, q.vec = vec, q.colstat = colstat != nullptr, q.C1 = a.C1, q.C2 = a.C2;
+  const GemmPlan plan = plan_gemm(q);
+  if (plan.family == kNone) return colstat ? VST_ERR_UNSUPPORTED : VST_ERR_ARG;
+  a.colstat = colstat;
+  return launch_plan(a, plan, (hipStream_t)stream);
 }
 
 extern "C" int vst_conv3x3_ex(const void* x1, int C1, const void* x2, int C2, int nimg, int H, int W, int stride,
@@ -1253,12 +1222,9 @@ extern "C" int vst_gemm_f32out(const void* A, int lda, const void* W, int ldw, i
   a.a1_bytes = fit(((size_t)(M - 1) * lda + K) * 2);
   a.w_bytes = fit(((size_t)(N - 1) * ldw + K) * 2);
   if (fit.over) return VST_ERR_ARG;  // past the 32-bit buffer offsets (not chunked here): refuse
-  int tile = 0, splits = 1;
-  choose(M, N, K, 0, 0, 0, tile, splits);
-  if (tile == 8) tile = 3;
-  a.ablate = gemm_ablate_env();
-  a.group_m = gemm_group_env();
-  return launch_gemm_ring(a, 0, 2, tile, 1, (hipStream_t)stream);
+  GemmQuery q{};
+  q.M = M, q.N = N, q.K = q.K1 = K, q.epi = 2, q.splits = 1;  // the slab epilogue: a ring tile, one split
+  return launch_plan(a, plan_gemm(q), (hipStream_t)stream);
 }
 
 extern "C" int vst_conv3x3(const void* x1, int C1, const void* x2, int C2, int nimg, int H, int W, int stride,

@@ -18,7 +18,7 @@
 // permutation is applied to each lane's SOURCE address (lane l fetches chunk (l&3) ^ G[(l>>4)&3]).
 #include <type_traits>
 
-#include "gemm_common.h"
+#include "gemm_plan.h"
 #include "gemm_epilogue.h"
 
 namespace vst {
@@ -508,16 +508,17 @@ static int dispatch_cfg(const GemmArgs& a, int amode, int epi, hipStream_t s, in
   return VST_ERR_ARG;
 }
 
-// tile: 1 = 128x128, 2 = 128x64, 3 = 256x256, 4 = 256x128, 6 = 256x160, 7 = 192x256.  epi: 0 plain, 1 GEGLU,
-// 2 split-K partial, 3 bias + GELU
-int launch_gemm_ring(const GemmArgs& a, int amode, int epi, int tile, int splits, hipStream_t s) {
-  switch (tile) {
-    case 1: return dispatch_cfg<Cfg128x128>(a, amode, epi, s, splits);
-    case 2: return epi == 1 ? VST_ERR_ARG : dispatch_cfg<Cfg128x64>(a, amode, epi, s, splits);
-    case 3: return dispatch_cfg<Cfg256x256>(a, amode, epi, s, splits);
-    case 4: return dispatch_cfg<Cfg256x128>(a, amode, epi, s, splits);
-    case 6: return epi == 1 ? VST_ERR_ARG : dispatch_cfg<Cfg256x160>(a, amode, epi, s, splits);
-    case 7: return dispatch_cfg<Cfg192x256>(a, amode, epi, s, splits);
+// The plan's tile with its A loader (dense / 3x3 conv) and epilogue: 0 plain, 1 GEGLU, 2 fp32 slab (always when the
+// plan splits K), 3 bias + GELU
+int launch_gemm_ring(const GemmArgs& a, const GemmPlan& p, hipStream_t s) {
+  const int amode = p.conv ? 1 : 0, epi = p.splits > 1 ? 2 : p.epi, splits = p.splits;
+  switch (p.bm * 1000 + p.bn) {
+    case 128128: return dispatch_cfg<Cfg128x128>(a, amode, epi, s, splits);
+    case 128064: return epi == 1 ? VST_ERR_ARG : dispatch_cfg<Cfg128x64>(a, amode, epi, s, splits);
+    case 256256: return dispatch_cfg<Cfg256x256>(a, amode, epi, s, splits);
+    case 256128: return dispatch_cfg<Cfg256x128>(a, amode, epi, s, splits);
+    case 256160: return epi == 1 ? VST_ERR_ARG : dispatch_cfg<Cfg256x160>(a, amode, epi, s, splits);
+    case 192256: return dispatch_cfg<Cfg192x256>(a, amode, epi, s, splits);
     default: return VST_ERR_ARG;
   }
 }

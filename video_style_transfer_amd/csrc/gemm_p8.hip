@@ -41,7 +41,7 @@
 // 0.2 ms slower, r5_ab_dma_in_mfma_lora_negative.txt), and the LoRA kernels on the plain GEMMs' B1 placement (+1 %,
 // r4_ab_b1_j1.txt).
 #include "attn_common.h"
-#include "gemm_common.h"
+#include "gemm_plan.h"
 #include "gemm_epilogue.h"
 
 #include <type_traits>
@@ -1109,33 +1109,8 @@ static int launch_p8_tile_per_wg(const GemmArgs& a, hipStream_t s) {
 // the tiles; each tile's last two k-tiles stream the next tile's first two into the ring, so a tile's fill overlaps
 // the previous tile's epilogue.  Same bits.  Measured (tools/p8_variant_ab.py, profiles/r4_p8_persist_ab.txt): 0-15 %
 // faster per launch on the step's multi-round shapes (K = 320 / 640 most), the denoise step -0.9 ms same-box; the
-// convs stay on one workgroup per tile (their persistent variant spilled SGPRs and ran 2 % slower).
-static int g_p8_persist = -1;  // VST_P8_PERSIST, or vst_p8_persist (tests, A/B)
-static int p8_persist_env() {
-  if (g_p8_persist < 0) g_p8_persist = env_int("VST_P8_PERSIST", 1);
-  return g_p8_persist;
-}
-static int p8_cus() {
-  static const int v = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8)
-      n = 256;
-    return n & ~7;
-  }();
-  return v;
-}
-
-// whether launch_gemm_p8 runs the persistent kernel for this shape: at least two tiles per workgroup, K a multiple of
-// 64 and >= 128 (the stream hands over two whole k-tiles), whole 8-column output chunks (and one A source:
-// launch_p8_epi)
-bool p8_persist_applies(int M, int N, int K, int epi, int bn) {
-  if (!p8_persist_env() || (epi != 0 && epi != 1 && epi != 3)) return false;
-  const int bm = bn == 320 ? 128 : 256;
-  const long tiles = (long)((M + bm - 1) / bm) * ((N + bn - 1) / bn);
-  return tiles >= 2L * p8_cus() && K >= 128 && (K & 63) == 0 && (N % (epi == 1 ? 16 : 8)) == 0;
-}
-
+// convs stay on one workgroup per tile (their persistent variant spilled SGPRs and ran 2 % slower).  Which launches
+// take it is the plan's decision (gemm.hip p8_persist_applies).
 template <int EPI, int BN, int BM, bool LORA = false>
 static int launch_p8_persist(const GemmArgs& a, hipStream_t s) {
   static bool attr = false;
@@ -1151,53 +1126,41 @@ static int launch_p8_persist(const GemmArgs& a, hipStream_t s) {
   return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
 }
 
-// The in-GEMM LoRA kernels on the persistent grid (128x320 tiles only: a pass of the staged epilogue must hold whole
-// row quadrants of the rotated LoRA accumulators), wherever p8_persist_applies: the 32x32 level's q/k/v 123 -> 108 us
-// and out-projection 48 -> 43 us per launch, bitwise equal (profiles/r5_ab_lora_persist.txt).  VST_P8_LORA_PERSIST=0
-// restores one workgroup per tile (A/B).
-static int p8_lora_persist_env() {
-  static const int v = env_int("VST_P8_LORA_PERSIST", 1);
-  return v;
-}
-bool p8_lora_persist_on() { return p8_persist_env() && p8_lora_persist_env(); }
-
-// BN = 320 runs 128-row tiles (P8Cfg)
+// BN = 320 runs 128-row tiles (P8Cfg).  The persistent grid exists for the plain / GEGLU / GELU epilogues and for the
+// in-GEMM LoRA on 128x320 tiles.
 template <int EPI, int BN, bool LORA = false>
-static int launch_p8_epi(const GemmArgs& a, hipStream_t s) {
+static int launch_p8_epi(const GemmArgs& a, bool persist, hipStream_t s) {
   constexpr int BM = BN == 320 ? 128 : 256;
   if constexpr (!LORA && EPI != 4 && EPI != 5)
-    if (!a.A2 && (size_t)a.M * a.ldc * 2 < 0x7fff0000u && p8_persist_applies(a.M, a.N, a.K, EPI, BN))
-      return launch_p8_persist<EPI, BN, BM>(a, s);
+    if (persist) return launch_p8_persist<EPI, BN, BM>(a, s);
   if constexpr (LORA && EPI == 0 && BN == 320)
-    if (p8_lora_persist_on() && !a.A2 && (size_t)a.M * a.ldc * 2 < 0x7fff0000u &&
-        p8_persist_applies(a.M, a.N, a.K, EPI, BN))
-      return launch_p8_persist<EPI, BN, BM, true>(a, s);
-  return launch_p8_tile_per_wg<EPI, BN, LORA, BM>(a, s);
+    if (persist) return launch_p8_persist<EPI, BN, BM, true>(a, s);
+  return persist ? VST_ERR_ARG : launch_p8_tile_per_wg<EPI, BN, LORA, BM>(a, s);
 }
 
-// in-GEMM LoRA down-projection (a.la set): epilogue 0 (bias / residual), bn 256 or 192
-int launch_gemm_p8_lora(const GemmArgs& a, int bn, hipStream_t s) {
+// in-GEMM LoRA down-projection (a.la set): epilogue 0 (bias / residual), bn 256, 192 or 320
+int launch_gemm_p8_lora(const GemmArgs& a, int bn, bool persist, hipStream_t s) {
   if (!a.la) return VST_ERR_ARG;
-  if (bn == 320) return launch_p8_epi<0, 320, true>(a, s);
-  return bn == 192 ? launch_p8_epi<0, 192, true>(a, s) : launch_p8_epi<0, 256, true>(a, s);
+  if (bn == 320) return launch_p8_epi<0, 320, true>(a, persist, s);
+  return bn == 192 ? launch_p8_epi<0, 192, true>(a, persist, s) : launch_p8_epi<0, 256, true>(a, persist, s);
 }
 
 // temporal attention epilogue (a.ta_hw set), 256x256 tiles
 int launch_gemm_p8_tattn(const GemmArgs& a, hipStream_t s) {
   if (a.ta_hw <= 0 || (a.ta_hw & 15) || a.A2 || (a.M & 255)) return VST_ERR_ARG;
-  return launch_p8_epi<5, 256>(a, s);
+  return launch_p8_epi<5, 256>(a, false, s);
 }
 
 // cross-attention epilogue (a.xa_k set), 256x192 tiles, with or without the in-GEMM LoRA
 int launch_gemm_p8_xattn(const GemmArgs& a, hipStream_t s) {
   if (!a.xa_k || !a.xa_v) return VST_ERR_ARG;
-  return a.la ? launch_p8_epi<4, 192, true>(a, s) : launch_p8_epi<4, 192, false>(a, s);
+  return a.la ? launch_p8_epi<4, 192, true>(a, false, s) : launch_p8_epi<4, 192, false>(a, false, s);
 }
 
-// implicit-GEMM 3x3 conv (GemmArgs conv geometry, Ctot % 64 == 0), epilogue 0; bn: 256, 192 or 320
-int launch_gemm_p8_conv(const GemmArgs& a, int bn, hipStream_t s) {
+// implicit-GEMM 3x3 conv (GemmArgs conv geometry, Ctot % 64 == 0), epilogue 0; tile width 256, 192 or 320
+int launch_gemm_p8_conv(const GemmArgs& a, const GemmPlan& p, hipStream_t s) {
   if ((a.C1 & 63) || (a.C2 & 63) || a.K != 9 * (a.C1 + a.C2)) return VST_ERR_ARG;
-  switch (bn) {
+  switch (p.bn) {
     case 256: return launch_p8_tile_per_wg<0, 256, false, 256, true>(a, s);
     case 192: return launch_p8_tile_per_wg<0, 192, false, 256, true>(a, s);
     case 320: return launch_p8_tile_per_wg<0, 320, false, 128, true>(a, s);
@@ -1205,32 +1168,26 @@ int launch_gemm_p8_conv(const GemmArgs& a, int bn, hipStream_t s) {
   }
 }
 
-// epi: 0 bias / row bias / residual, 1 GEGLU, 3 bias + GELU; bn: 256, 192 or 320 (128-row tiles; not with GEGLU)
-int launch_gemm_p8(const GemmArgs& a, int epi, int bn, hipStream_t s) {
+// epi: 0 bias / row bias / residual, 1 GEGLU, 3 bias + GELU; tile width 256, 192 or 320 (128-row tiles; not with GEGLU)
+int launch_gemm_p8(const GemmArgs& a, const GemmPlan& p, hipStream_t s) {
   if (a.A2 && (a.K1 & 63)) return VST_ERR_ARG;  // a 64-deep k-tile must not straddle the two A sources
-  if (bn == 192 || bn == 320) {
-    switch (epi) {
-      case 0: return bn == 192 ? launch_p8_epi<0, 192>(a, s) : launch_p8_epi<0, 320>(a, s);
-      case 3: return bn == 192 ? launch_p8_epi<3, 192>(a, s) : launch_p8_epi<3, 320>(a, s);
+  if (p.bn == 192 || p.bn == 320) {
+    switch (p.epi) {
+      case 0: return p.bn == 192 ? launch_p8_epi<0, 192>(a, p.persist, s) : launch_p8_epi<0, 320>(a, p.persist, s);
+      case 3: return p.bn == 192 ? launch_p8_epi<3, 192>(a, p.persist, s) : launch_p8_epi<3, 320>(a, p.persist, s);
       default: return VST_ERR_ARG;
     }
   }
-  if (bn != 256) return VST_ERR_ARG;
-  switch (epi) {
-    case 0: return launch_p8_epi<0, 256>(a, s);
-    case 1: return launch_p8_epi<1, 256>(a, s);
-    case 3: return launch_p8_epi<3, 256>(a, s);
+  if (p.bn != 256) return VST_ERR_ARG;
+  switch (p.epi) {
+    case 0: return launch_p8_epi<0, 256>(a, p.persist, s);
+    case 1: return launch_p8_epi<1, 256>(a, p.persist, s);
+    case 3: return launch_p8_epi<3, 256>(a, p.persist, s);
     default: return VST_ERR_ARG;
   }
 }
 
 }  // namespace vst
-
-extern "C" int vst_p8_persist(int on) {
-  const int prev = vst::p8_persist_env() ? 1 : 0;
-  vst::g_p8_persist = on ? 1 : 0;
-  return prev;
-}
 
 #ifdef VST_P8_TRACE
 extern "C" int vst_p8_trace_read(void* host_dst, int n_wg) {
