@@ -665,6 +665,20 @@ def test_group_norm_frame_partials_sharded(cuda, K, P, nclip, Fr, HW, C):
     check(whole.cpu(), ref.permute(0, 2, 1).reshape(-1, C), name="groupnorm_frames")
 
 
+@pytest.mark.parametrize("ns,rps,C", [(3, 77, 64), (2, 300, 320)])
+def test_group_norm_finalize_forms_agree(cuda, K, ns, rps, C):
+    """The per-sample GroupNorm is the rank-major partials form with one rank and one frame per clip: the same chunk
+    partials merged in the same order, so the same bits (one finalize kernel serves both entry points)."""
+    g = torch.Generator().manual_seed(ns * rps + C)
+    x = (rnd(ns * rps, C, gen=g) + 0.3).to(cuda)
+    gam = (torch.rand(C, generator=g) + 0.5).to(cuda)
+    bet = (torch.randn(C, generator=g) * 0.1).to(cuda)
+    eps = 1e-5
+    assert torch.equal(K.group_norm(x, ns, rps, 32, eps, gam, bet, silu=True),
+                       K.group_norm_apply_partials(x, ns, 1, rps, 32, eps, gam, bet,
+                                                   K.group_norm_frame_partials(x, ns, rps, 32), 1, silu=True))
+
+
 @pytest.mark.parametrize("nimg,HW,C", [(32, 256, 1280), (32, 1024, 640), (8, 4096, 320), (6, 576, 1280)])
 def test_group_norm_frame_invariant(cuda, K, nimg, HW, C):
     """Per-frame GroupNorm: a frame's output does not depend on how many frames share the launch (the chunking is a
@@ -691,9 +705,12 @@ def test_permute_rows(cuda, K, dims, perm):
 
 
 @pytest.mark.parametrize("rows,C,use_pe,offset", [(300, 320, False, 0.0), (64, 1280, True, 0.0), (513, 640, True, 0.0),
-                                                 (10, 64, False, 0.0), (256, 1280, False, 40.0), (96, 320, False, -25.0)])
+                                                 (10, 64, False, 0.0), (256, 1280, False, 40.0), (96, 320, False, -25.0),
+                                                 (9, 768, True, 0.0), (9, 2048, False, 0.0)])
 def test_layer_norm(cuda, K, rows, C, use_pe, offset):
-    """offset: rows whose mean is far from 0 relative to their spread (the statistics' cancellation case)."""
+    """offset: rows whose mean is far from 0 relative to their spread (the statistics' cancellation case).
+    C = 768 / 2048: the generic kernel with 2 / 4 chunks per lane; 9 rows leave the last workgroup with a wave whose
+    second row is past the end."""
     g = torch.Generator().manual_seed(rows + C)
     x = (rnd(rows, C, gen=g).float() + offset).to(torch.bfloat16)
     gam, bet = torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g) * 0.1

@@ -422,8 +422,6 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
 
 using namespace vst;
 
-static inline int ok() { return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH; }
-
 extern "C" int vst_timestep_embedding(const float* t, const int* step_idx, int n, int dim, int flip_sin_to_cos,
                                       float downscale_freq_shift, void* out, int ld, int col0, int per_row,
                                       void* stream) {
@@ -431,14 +429,14 @@ extern "C" int vst_timestep_embedding(const float* t, const int* step_idx, int n
   const int tot = n * (dim / 2);
   hipLaunchKernelGGL(timestep_embed_kernel, dim3((tot + 255) / 256), dim3(256), 0, (hipStream_t)stream, t, step_idx,
                      n, dim, flip_sin_to_cos, downscale_freq_shift, (bf16_t*)out, ld, col0, per_row);
-  return ok();
+  return launch_status();
 }
 
 extern "C" int vst_silu(const void* x, void* y, size_t n, void* stream) {
   if (!x || !y) return VST_ERR_ARG;
   const int grid = (int)std::min<size_t>((n + 255) / 256, 4096);
   hipLaunchKernelGGL(silu_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y, n);
-  return ok();
+  return launch_status();
 }
 
 extern "C" int vst_quick_gelu(const void* x, void* y, size_t n, void* stream) {
@@ -446,7 +444,7 @@ extern "C" int vst_quick_gelu(const void* x, void* y, size_t n, void* stream) {
   const int grid = (int)std::min<size_t>((n + 255) / 256, 4096);
   hipLaunchKernelGGL(quick_gelu_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y,
                      n);
-  return ok();
+  return launch_status();
 }
 
 extern "C" int vst_embed_tokens(const int* ids, int rows, int L, const void* tok, const void* pos, int C, float* y,
@@ -454,7 +452,7 @@ extern "C" int vst_embed_tokens(const int* ids, int rows, int L, const void* tok
   if (!ids || !tok || !pos || !y || rows <= 0 || L <= 0 || C <= 0 || ldy < C) return VST_ERR_ARG;
   hipLaunchKernelGGL(embed_tokens_kernel, dim3((rows * C + 255) / 256), dim3(256), 0, (hipStream_t)stream, ids, rows,
                      L, (const bf16_t*)tok, (const bf16_t*)pos, C, y, ldy);
-  return ok();
+  return launch_status();
 }
 
 extern "C" int vst_add(const void* a, const void* b, void* y, size_t n, void* stream) {
@@ -462,7 +460,7 @@ extern "C" int vst_add(const void* a, const void* b, void* y, size_t n, void* st
   const int grid = (int)std::min<size_t>((n + 255) / 256, 4096);
   hipLaunchKernelGGL(add_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)a, (const bf16_t*)b,
                      (bf16_t*)y, n);
-  return ok();
+  return launch_status();
 }
 
 extern "C" int vst_copy2d(const void* x, int ldx, void* y, int ldy, int rows, int cols, void* stream) {
@@ -470,7 +468,7 @@ extern "C" int vst_copy2d(const void* x, int ldx, void* y, int ldy, int rows, in
   const int tot = rows * cols;
   hipLaunchKernelGGL(copy2d_kernel, dim3((tot + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
                      ldx, (bf16_t*)y, ldy, rows, cols);
-  return ok();
+  return launch_status();
 }
 
 extern "C" int vst_pack_latents(const float* lat, int B, int Cl, int F, int HW, const float* sigmas,
@@ -480,7 +478,7 @@ extern "C" int vst_pack_latents(const float* lat, int B, int Cl, int F, int HW, 
   const size_t n = (size_t)B * Cl * F * HW;
   hipLaunchKernelGGL(pack_latents_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, lat, B,
                      Cl, F, HW, sigmas, step_idx, fixed_scale, ncopy, (bf16_t*)out);
-  return ok();
+  return launch_status();
 }
 
 extern "C" int vst_euler_cfg_step(const void* noise, int ncopy, float guidance, float* lat, int B, int Cl, int F,
@@ -489,13 +487,13 @@ extern "C" int vst_euler_cfg_step(const void* noise, int ncopy, float guidance, 
   const size_t n = (size_t)B * Cl * F * HW;
   hipLaunchKernelGGL(euler_cfg_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)noise, ncopy, guidance, lat, B, Cl, F, HW, sigmas, step_idx);
-  return ok();
+  return launch_status();
 }
 
 extern "C" int vst_step_advance(int* step_idx, int num_steps, void* stream) {
   if (!step_idx || num_steps <= 0) return VST_ERR_ARG;
   hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, step_idx, num_steps);
-  return ok();
+  return launch_status();
 }
 
 extern "C" int vst_permute_rows(const void* src, void* dst, int C, int d0, int d1, int d2, int d3, int p0, int p1,
@@ -511,7 +509,7 @@ extern "C" int vst_permute_rows(const void* src, void* dst, int C, int d0, int d
   const int grid = (int)std::min<size_t>((total + 255) / 256, 16384);
   hipLaunchKernelGGL(permute_rows_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)src,
                      (bf16_t*)dst, C, make_int4(d0, d1, d2, d3), make_int4(p0, p1, p2, p3), total);
-  return ok();
+  return launch_status();
 }
 
 extern "C" int vst_add_row_table(const void* x, int ldx, int C, int rows, const float* table, int div, int mod,
@@ -522,7 +520,7 @@ extern "C" int vst_add_row_table(const void* x, int ldx, int C, int rows, const 
   const int grid = (int)std::min<size_t>((total + 255) / 256, 16384);
   hipLaunchKernelGGL(add_row_table_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, ldx, C,
                      table, div, mod, (bf16_t*)y, ldy, total);
-  return ok();
+  return launch_status();
 }
 
 extern "C" int vst_unpack_tokens(const void* src, int B, int C, int F, int HW, float* out, void* stream) {
@@ -530,7 +528,7 @@ extern "C" int vst_unpack_tokens(const void* src, int B, int C, int F, int HW, f
   const dim3 grid((HW + 63) / 64, (C + 63) / 64, B * F);
   hipLaunchKernelGGL(unpack_tokens_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)src, C, F, HW,
                      out);
-  return ok();
+  return launch_status();
 }
 
 extern "C" int vst_transpose(const void* x, int ldx, int rows, int cols, void* y, int ldy, void* stream) {
@@ -539,7 +537,7 @@ extern "C" int vst_transpose(const void* x, int ldx, int rows, int cols, void* y
   if (grid.y > 65535) return VST_ERR_ARG;
   hipLaunchKernelGGL(transpose_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, ldx, rows, cols,
                      (bf16_t*)y, ldy);
-  return ok();
+  return launch_status();
 }
 
 extern "C" int vst_geglu_bwd(const void* p, int ldp, const void* g, int ldg, int M, int Nh, void* dp, int lddp,
@@ -551,7 +549,7 @@ extern "C" int vst_geglu_bwd(const void* p, int ldp, const void* g, int ldg, int
   const int grid = (int)std::min<size_t>((total + 255) / 256, 16384);
   hipLaunchKernelGGL(geglu_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)p, ldp,
                      (const bf16_t*)g, ldg, M, Nh, (bf16_t*)dp, lddp);
-  return ok();
+  return launch_status();
 }
 
 extern "C" int vst_zero_insert(const void* x, int nimg, int h, int w, int C, void* y, void* stream) {
@@ -560,7 +558,7 @@ extern "C" int vst_zero_insert(const void* x, int nimg, int h, int w, int C, voi
   const int grid = (int)std::min<size_t>((total + 255) / 256, 16384);
   hipLaunchKernelGGL(zero_insert_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, nimg, h, w,
                      C, (bf16_t*)y);
-  return ok();
+  return launch_status();
 }
 
 extern "C" int vst_sumpool2x2(const void* x, int nimg, int h, int w, int C, void* y, void* stream) {
@@ -569,7 +567,7 @@ extern "C" int vst_sumpool2x2(const void* x, int nimg, int h, int w, int C, void
   const int grid = (int)std::min<size_t>((total + 255) / 256, 16384);
   hipLaunchKernelGGL(sumpool2x2_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, nimg, h, w,
                      C, (bf16_t*)y);
-  return ok();
+  return launch_status();
 }
 
 static inline int grid_for(size_t total) { return (int)std::min<size_t>((total + 255) / 256, 16384); }
@@ -578,21 +576,21 @@ extern "C" int vst_nchw_to_nhwc(const float* src, int n, int C, int HW, float mu
   if (!src || !dst || n <= 0 || C <= 0 || HW <= 0 || ldd < C) return VST_ERR_ARG;
   hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(grid_for((size_t)n * HW * ldd)), dim3(256), 0, (hipStream_t)stream, src,
                      n, C, HW, mul, (bf16_t*)dst, ldd);
-  return ok();
+  return launch_status();
 }
 
 extern "C" int vst_nhwc_to_nchw(const void* src, int ld, int n, int C, int HW, float* dst, void* stream) {
   if (!src || !dst || n <= 0 || C <= 0 || HW <= 0 || ld < C) return VST_ERR_ARG;
   hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3(grid_for((size_t)n * C * HW)), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)src, ld, n, C, HW, dst);
-  return ok();
+  return launch_status();
 }
 
 extern "C" int vst_frames_to_u8(const void* src, int ld, int n, int C, int HW, void* dst, void* stream) {
   if (!src || !dst || n <= 0 || C <= 0 || HW <= 0 || ld < C) return VST_ERR_ARG;
   hipLaunchKernelGGL(frames_to_u8_kernel, dim3(grid_for((size_t)n * HW * C)), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)src, ld, n, C, HW, (uint8_t*)dst);
-  return ok();
+  return launch_status();
 }
 
 extern "C" int vst_vae_sample(const void* moments, int ld, int n, int HW, const float* eps, float mul, float* out,
@@ -600,14 +598,14 @@ extern "C" int vst_vae_sample(const void* moments, int ld, int n, int HW, const 
   if (!moments || !out || n <= 0 || HW <= 0 || ld < 8) return VST_ERR_ARG;
   hipLaunchKernelGGL(vae_sample_kernel, dim3(grid_for((size_t)n * 4 * HW)), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)moments, ld, n, HW, eps, mul, out);
-  return ok();
+  return launch_status();
 }
 
 extern "C" int vst_softmax_rows(const float* S, int lds, int rows, int n, float scale, void* P, int ldp, void* stream) {
   if (!S || !P || rows <= 0 || n <= 0 || lds < n || ldp < n || (lds & 3) || (ldp & 3)) return VST_ERR_ARG;
   hipLaunchKernelGGL(softmax_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, S, lds, rows, n,
                      scale * 1.4426950408889634f, (bf16_t*)P, ldp);
-  return ok();
+  return launch_status();
 }
 
 extern "C" const char* vst_version(void) { return "vst-hip 0.1 gfx950"; }
@@ -716,5 +714,5 @@ extern "C" int vst_colsum(const void* x, int ldx, int M, int N, float* y, void* 
   hipLaunchKernelGGL(colsum_rows32_kernel, dim3((N + 255) / 256, p.R2), dim3(256), 0, s, (const float*)part1, p.R, N,
                      part2);
   hipLaunchKernelGGL(colsum_rows32_kernel, dim3((N + 255) / 256, 1), dim3(256), 0, s, (const float*)part2, p.R2, N, y);
-  return ok();
+  return launch_status();
 }

@@ -21,12 +21,28 @@
 
 namespace vst {
 
-// Launch geometry shared by the stats and apply passes: grid (nchunk, nsamples), each workgroup owns
-// `rpc` consecutive rows of one sample and has rps x CH threads (CH = C/8 16-B channel chunks per row,
-// rps = 512 / CH rows in flight per step), so no lane idles whatever C is, and `rpc` is chosen by the
-// host so that every launch has >= ~256 workgroups (the 16x16-latent GroupNorms have only 256 rows
-// per frame: one 256-row chunk per sample gave 32 workgroups and 0.7 TB/s).
-__host__ __device__ inline int gn_rps(int C) { return max(1, 512 / (C / 8)); }
+constexpr int kGnStatsU = 8;  // independent 16-B loads in flight per thread, statistics pass
+constexpr int kGnApplyU = 4;  // ... apply pass
+constexpr int kLnlMI = 2;     // 16-row fragments per layernorm_lora workgroup
+
+// A thread's place in the launch geometry of the row-walking GroupNorm kernels (GnGeom on the host side): grid
+// (nchunk, nsamples), workgroup `chunk` of sample `s` owns rows [r_beg, r_end) of it and has rps x CH threads; this
+// thread walks rows r_beg + rph, + rps, ... at channels [c, c + 8).
+struct GnThread {
+  int s, chunk, rps, r_beg, r_end, rph, c;
+};
+__device__ __forceinline__ GnThread gn_thread(int C, int rows_per_sample, int rpc) {
+  const int CH = C / 8;
+  GnThread t;
+  t.s = blockIdx.y;
+  t.chunk = blockIdx.x;
+  t.rps = blockDim.x / CH;
+  t.r_beg = t.chunk * rpc;
+  t.r_end = min(rows_per_sample, t.r_beg + rpc);
+  t.rph = threadIdx.x / CH;
+  t.c = (threadIdx.x % CH) * 8;
+  return t;
+}
 
 // x1: [rows, C1] (ld1), x2: [rows, C2] (ld2): base pointer / stride of the source holding channel c
 __device__ __forceinline__ void gn_src(const bf16_t* x1, int ld1, int C1, const bf16_t* x2, int ld2, int c,
@@ -41,14 +57,9 @@ __global__ __launch_bounds__(512) void gn_stats_kernel(const bf16_t* __restrict_
                                                        float* __restrict__ part) {
   extern __shared__ __attribute__((aligned(16))) float gsm[];  // [rps][C] sums then sumsqs
   const int C = C1 + C2;
-  const int CH = C / 8;
-  const int rps = blockDim.x / CH;
-  const int s = blockIdx.y, chunk = blockIdx.x;
-  const int nchunk = gridDim.x;
-  const int r_beg = chunk * rpc;
-  const int r_end = min(rows_per_sample, r_beg + rpc);
+  const GnThread t = gn_thread(C, rows_per_sample, rpc);
+  const int s = t.s, chunk = t.chunk, nchunk = gridDim.x, rps = t.rps, rph = t.rph, c = t.c;
   const int tid = threadIdx.x;
-  const int cch = tid % CH, rph = tid / CH, c = cch * 8;
   const bf16_t* base;
   int ld;
   gn_src(x1, ld1, C1, x2, ld2, c, base, ld);
@@ -56,20 +67,16 @@ __global__ __launch_bounds__(512) void gn_stats_kernel(const bf16_t* __restrict_
   float a[8], q[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) { a[e] = 0.f; q[e] = 0.f; }
-  // GN_UNROLL independent 16-B loads in flight per thread
-#ifndef VST_GN_STATS_U
-#define VST_GN_STATS_U 8
-#endif
-  constexpr int GN_UNROLL = VST_GN_STATS_U;
-  for (int r = r_beg + rph; r < r_end; r += GN_UNROLL * rps) {
-    u32x4 v[GN_UNROLL];
+  constexpr int U = kGnStatsU;
+  for (int r = t.r_beg + rph; r < t.r_end; r += U * rps) {
+    u32x4 v[U];
 #pragma unroll
-    for (int u = 0; u < GN_UNROLL; ++u) {
+    for (int u = 0; u < U; ++u) {
       const int rr = r + u * rps;
-      v[u] = rr < r_end ? *reinterpret_cast<const u32x4*>(base + (size_t)rr * ld) : u32x4{0u, 0u, 0u, 0u};
+      v[u] = rr < t.r_end ? *reinterpret_cast<const u32x4*>(base + (size_t)rr * ld) : u32x4{0u, 0u, 0u, 0u};
     }
 #pragma unroll
-    for (int u = 0; u < GN_UNROLL; ++u) {
+    for (int u = 0; u < U; ++u) {
       float f[8];
       unpack8(v[u], f);
 #pragma unroll
@@ -105,41 +112,58 @@ __global__ __launch_bounds__(512) void gn_stats_kernel(const bf16_t* __restrict_
   }
 }
 
-// one 64-thread block per (sample, group): merge the chunk partials (sum, sumsq) in double, then
-// emit the per-channel affine  y = x * scale[s,c] + shift[s,c]  (scale = rstd*gamma,
-// shift = beta - mean*rstd*gamma) so the apply pass is one FMA per element.
-__global__ __launch_bounds__(64) void gn_finalize_kernel(const float* __restrict__ part, int nchunk,
-                                                         int rows_per_sample, int groups, int Cg, float eps,
-                                                         const float* __restrict__ gamma,
-                                                         const float* __restrict__ beta, float* __restrict__ scale,
-                                                         float* __restrict__ shift, int C,
-                                                         float* __restrict__ stats = nullptr) {
-  const int s = blockIdx.x / groups, gi = blockIdx.x - s * groups;
+// Tail of the GroupNorm finalize kernels, one 64-thread block per (sample b, group gi): a, q = this lane's part of
+// the group's sum and sum of squares over `count` elements.  Butterfly in double, then the per-channel affine
+// y = x * scale[b,c] + shift[b,c]  (scale = rstd*gamma, shift = beta - mean*rstd*gamma) so the apply pass is one
+// FMA per element, and (backward) the optional (mean, rstd) per (sample, group).
+__device__ __forceinline__ void gn_finalize_tail(double a, double q, double count, int b, int gi, int Cg, int C,
+                                                 float eps, const float* __restrict__ gamma,
+                                                 const float* __restrict__ beta, float* __restrict__ scale,
+                                                 float* __restrict__ shift, float* __restrict__ stats) {
   const int lane = threadIdx.x;
-  double a = 0.0, q = 0.0;
-  for (int c = lane; c < nchunk; c += 64) {
-    const float* p = part + (((size_t)s * nchunk + c) * groups + gi) * 2;
-    a += p[0];
-    q += p[1];
-  }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     a += __shfl_xor(a, o);
     q += __shfl_xor(q, o);
   }
-  const double n = (double)rows_per_sample * Cg;
-  const double mean = a / n;
-  const double var = fmax(q / n - mean * mean, 0.0);
+  const double mean = a / count;
+  const double var = fmax(q / count - mean * mean, 0.0);
   const float rstd = (float)(1.0 / sqrt(var + (double)eps));
   for (int c = gi * Cg + lane; c < (gi + 1) * Cg; c += 64) {
     const float sc = rstd * gamma[c];
-    scale[(size_t)s * C + c] = sc;
-    shift[(size_t)s * C + c] = beta[c] - (float)mean * sc;
+    scale[(size_t)b * C + c] = sc;
+    shift[(size_t)b * C + c] = beta[c] - (float)mean * sc;
   }
-  if (stats != nullptr && lane == 0) {  // backward: (mean, rstd) per (sample, group)
+  if (stats != nullptr && lane == 0) {
     stats[(size_t)blockIdx.x * 2] = (float)mean;
     stats[(size_t)blockIdx.x * 2 + 1] = rstd;
   }
+}
+
+// Merge a sample's chunk partials (sum, sumsq) in one fixed order (lane-strided over (global frame, chunk), then the
+// butterfly), read from the rank-major layout [P][nclips][Fl][nck][G][2].  Per-frame and per-clip GroupNorms of one
+// launch (vst_groupnorm, vst_groupnorm_bwd) are P = 1, Fl = 1: [nsamples][nchunk][G][2].  The motion-module GroupNorm
+// (statistics over every frame of a clip), frame-sharded or not, builds its statistics from per-FRAME chunk partials
+// (gn_stats_kernel with one sample per frame, chunking that depends only on the frame's row count), so a rank
+// holding some frames of a clip produces exactly the partials the unsharded forward produces for those frames, and
+// the all-gather leaves them rank-major (P = 1: the unsharded layout): the sharded and unsharded statistics are the
+// same bits whatever P is.
+__global__ __launch_bounds__(64) void gn_finalize_kernel(const float* __restrict__ part, int P, int nclips, int Fl,
+                                                         int nck, int groups, int Cg, double count, float eps,
+                                                         const float* __restrict__ gamma,
+                                                         const float* __restrict__ beta, float* __restrict__ scale,
+                                                         float* __restrict__ shift, int C,
+                                                         float* __restrict__ stats) {
+  const int b = blockIdx.x / groups, gi = blockIdx.x - b * groups;
+  const int per_rank = Fl * nck;  // a rank's partials of one clip are contiguous, in (frame, chunk) order
+  double a = 0.0, q = 0.0;
+  for (int c = threadIdx.x; c < P * per_rank; c += 64) {  // c: the clip's partials in (global frame, chunk) order
+    const int r = P == 1 ? 0 : c / per_rank;
+    const float* p = part + ((((size_t)r * nclips + b) * per_rank + (c - r * per_rank)) * groups + gi) * 2;
+    a += p[0];
+    q += p[1];
+  }
+  gn_finalize_tail(a, q, count, b, gi, Cg, C, eps, gamma, beta, scale, shift, stats);
 }
 
 // Column statistics of a bf16 tensor x [M, C] in the arithmetic of the 128x320 conv tiles' epilogue
@@ -211,20 +235,7 @@ __global__ __launch_bounds__(64) void gn_finalize_colstat_kernel(const float* __
     a += p[0];
     q += p[1];
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    a += __shfl_xor(a, o);
-    q += __shfl_xor(q, o);
-  }
-  const double n = (double)rows_per_sample * Cg;
-  const double mean = a / n;
-  const double var = fmax(q / n - mean * mean, 0.0);
-  const float rstd = (float)(1.0 / sqrt(var + (double)eps));
-  for (int c = gi * Cg + lane; c < (gi + 1) * Cg; c += 64) {
-    const float sc = rstd * gamma[c];
-    scale[(size_t)s * C + c] = sc;
-    shift[(size_t)s * C + c] = beta[c] - (float)mean * sc;
-  }
+  gn_finalize_tail(a, q, (double)rows_per_sample * Cg, s, gi, Cg, C, eps, gamma, beta, scale, shift, nullptr);
 }
 
 // ---- GroupNorm backward (training path) ----
@@ -238,6 +249,18 @@ __device__ __forceinline__ float silu_grad(float z) {
   const float sg = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-z * 1.4426950408889634f));
   return sg * (1.0f + z * (1.0f - sg));
 }
+__device__ __forceinline__ float gn_dz(float g, float x, float sc, float sh, int act) {
+  return act ? g * silu_grad(x * sc + sh) : g;
+}
+// this thread's 8 channels of the forward's affine (sample s, channels [c, c + 8))
+__device__ __forceinline__ void gn_load_affine(const float* __restrict__ scale, const float* __restrict__ shift,
+                                               size_t sc0, float* sc, float* sh) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    sc[e] = scale[sc0 + e];
+    sh[e] = shift[sc0 + e];
+  }
+}
 
 __global__ __launch_bounds__(512) void gn_bwd_sums_kernel(const bf16_t* __restrict__ x, int ldx,
                                                           const bf16_t* __restrict__ g, int ldg, int C,
@@ -245,27 +268,21 @@ __global__ __launch_bounds__(512) void gn_bwd_sums_kernel(const bf16_t* __restri
                                                           const float* __restrict__ shift, int act,
                                                           float* __restrict__ part2) {
   extern __shared__ __attribute__((aligned(16))) float bsm[];  // [rps][C] sum dz, then [rps][C] sum dz*x
-  const int CH = C / 8;
-  const int rps = blockDim.x / CH;
-  const int s = blockIdx.y, chunk = blockIdx.x, nchunk = gridDim.x;
-  const int r_beg = chunk * rpc, r_end = min(rows_per_sample, r_beg + rpc);
-  const int tid = threadIdx.x, cch = tid % CH, rph = tid / CH, c = cch * 8;
+  const GnThread t = gn_thread(C, rows_per_sample, rpc);
+  const int s = t.s, chunk = t.chunk, nchunk = gridDim.x, rps = t.rps, rph = t.rph, c = t.c;
+  const int tid = threadIdx.x;
   const size_t row0 = (size_t)s * rows_per_sample;
   float sc[8], sh[8], a[8], q[8];
+  gn_load_affine(scale, shift, (size_t)s * C + c, sc, sh);
 #pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    sc[e] = scale[(size_t)s * C + c + e];
-    sh[e] = shift[(size_t)s * C + c + e];
-    a[e] = 0.f;
-    q[e] = 0.f;
-  }
-  for (int r = r_beg + rph; r < r_end; r += rps) {
+  for (int e = 0; e < 8; ++e) { a[e] = 0.f; q[e] = 0.f; }
+  for (int r = t.r_beg + rph; r < t.r_end; r += rps) {
     float xv[8], gv[8];
     unpack8(*reinterpret_cast<const u32x4*>(x + (row0 + r) * ldx + c), xv);
     unpack8(*reinterpret_cast<const u32x4*>(g + (row0 + r) * ldg + c), gv);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      const float dz = act ? gv[e] * silu_grad(xv[e] * sc[e] + sh[e]) : gv[e];
+      const float dz = gn_dz(gv[e], xv[e], sc[e], sh[e], act);
       a[e] += dz;
       q[e] += dz * xv[e];
     }
@@ -327,28 +344,24 @@ __global__ __launch_bounds__(512) void gn_bwd_apply_kernel(const bf16_t* __restr
                                                            const float* __restrict__ shift, int act,
                                                            const float* __restrict__ coef, bf16_t* __restrict__ dx,
                                                            int lddx) {
-  const int CH = C / 8;
-  const int rps = blockDim.x / CH;
-  const int s = blockIdx.y;
-  const int r_beg = blockIdx.x * rpc, r_end = min(rows_per_sample, r_beg + rpc);
-  const int tid = threadIdx.x, cch = tid % CH, rph = tid / CH, c = cch * 8;
+  const GnThread t = gn_thread(C, rows_per_sample, rpc);
+  const int s = t.s, c = t.c;
   const size_t row0 = (size_t)s * rows_per_sample;
   float sc[8], sh[8], ca[8], c0[8], c1[8];
+  gn_load_affine(scale, shift, (size_t)s * C + c, sc, sh);
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
-    sc[e] = scale[(size_t)s * C + c + e];
-    sh[e] = shift[(size_t)s * C + c + e];
     ca[e] = coef[((size_t)s * C + c + e) * 3];
     c0[e] = coef[((size_t)s * C + c + e) * 3 + 1];
     c1[e] = coef[((size_t)s * C + c + e) * 3 + 2];
   }
-  for (int r = r_beg + rph; r < r_end; r += rps) {
+  for (int r = t.r_beg + t.rph; r < t.r_end; r += t.rps) {
     float xv[8], gv[8], o[8];
     unpack8(*reinterpret_cast<const u32x4*>(x + (row0 + r) * ldx + c), xv);
     unpack8(*reinterpret_cast<const u32x4*>(g + (row0 + r) * ldg + c), gv);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      const float dz = act ? gv[e] * silu_grad(xv[e] * sc[e] + sh[e]) : gv[e];
+      const float dz = gn_dz(gv[e], xv[e], sc[e], sh[e], act);
       o[e] = ca[e] * dz + c0[e] + c1[e] * xv[e];
     }
     *reinterpret_cast<u32x4*>(dx + (row0 + r) * lddx + c) = pack8(o);
@@ -374,12 +387,8 @@ __global__ __launch_bounds__(512) void gn_apply_kernel(const bf16_t* __restrict_
                                                        const float* __restrict__ shift, int act,
                                                        bf16_t* __restrict__ y, int ldy) {
   const int C = C1 + C2;
-  const int CH = C / 8;
-  const int rps = blockDim.x / CH;
-  const int s = blockIdx.y;
-  const int r_beg = blockIdx.x * rpc;
-  const int r_end = min(rows_per_sample, r_beg + rpc);
-  const int cch = threadIdx.x % CH, rph = threadIdx.x / CH, c = cch * 8;
+  const GnThread t = gn_thread(C, rows_per_sample, rpc);
+  const int s = t.s, rps = t.rps, r_end = t.r_end, c = t.c;
   const bf16_t* base;
   int ld;
   gn_src(x1, ld1, C1, x2, ld2, c, base, ld);
@@ -390,11 +399,8 @@ __global__ __launch_bounds__(512) void gn_apply_kernel(const bf16_t* __restrict_
   const f32x4* sc = reinterpret_cast<const f32x4*>(scale + (size_t)s * C + c);
   const f32x4* sh = reinterpret_cast<const f32x4*>(shift + (size_t)s * C + c);
   const f32x4 a0 = sc[0], a1 = sc[1], b0 = sh[0], b1 = sh[1];
-#ifndef VST_GN_APPLY_U
-#define VST_GN_APPLY_U 4
-#endif
-  constexpr int U = VST_GN_APPLY_U;  // loads in flight per thread
-  for (int r = r_beg + rph; r < r_end; r += U * rps) {
+  constexpr int U = kGnApplyU;
+  for (int r = t.r_beg + t.rph; r < r_end; r += U * rps) {
     u32x4 v[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -421,41 +427,38 @@ __global__ __launch_bounds__(512) void gn_apply_kernel(const bf16_t* __restrict_
   }
 }
 
-// Motion-module GroupNorm (statistics over every frame of a clip), frame-sharded or not.  The statistics are
-// built from per-FRAME chunk partials (gn_stats_kernel with one sample per frame, chunking that depends only on
-// the frame's row count), so a rank holding some frames of a clip produces exactly the partials the unsharded
-// forward produces for those frames.  The finalize merges the clip's F x nck partials in one fixed order, read
-// from the rank-major layout [P][clips][F/P][nck][G][2] an all-gather leaves (P = 1: the unsharded layout), so the
-// sharded and unsharded statistics are the same bits whatever P is.
-__global__ __launch_bounds__(64) void gn_finalize_parts_kernel(const float* __restrict__ part, int P, int nclips,
-                                                               int Fl, int nck, int groups, int Cg, double count,
-                                                               float eps, const float* __restrict__ gamma,
-                                                               const float* __restrict__ beta, float* __restrict__ scale,
-                                                               float* __restrict__ shift, int C) {
-  const int b = blockIdx.x / groups, gi = blockIdx.x - b * groups;
-  const int lane = threadIdx.x;
-  const int per_clip = P * Fl * nck;  // partials of one clip, in (global frame, chunk) order
-  double a = 0.0, q = 0.0;
-  for (int c = lane; c < per_clip; c += 64) {
-    const int f = c / nck, k = c - f * nck;
-    const int r = f / Fl, fl = f - r * Fl;
-    const float* p = part + (((((size_t)r * nclips + b) * Fl + fl) * nck + k) * groups + gi) * 2;
-    a += p[0];
-    q += p[1];
-  }
+// One wave per row, lane l holding the 8-channel chunks l, l + 64, ... (up to MAXCH of them) -- the row layout of
+// layernorm_kernel and layernorm_bwd_kernel.  Chunks past C, and every chunk of a row that is not `live`, are zeros.
+template <int MAXCH>
+__device__ __forceinline__ void ln_load_row(const bf16_t* __restrict__ row, bool live, int lane, int CH,
+                                            float (&v)[MAXCH][8]) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    a += __shfl_xor(a, o);
-    q += __shfl_xor(q, o);
+  for (int i = 0; i < MAXCH; ++i) {
+    const int cc = lane + 64 * i;
+    u32x4 raw = u32x4{0u, 0u, 0u, 0u};
+    if (cc < CH && live) raw = *reinterpret_cast<const u32x4*>(row + cc * 8);
+    unpack8(raw, v[i]);
   }
-  const double mean = a / count;
-  const double var = fmax(q / count - mean * mean, 0.0);
-  const float rstd = (float)(1.0 / sqrt(var + (double)eps));
-  for (int c = gi * Cg + lane; c < (gi + 1) * Cg; c += 64) {
-    const float sc = rstd * gamma[c];
-    scale[(size_t)b * C + c] = sc;
-    shift[(size_t)b * C + c] = beta[c] - (float)mean * sc;
+}
+// Two-pass row statistics: sum -> mean, then squared deviations over the real channels only -> rstd.
+template <int MAXCH>
+__device__ __forceinline__ void ln_row_stats(const float (&v)[MAXCH][8], int lane, int CH, int C, float eps,
+                                             float& mean, float& rstd) {
+  float sum = 0.f;
+#pragma unroll
+  for (int i = 0; i < MAXCH; ++i)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) sum += v[i][e];  // zero-filled past C
+  mean = wave_sum(sum) / C;
+  float sq = 0.f;
+#pragma unroll
+  for (int i = 0; i < MAXCH; ++i) {
+    if (lane + 64 * i < CH) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { const float d = v[i][e] - mean; sq += d * d; }
+    }
   }
+  rstd = rsqrtf(wave_sum(sq) / C + eps);
 }
 
 // LayerNorm: each wave normalises ROWS rows (all their 16-B loads issued before any reduction, so
@@ -471,16 +474,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const bf16_t* __restrict
   const int CH = C / 8;
   float v[ROWS][MAXCH][8];
 #pragma unroll
-  for (int r = 0; r < ROWS; ++r) {
-    const int row = row0 + r;
-#pragma unroll
-    for (int i = 0; i < MAXCH; ++i) {
-      const int cc = lane + 64 * i;
-      u32x4 raw = u32x4{0u, 0u, 0u, 0u};
-      if (cc < CH && row < rows) raw = *reinterpret_cast<const u32x4*>(x + (size_t)row * ldx + cc * 8);
-      unpack8(raw, v[r][i]);
-    }
-  }
+  for (int r = 0; r < ROWS; ++r) ln_load_row<MAXCH>(x + (size_t)(row0 + r) * ldx, row0 + r < rows, lane, CH, v[r]);
   float gg[MAXCH][8], bb[MAXCH][8];
 #pragma unroll
   for (int i = 0; i < MAXCH; ++i) {
@@ -497,21 +491,8 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const bf16_t* __restrict
   for (int r = 0; r < ROWS; ++r) {
     const int row = row0 + r;
     if (row >= rows) break;
-    float sum = 0.f;
-#pragma unroll
-    for (int i = 0; i < MAXCH; ++i)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) sum += v[r][i][e];  // zero-filled past C
-    const float mean = wave_sum(sum) / C;
-    float sq = 0.f;
-#pragma unroll
-    for (int i = 0; i < MAXCH; ++i) {
-      if (lane + 64 * i < CH) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { const float d = v[r][i][e] - mean; sq += d * d; }
-      }
-    }
-    const float rstd = rsqrtf(wave_sum(sq) / C + eps);
+    float mean, rstd;
+    ln_row_stats<MAXCH>(v[r], lane, CH, C, eps, mean, rstd);
     const float* pr = pe ? pe + (size_t)((row / pe_div) % pe_mod) * C : nullptr;
 #pragma unroll
     for (int i = 0; i < MAXCH; ++i) {
@@ -628,10 +609,7 @@ __global__ __launch_bounds__(512, 2) void layernorm_lora_kernel(const bf16_t* __
                                                                 const bf16_t* __restrict__ A, int R,
                                                                 bf16_t* __restrict__ y, int ldy, bf16_t* __restrict__ u,
                                                                 int ldu) {
-#ifndef VST_LNL_MI
-#define VST_LNL_MI 2
-#endif
-  constexpr int MI = VST_LNL_MI, NW = 8;  // MAXT = ceil(C / 256) k32-chunks per wave (C <= 256 * MAXT)
+  constexpr int MI = kLnlMI, NW = 8;  // MAXT = ceil(C / 256) k32-chunks per wave (C <= 256 * MAXT)
   __shared__ f32x4 red[NW][MI][NJ][64];
   __shared__ float st[NW][MI][16];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -785,31 +763,10 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const bf16_t* __rest
   }
   for (int row = blockIdx.x * 4 + w; row < rows; row += gridDim.x * 4) {
     float xv[MAXCH][8], gv[MAXCH][8];
-#pragma unroll
-    for (int i = 0; i < MAXCH; ++i) {
-      const int cc = lane + 64 * i;
-      u32x4 rx = u32x4{0u, 0u, 0u, 0u}, rg = u32x4{0u, 0u, 0u, 0u};
-      if (cc < CH) {
-        rx = *reinterpret_cast<const u32x4*>(x + (size_t)row * ldx + cc * 8);
-        rg = *reinterpret_cast<const u32x4*>(g + (size_t)row * ldg + cc * 8);
-      }
-      unpack8(rx, xv[i]);
-      unpack8(rg, gv[i]);
-    }
-    float sum = 0.f;
-#pragma unroll
-    for (int i = 0; i < MAXCH; ++i)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) sum += xv[i][e];
-    const float mean = wave_sum(sum) / C;
-    float sq = 0.f;
-#pragma unroll
-    for (int i = 0; i < MAXCH; ++i)
-      if (lane + 64 * i < CH) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { const float d = xv[i][e] - mean; sq += d * d; }
-      }
-    const float rstd = rsqrtf(wave_sum(sq) / C + eps);
+    ln_load_row<MAXCH>(x + (size_t)row * ldx, true, lane, CH, xv);
+    ln_load_row<MAXCH>(g + (size_t)row * ldg, true, lane, CH, gv);
+    float mean, rstd;
+    ln_row_stats<MAXCH>(xv, lane, CH, C, eps, mean, rstd);
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int i = 0; i < MAXCH; ++i)
@@ -890,91 +847,46 @@ static inline int gn_rpc_rows(int rows_per_sample) {
   return std::max(8, std::min(256, (rows_per_sample + 7) / 8));
 }
 static inline int gn_rpc(int nsamples, int rows_per_sample) {
-  static const long long target = std::max(1, env_int("VST_GN_TARGET", 256));  // tuning only (tools/norm_bench.py)
+  constexpr long long target = 256;
   const long long total = (long long)nsamples * rows_per_sample;
   return (int)std::max<long long>(8, std::min<long long>(256, (total + target - 1) / target));
 }
-static inline int gn_nchunk(int nsamples, int rows_per_sample) {
-  const int rpc = gn_rpc(nsamples, rows_per_sample);
-  return (rows_per_sample + rpc - 1) / rpc;
-}
-static inline int gn_nchunk_rows(int rows_per_sample) {
-  const int rpc = gn_rpc_rows(rows_per_sample);
-  return (rows_per_sample + rpc - 1) / rpc;
-}
-static inline size_t gn_part_floats(int nsamples, int rows_per_sample, int groups) {
-  const int nchunk = gn_nchunk(nsamples, rows_per_sample);
-  return ((size_t)nsamples * nchunk * groups * 2 + 3) & ~(size_t)3;  // keep scale/shift 16-B aligned
-}
-static inline size_t gn_part_floats_rows(int nsamples, int rows_per_sample, int groups) {
-  return ((size_t)nsamples * gn_nchunk_rows(rows_per_sample) * groups * 2 + 3) & ~(size_t)3;
+
+// Launch geometry shared by the row-walking passes (GnThread on the device side): grid (nchunk, nsamples), each
+// workgroup owns `rpc` consecutive rows of one sample and has rps x CH threads (CH = C/8 16-B channel chunks per
+// row, rps = 512 / CH rows in flight per step), so no lane idles whatever C is, and `rpc` is chosen by the rules
+// above so that every launch has >= ~256 workgroups (the 16x16-latent GroupNorms have only 256 rows per frame: one
+// 256-row chunk per sample gave 32 workgroups and 0.7 TB/s).
+struct GnGeom {
+  int C, CH, rps, rpc, nchunk;
+  size_t lds;  // [2][rps][C] floats: the stats and backward-sums passes' row-phase fold
+  GnGeom(int C_, int rows_per_sample, int rpc_)
+      : C(C_), CH(C_ / 8), rps(std::max(1, 512 / std::max(1, C_ / 8))), rpc(rpc_),
+        nchunk((rows_per_sample + rpc_ - 1) / rpc_), lds((size_t)2 * rps * C_ * sizeof(float)) {}
+  dim3 grid(int nsamples) const { return dim3(nchunk, nsamples); }
+  dim3 block() const { return dim3(rps * CH); }
+  // floats of the [nsamples][nchunk][groups][2] partials, rounded up so what follows stays 16-B aligned
+  size_t part_floats(int nsamples, int groups) const {
+    return ((size_t)nsamples * nchunk * groups * 2 + 3) & ~(size_t)3;
+  }
+};
+static inline GnGeom gn_fwd_geom(int C, int rows_per_sample) {
+  return GnGeom(C, rows_per_sample, gn_rpc_rows(rows_per_sample));
 }
 
-extern "C" size_t vst_groupnorm_workspace_bytes(int nsamples, int rows_per_sample, int groups, int C) {
-  return (gn_part_floats_rows(nsamples, rows_per_sample, groups) + (size_t)2 * nsamples * C) * sizeof(float);
+static void launch_gn_stats(const GnGeom& gm, int nsamples, const void* x1, int ld1, int C1, const void* x2, int ld2,
+                            int C2, int rows_per_sample, int groups, float* part, hipStream_t s) {
+  hipLaunchKernelGGL(gn_stats_kernel, gm.grid(nsamples), gm.block(), gm.lds, s, (const bf16_t*)x1, ld1, C1,
+                     (const bf16_t*)x2, ld2, C2, rows_per_sample, gm.rpc, groups, part);
+}
+static void launch_gn_apply(const GnGeom& gm, int nsamples, const void* x1, int ld1, int C1, const void* x2, int ld2,
+                            int C2, int rows_per_sample, const float* scale, const float* shift, int silu_act, void* y,
+                            int ldy, hipStream_t s) {
+  hipLaunchKernelGGL(gn_apply_kernel, gm.grid(nsamples), gm.block(), 0, s, (const bf16_t*)x1, ld1, C1,
+                     (const bf16_t*)x2, ld2, C2, rows_per_sample, gm.rpc, scale, shift, silu_act, (bf16_t*)y, ldy);
 }
 
-extern "C" int vst_groupnorm(const void* x1, int ld1, int C1, const void* x2, int ld2, int C2, int nsamples,
-                             int rows_per_sample, int groups, float eps, const float* gamma, const float* beta,
-                             int silu_act, void* y, int ldy, void* workspace, void* stream) {
-  const int C = C1 + (x2 ? C2 : 0);
-  if (!x1 || !y || !workspace || !gamma || !beta || nsamples <= 0 || rows_per_sample <= 0 || groups <= 0)
-    return VST_ERR_ARG;
-  if (C % groups || C % 8 || C1 % 8 || (ld1 & 7) || (ldy & 7) || (x2 && (ld2 & 7))) return VST_ERR_ARG;
-  if (C > 4096) return VST_ERR_ARG;
-  if (!x2) C2 = 0;
-  hipStream_t s = (hipStream_t)stream;
-  const int rpc = gn_rpc_rows(rows_per_sample);
-  const int nchunk = gn_nchunk_rows(rows_per_sample);
-  float* part = (float*)workspace;
-  float* scale = part + gn_part_floats_rows(nsamples, rows_per_sample, groups);
-  float* shift = scale + (size_t)nsamples * C;
-  const int CH = C / 8;
-  const int rps = gn_rps(C);
-  const size_t lds = (size_t)2 * rps * C * sizeof(float);
-  hipLaunchKernelGGL(gn_stats_kernel, dim3(nchunk, nsamples), dim3(rps * CH), lds, s, (const bf16_t*)x1, ld1, C1,
-                     (const bf16_t*)x2, ld2, C2, rows_per_sample, rpc, groups, part);
-  hipLaunchKernelGGL(gn_finalize_kernel, dim3(nsamples * groups), dim3(64), 0, s, part, nchunk, rows_per_sample,
-                     groups, C / groups, eps, gamma, beta, scale, shift, C);
-  hipLaunchKernelGGL(gn_apply_kernel, dim3(nchunk, nsamples), dim3(rps * CH), 0, s, (const bf16_t*)x1, ld1, C1,
-                     (const bf16_t*)x2, ld2, C2, rows_per_sample, rpc, scale, shift, silu_act, (bf16_t*)y, ldy);
-  return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
-}
-
-// Column statistics of x [M, C] (C % 8 == 0) as the 128x320 conv epilogue writes them: cs [ceil(M / 128)][C][2].
-extern "C" int vst_colstat(const void* x, int ldx, int M, int C, float* cs, void* stream) {
-  if (!x || !cs || M <= 0 || C <= 0 || C % 8 || (ldx & 7)) return VST_ERR_ARG;
-  hipLaunchKernelGGL(gn_colstat_kernel, dim3((M + 127) / 128, (C + 319) / 320), dim3(512), 0, (hipStream_t)stream,
-                     (const bf16_t*)x, ldx, M, C, cs);
-  return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
-}
-
-// vst_groupnorm with the statistics from column statistics of x1 (and x2) written by the producing conv
-// (vst_conv3x3_colstat, 128-row tiles): rows_per_sample % 128 == 0.  workspace: vst_groupnorm_workspace_bytes.
-extern "C" int vst_groupnorm_colstat(const void* x1, int ld1, int C1, const float* cs1, const void* x2, int ld2, int C2,
-                                     const float* cs2, int nsamples, int rows_per_sample, int groups, float eps,
-                                     const float* gamma, const float* beta, int silu_act, void* y, int ldy,
-                                     void* workspace, void* stream) {
-  const int C = C1 + (x2 ? C2 : 0);
-  if (!x1 || !cs1 || !y || !workspace || !gamma || !beta || nsamples <= 0 || rows_per_sample <= 0 || groups <= 0)
-    return VST_ERR_ARG;
-  if ((x2 && !cs2) || rows_per_sample % 128) return VST_ERR_ARG;
-  if (C % groups || C % 8 || C1 % 8 || (ld1 & 7) || (ldy & 7) || (x2 && (ld2 & 7))) return VST_ERR_ARG;
-  if (C > 4096) return VST_ERR_ARG;
-  if (!x2) C2 = 0;
-  hipStream_t s = (hipStream_t)stream;
-  const int rpc = gn_rpc_rows(rows_per_sample);
-  const int nchunk = gn_nchunk_rows(rows_per_sample);
-  float* scale = (float*)workspace + gn_part_floats_rows(nsamples, rows_per_sample, groups);
-  float* shift = scale + (size_t)nsamples * C;
-  hipLaunchKernelGGL(gn_finalize_colstat_kernel, dim3(nsamples * groups), dim3(64), 0, s, cs1, C1, cs2, C2,
-                     rows_per_sample / 128, rows_per_sample, groups, C / groups, eps, gamma, beta, scale, shift);
-  hipLaunchKernelGGL(gn_apply_kernel, dim3(nchunk, nsamples), dim3(gn_rps(C) * (C / 8)), 0, s, (const bf16_t*)x1,
-                     ld1, C1, (const bf16_t*)x2, ld2, C2, rows_per_sample, rpc, scale, shift, silu_act, (bf16_t*)y,
-                     ldy);
-  return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
-}
-
+// the argument conditions every GroupNorm entry point shares; each adds its own
 static int gn_check(const void* x1, int ld1, int C1, const void* x2, int ld2, int C2, int nsamples,
                     int rows_per_sample, int groups) {
   const int C = C1 + (x2 ? C2 : 0);
@@ -984,21 +896,70 @@ static int gn_check(const void* x1, int ld1, int C1, const void* x2, int ld2, in
   return VST_OK;
 }
 
+extern "C" size_t vst_groupnorm_workspace_bytes(int nsamples, int rows_per_sample, int groups, int C) {
+  return (gn_fwd_geom(C, rows_per_sample).part_floats(nsamples, groups) + (size_t)2 * nsamples * C) * sizeof(float);
+}
+
+extern "C" int vst_groupnorm(const void* x1, int ld1, int C1, const void* x2, int ld2, int C2, int nsamples,
+                             int rows_per_sample, int groups, float eps, const float* gamma, const float* beta,
+                             int silu_act, void* y, int ldy, void* workspace, void* stream) {
+  if (gn_check(x1, ld1, C1, x2, ld2, C2, nsamples, rows_per_sample, groups) || !y || !workspace || !gamma || !beta ||
+      (ldy & 7))
+    return VST_ERR_ARG;
+  if (!x2) C2 = 0;
+  const int C = C1 + C2;
+  hipStream_t s = (hipStream_t)stream;
+  const GnGeom gm = gn_fwd_geom(C, rows_per_sample);
+  float* part = (float*)workspace;
+  float* scale = part + gm.part_floats(nsamples, groups);
+  float* shift = scale + (size_t)nsamples * C;
+  launch_gn_stats(gm, nsamples, x1, ld1, C1, x2, ld2, C2, rows_per_sample, groups, part, s);
+  hipLaunchKernelGGL(gn_finalize_kernel, dim3(nsamples * groups), dim3(64), 0, s, part, 1, nsamples, 1, gm.nchunk,
+                     groups, C / groups, (double)rows_per_sample * (C / groups), eps, gamma, beta, scale, shift, C,
+                     (float*)nullptr);
+  launch_gn_apply(gm, nsamples, x1, ld1, C1, x2, ld2, C2, rows_per_sample, scale, shift, silu_act, y, ldy, s);
+  return launch_status();
+}
+
+// Column statistics of x [M, C] (C % 8 == 0) as the 128x320 conv epilogue writes them: cs [ceil(M / 128)][C][2].
+extern "C" int vst_colstat(const void* x, int ldx, int M, int C, float* cs, void* stream) {
+  if (!x || !cs || M <= 0 || C <= 0 || C % 8 || (ldx & 7)) return VST_ERR_ARG;
+  hipLaunchKernelGGL(gn_colstat_kernel, dim3((M + 127) / 128, (C + 319) / 320), dim3(512), 0, (hipStream_t)stream,
+                     (const bf16_t*)x, ldx, M, C, cs);
+  return launch_status();
+}
+
+// vst_groupnorm with the statistics from column statistics of x1 (and x2) written by the producing conv
+// (vst_conv3x3_colstat, 128-row tiles): rows_per_sample % 128 == 0.  workspace: vst_groupnorm_workspace_bytes.
+extern "C" int vst_groupnorm_colstat(const void* x1, int ld1, int C1, const float* cs1, const void* x2, int ld2, int C2,
+                                     const float* cs2, int nsamples, int rows_per_sample, int groups, float eps,
+                                     const float* gamma, const float* beta, int silu_act, void* y, int ldy,
+                                     void* workspace, void* stream) {
+  if (gn_check(x1, ld1, C1, x2, ld2, C2, nsamples, rows_per_sample, groups) || !cs1 || !y || !workspace || !gamma ||
+      !beta || (x2 && !cs2) || rows_per_sample % 128 || (ldy & 7))
+    return VST_ERR_ARG;
+  if (!x2) C2 = 0;
+  const int C = C1 + C2;
+  hipStream_t s = (hipStream_t)stream;
+  const GnGeom gm = gn_fwd_geom(C, rows_per_sample);
+  float* scale = (float*)workspace + gm.part_floats(nsamples, groups);
+  float* shift = scale + (size_t)nsamples * C;
+  hipLaunchKernelGGL(gn_finalize_colstat_kernel, dim3(nsamples * groups), dim3(64), 0, s, cs1, C1, cs2, C2,
+                     rows_per_sample / 128, rows_per_sample, groups, C / groups, eps, gamma, beta, scale, shift);
+  launch_gn_apply(gm, nsamples, x1, ld1, C1, x2, ld2, C2, rows_per_sample, scale, shift, silu_act, y, ldy, s);
+  return launch_status();
+}
+
 extern "C" int vst_groupnorm_frame_chunks(int rows_per_frame) {
-  return rows_per_frame > 0 ? gn_nchunk_rows(rows_per_frame) : 0;
+  return rows_per_frame > 0 ? gn_fwd_geom(0, rows_per_frame).nchunk : 0;  // (the chunking does not depend on C)
 }
 
 extern "C" int vst_groupnorm_frame_partials(const void* x1, int ld1, int C1, int nframes, int rows_per_frame,
                                             int groups, float* part, void* stream) {
   if (gn_check(x1, ld1, C1, nullptr, 0, 0, nframes, rows_per_frame, groups) || !part) return VST_ERR_ARG;
-  const int C = C1;
-  hipStream_t s = (hipStream_t)stream;
-  const int rps = gn_rps(C);
-  const size_t lds = (size_t)2 * rps * C * sizeof(float);
-  hipLaunchKernelGGL(gn_stats_kernel, dim3(gn_nchunk_rows(rows_per_frame), nframes), dim3(rps * (C / 8)), lds, s,
-                     (const bf16_t*)x1, ld1, C1, (const bf16_t*)nullptr, 0, 0, rows_per_frame,
-                     gn_rpc_rows(rows_per_frame), groups, part);
-  return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
+  launch_gn_stats(gn_fwd_geom(C1, rows_per_frame), nframes, x1, ld1, C1, nullptr, 0, 0, rows_per_frame, groups, part,
+                  (hipStream_t)stream);
+  return launch_status();
 }
 
 extern "C" int vst_groupnorm_apply_partials(const void* x1, int ld1, int C1, int nclips, int frames_local,
@@ -1013,16 +974,15 @@ extern "C" int vst_groupnorm_apply_partials(const void* x1, int ld1, int C1, int
   hipStream_t s = (hipStream_t)stream;
   float* scale = scale_shift;
   float* shift = scale + (size_t)nclips * C;
-  const int nck = gn_nchunk_rows(rows_per_frame);
+  const int rpc = gn_rpc_rows(rows_per_frame);  // the frame's chunking, for the statistics and the apply alike
+  const int nck = GnGeom(C, rows_per_frame, rpc).nchunk;
   const double count = (double)nranks * frames_local * rows_per_frame * (C / groups);
-  hipLaunchKernelGGL(gn_finalize_parts_kernel, dim3(nclips * groups), dim3(64), 0, s, part, nranks, nclips,
-                     frames_local, nck, groups, C / groups, count, eps, gamma, beta, scale, shift, C);
+  hipLaunchKernelGGL(gn_finalize_kernel, dim3(nclips * groups), dim3(64), 0, s, part, nranks, nclips, frames_local,
+                     nck, groups, C / groups, count, eps, gamma, beta, scale, shift, C, (float*)nullptr);
   const int rows_per_clip = frames_local * rows_per_frame;
-  const int rpc = gn_rpc_rows(rows_per_frame);
-  hipLaunchKernelGGL(gn_apply_kernel, dim3((rows_per_clip + rpc - 1) / rpc, nclips), dim3(gn_rps(C) * (C / 8)), 0, s,
-                     (const bf16_t*)x1, ld1, C1, (const bf16_t*)nullptr, 0, 0, rows_per_clip, rpc, scale, shift,
-                     silu_act, (bf16_t*)y, ldy);
-  return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
+  launch_gn_apply(GnGeom(C, rows_per_clip, rpc), nclips, x1, ld1, C1, nullptr, 0, 0, rows_per_clip, scale, shift,
+                  silu_act, y, ldy, s);
+  return launch_status();
 }
 
 extern "C" int vst_layernorm(const void* x, int ldx, int C, int rows, const float* gamma, const float* beta,
@@ -1035,39 +995,25 @@ extern "C" int vst_layernorm(const void* x, int ldx, int C, int rows, const floa
 #define VST_LNG(LPR, RIT)                                                                                      \
   hipLaunchKernelGGL((layernorm_g_kernel<LPR, RIT>), dim3((rows + 4 * (64 / LPR) * RIT - 1) / (4 * (64 / LPR) * RIT)), \
                      blk, 0, s, (const bf16_t*)x, ldx, C, rows, gamma, beta, eps, pe, pe_div, pe_mod, (bf16_t*)y, ldy)
+#define VST_LN(MC, R)                                                                                          \
+  hipLaunchKernelGGL((layernorm_kernel<MC, R>), dim3((rows + 4 * R - 1) / (4 * R)), blk, 0, s, (const bf16_t*)x, ldx, \
+                     C, rows, gamma, beta, eps, pe, pe_div, pe_mod, (bf16_t*)y, ldy)
   // A/B switch (tools/ab_bench.sh): on when the variable is set at all, whatever its value
   static const bool generic_only = env_int("VST_LN_GENERIC", INT_MIN) != INT_MIN;
   const bool g16 = !generic_only && ((uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)pe) % 16 == 0;
   // RIT = row passes per wave whose loads are all in flight before the first reduction.  C = 1280 (M = 8192 rows in the
   // step): 1 pass, 1024 workgroups: 9.8 -> 9.2 us per launch graph-timed, step -0.15..-0.2 ms same-box
-  // (profiles/r3_ab_ln_rit.txt); VST_LN_RIT (1 / 2 / 4) overrides every width for A/B.
-  static const int rit_env = env_int("VST_LN_RIT", 0);
-#define VST_LNG_RIT(LPR, DEF)                                        \
-  {                                                                  \
-    const int rit = rit_env ? rit_env : (DEF);                       \
-    if (rit == 1) VST_LNG(LPR, 1);                                   \
-    else if (rit == 4) VST_LNG(LPR, 4);                              \
-    else VST_LNG(LPR, 2);                                            \
-    return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH; \
-  }
-  if (g16 && C == 320) VST_LNG_RIT(8, 2)
-  if (g16 && C == 640) VST_LNG_RIT(16, 2)
-  if (g16 && C == 1280) VST_LNG_RIT(32, 1)
-#undef VST_LNG_RIT
+  // (profiles/r3_ab_ln_rit.txt).
+  if (g16 && C == 320) VST_LNG(8, 2);
+  else if (g16 && C == 640) VST_LNG(16, 2);
+  else if (g16 && C == 1280) VST_LNG(32, 1);
+  else if (CH <= 64) VST_LN(1, 4);
+  else if (CH <= 128) VST_LN(2, 2);
+  else if (CH <= 256) VST_LN(4, 2);
+  else return VST_ERR_ARG;
 #undef VST_LNG
-#define VST_LN(MC, R)                                                                                          \
-  hipLaunchKernelGGL((layernorm_kernel<MC, R>), dim3((rows + 4 * R - 1) / (4 * R)), blk, 0, s, (const bf16_t*)x, ldx, \
-                     C, rows, gamma, beta, eps, pe, pe_div, pe_mod, (bf16_t*)y, ldy)
-  if (CH <= 64)
-    VST_LN(1, 4);
-  else if (CH <= 128)
-    VST_LN(2, 2);
-  else if (CH <= 256)
-    VST_LN(4, 2);
 #undef VST_LN
-  else
-    return VST_ERR_ARG;
-  return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
+  return launch_status();
 }
 
 extern "C" int vst_layernorm_lora(const void* x, int ldx, int C, int rows, const float* gamma, const float* beta,
@@ -1075,7 +1021,7 @@ extern "C" int vst_layernorm_lora(const void* x, int ldx, int C, int rows, const
   if (!x || !y || !u || !A || !gamma || !beta || rows <= 0 || C <= 0 || (C & 31) || C > 1280) return VST_ERR_ARG;
   if (R <= 0 || R > 64 || (R & 15) || (ldx & 7) || (ldy & 7) || (ldu & 3) || ldu < R) return VST_ERR_ARG;
   if (((size_t)(rows - 1) * ldx + C) * 2 > 0x7fffffffULL) return VST_ERR_ARG;  // x through a 32-bit buffer offset
-  const dim3 grid((rows + 16 * VST_LNL_MI - 1) / (16 * VST_LNL_MI)), blk(512);
+  const dim3 grid((rows + 16 * kLnlMI - 1) / (16 * kLnlMI)), blk(512);
   hipStream_t s = (hipStream_t)stream;
 #define VST_LNL(NJ, MT)                                                                                         \
   hipLaunchKernelGGL((layernorm_lora_kernel<NJ, MT>), grid, blk, 0, s, (const bf16_t*)x, ldx, C, rows, gamma, beta, \
@@ -1093,7 +1039,7 @@ extern "C" int vst_layernorm_lora(const void* x, int ldx, int C, int rows, const
   }
 #undef VST_LNL_T
 #undef VST_LNL
-  return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
+  return launch_status();
 }
 
 // fp32 residual stream + LayerNorm (the CLIP text encoders, text_encoder.py): h_out = h + y (y bf16, optional),
@@ -1150,7 +1096,7 @@ extern "C" int vst_residual_layernorm(const float* h, int ldh, const void* y, in
     return VST_ERR_ARG;
   hipLaunchKernelGGL(residual_layernorm_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, h, ldh,
                      (const bf16_t*)y, ldy, C, gamma, beta, eps, h_out, ldho, (bf16_t*)n, ldn);
-  return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
+  return launch_status();
 }
 
 // ---- LayerNorm backward (training path) ----
@@ -1181,53 +1127,59 @@ extern "C" int vst_layernorm_bwd(const void* x, int ldx, const void* g, int ldg,
   if (dgamma)
     hipLaunchKernelGGL(layernorm_bwd_reduce_kernel, dim3((2 * C + 15) / 16), dim3(256), 0, s, part, grid, C, dgamma,
                        dbeta);
-  return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
+  return launch_status();
 }
 
 // ---- GroupNorm backward host side ----
-static inline size_t gnb_floats(int nsamples, int rows_per_sample, int groups, int C) {
-  const size_t nchunk = gn_nchunk(nsamples, rows_per_sample);
-  const size_t a4 = 4;
-  auto up = [&](size_t n) { return (n + a4 - 1) / a4 * a4; };
-  return up(gn_part_floats(nsamples, rows_per_sample, groups)) + up((size_t)2 * nsamples * C)  // part, scale/shift
-         + up((size_t)2 * nsamples * groups) + up((size_t)nsamples * nchunk * 2 * C)           // stats, part2
-         + up((size_t)2 * nsamples * C) + up((size_t)3 * nsamples * C);                        // chsum, coef
+// Workspace carve, in floats, every piece 16-B aligned: part | scale, shift | stats | part2 | chsum | coef.
+struct GnBwdWs {
+  size_t scale, stats, part2, chsum, coef, total;  // (part is at 0, shift at scale + nsamples * C)
+};
+static GnBwdWs gn_bwd_ws(const GnGeom& gm, int nsamples, int groups) {
+  auto up = [](size_t n) { return (n + 3) / 4 * 4; };
+  const size_t nsC = (size_t)nsamples * gm.C;
+  GnBwdWs w;
+  w.scale = gm.part_floats(nsamples, groups);
+  w.stats = w.scale + up(2 * nsC);
+  w.part2 = w.stats + up((size_t)2 * nsamples * groups);
+  w.chsum = w.part2 + up((size_t)nsamples * gm.nchunk * 2 * gm.C);
+  w.coef = w.chsum + up(2 * nsC);
+  w.total = w.coef + up(3 * nsC);
+  return w;
 }
 
 extern "C" size_t vst_groupnorm_bwd_workspace_bytes(int nsamples, int rows_per_sample, int groups, int C) {
-  return gnb_floats(nsamples, rows_per_sample, groups, C) * sizeof(float);
+  const GnGeom gm(C, rows_per_sample, gn_rpc(nsamples, rows_per_sample));
+  return gn_bwd_ws(gm, nsamples, groups).total * sizeof(float);
 }
 
 extern "C" int vst_groupnorm_bwd(const void* x, int ldx, const void* g, int ldg, int C, int nsamples,
                                  int rows_per_sample, int groups, float eps, const float* gamma, const float* beta,
                                  int silu_act, void* dx, int lddx, float* dgamma, float* dbeta, void* workspace,
                                  void* stream) {
-  if (!x || !g || !dx || !gamma || !beta || !dgamma || !dbeta || !workspace || nsamples <= 0 ||
-      rows_per_sample <= 0 || groups <= 0 || C % groups || C % 8 || C > 4096 || (ldx & 7) || (ldg & 7) || (lddx & 7))
+  if (gn_check(x, ldx, C, nullptr, 0, 0, nsamples, rows_per_sample, groups) || !g || !dx || !gamma || !beta ||
+      !dgamma || !dbeta || !workspace || (ldg & 7) || (lddx & 7))
     return VST_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-  const int rpc = gn_rpc(nsamples, rows_per_sample);
-  const int nchunk = gn_nchunk(nsamples, rows_per_sample);
-  const int CH = C / 8, rps = gn_rps(C);
-  auto up = [](size_t n) { return (n + 3) / 4 * 4; };
+  const GnGeom gm(C, rows_per_sample, gn_rpc(nsamples, rows_per_sample));
+  const GnBwdWs w = gn_bwd_ws(gm, nsamples, groups);
   float* part = (float*)workspace;
-  float* scale = part + up(gn_part_floats(nsamples, rows_per_sample, groups));
+  float* scale = part + w.scale;
   float* shift = scale + nsamples * (size_t)C;
-  float* stats = scale + up((size_t)2 * nsamples * C);
-  float* part2 = stats + up((size_t)2 * nsamples * groups);
-  float* chsum = part2 + up((size_t)nsamples * nchunk * 2 * C);
-  float* coef = chsum + up((size_t)2 * nsamples * C);
-  const size_t lds = (size_t)2 * rps * C * sizeof(float);
-  hipLaunchKernelGGL(gn_stats_kernel, dim3(nchunk, nsamples), dim3(rps * CH), lds, s, (const bf16_t*)x, ldx, C,
-                     (const bf16_t*)nullptr, 0, 0, rows_per_sample, rpc, groups, part);
-  hipLaunchKernelGGL(gn_finalize_kernel, dim3(nsamples * groups), dim3(64), 0, s, part, nchunk, rows_per_sample,
-                     groups, C / groups, eps, gamma, beta, scale, shift, C, stats);
-  hipLaunchKernelGGL(gn_bwd_sums_kernel, dim3(nchunk, nsamples), dim3(rps * CH), lds, s, (const bf16_t*)x, ldx,
-                     (const bf16_t*)g, ldg, C, rows_per_sample, rpc, scale, shift, silu_act, part2);
-  hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3(nsamples * groups), dim3(64), 0, s, part2, nchunk, C, groups,
+  float* stats = part + w.stats;
+  float* part2 = part + w.part2;
+  float* chsum = part + w.chsum;
+  float* coef = part + w.coef;
+  launch_gn_stats(gm, nsamples, x, ldx, C, nullptr, 0, 0, rows_per_sample, groups, part, s);
+  hipLaunchKernelGGL(gn_finalize_kernel, dim3(nsamples * groups), dim3(64), 0, s, part, 1, nsamples, 1, gm.nchunk,
+                     groups, C / groups, (double)rows_per_sample * (C / groups), eps, gamma, beta, scale, shift, C,
+                     stats);
+  hipLaunchKernelGGL(gn_bwd_sums_kernel, gm.grid(nsamples), gm.block(), gm.lds, s, (const bf16_t*)x, ldx,
+                     (const bf16_t*)g, ldg, C, rows_per_sample, gm.rpc, scale, shift, silu_act, part2);
+  hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3(nsamples * groups), dim3(64), 0, s, part2, gm.nchunk, C, groups,
                      rows_per_sample, stats, gamma, chsum, coef);
-  hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3(nchunk, nsamples), dim3(rps * CH), 0, s, (const bf16_t*)x, ldx,
-                     (const bf16_t*)g, ldg, C, rows_per_sample, rpc, scale, shift, silu_act, coef, (bf16_t*)dx, lddx);
+  hipLaunchKernelGGL(gn_bwd_apply_kernel, gm.grid(nsamples), gm.block(), 0, s, (const bf16_t*)x, ldx,
+                     (const bf16_t*)g, ldg, C, rows_per_sample, gm.rpc, scale, shift, silu_act, coef, (bf16_t*)dx, lddx);
   hipLaunchKernelGGL(gn_bwd_param_kernel, dim3((C + 255) / 256), dim3(256), 0, s, chsum, nsamples, C, dgamma, dbeta);
-  return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
+  return launch_status();
 }

@@ -152,3 +152,8 @@ __device__ __forceinline__ int xcd_remap(int orig, int nwg) {
 #define VST_ERR_ARG 1
 #define VST_ERR_LAUNCH 2
 #define VST_ERR_UNSUPPORTED 3
+
+namespace vst {
+// Host side: the status an entry point returns after its launches.
+inline int launch_status() { return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH; }
+}  // namespace vst
