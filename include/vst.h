@@ -369,6 +369,27 @@ int vst_nhwc_to_nchw(const void* src, int ld, int n, int C, int HW, float* dst, 
 int vst_frames_to_u8(const void* src, int ld, int n, int C, int HW, void* dst, void* stream);
 int vst_vae_sample(const void* moments, int ld, int n, int HW, const float* eps, float mul, float* out, void* stream);
 
+/* ---- Video-to-video: entering the denoise loop part-way from an encoded source clip (SDEdit / img2img strength)
+ * with an optional per-pixel keep mask (latent inpainting for a 4-channel UNet).  No reference counterpart (its loop
+ * starts from noise, inference_animatediff.py:88-95); the definitions are DESIGN.md §13, after the diffusers img2img /
+ * inpaint pipelines.  Every entry returns 1 before any launch on a NULL pointer or a non-positive size; the step is
+ * read on the device and must index the sigma table (the caller's counter, kept in range by vst_step_advance).
+ * vst_noise_latents: lat[i] = z0[i] + sigmas[*step_idx] * eps[i] over n fp32 elements (the start latents).
+ * vst_euler_cfg_step_masked: vst_euler_cfg_step followed by the blend with the re-noised source, in fp32:
+ *   lat' = lat + (sigmas[s+1] - sigmas[s]) * eps_hat;  lat = m * lat' + (1 - m) * (z0 + sigmas[s+1] * eps)
+ *   with noise rows as vst_euler_cfg_step reads them, lat / z0 / eps fp32 (B, Cl, F, HW), mask fp32
+ *   (mask_clips, F, HW) in [0, 1] broadcast over channels (1 = free, 0 = keep the source), mask_clips 1 or B.
+ *   m == 1 stores exactly vst_euler_cfg_step's bits; m == 0 at sigmas[s+1] == 0 stores z0's.
+ * vst_u8_to_frames: uint8 frames (n, HW, C) -> bf16 rows [n*HW][ldd] = (v / 255 - 0.5) / 0.5 in fp32
+ *   (video_dataset.py:117-118), channels C..ldd-1 zero-filled: the encoder's input, the inverse boundary of
+ *   vst_frames_to_u8. */
+int vst_noise_latents(const float* z0, const float* eps, const float* sigmas, const int* step_idx, float* lat,
+                      size_t n, void* stream);
+int vst_euler_cfg_step_masked(const void* noise, int ncopy, float guidance, float* lat, int B, int Cl, int F, int HW,
+                              const float* sigmas, const int* step_idx, const float* z0, const float* eps,
+                              const float* mask, int mask_clips, void* stream);
+int vst_u8_to_frames(const void* src, int n, int C, int HW, void* dst, int ldd, void* stream);
+
 /* Ceiling probes (no reference counterpart; bench.py's measured peaks next to the vendor figures,
  * SURVEY §8(d)).  vst_probe_mfma: `grid` workgroups x 8 waves, each wave `iters` x 16 independent
  * 16x16x32 bf16 MFMAs (flops = grid*8*iters*16*16384).  vst_probe_hbm_read: streams `bytes` of `src`

@@ -1220,6 +1220,62 @@ def step_advance(step_idx, num_steps):
     _lib.call("vst_step_advance", _p(step_idx), int(num_steps), _stream())
 
 
+# ---- video-to-video: start latents from a source clip, the masked Euler step (pipeline.set_source) ----
+def _flat(t, dtype, shape, name, fn):
+    """Validate a tensor a kernel addresses as one contiguous block: on the device, `dtype`, contiguous, `shape`
+    (None: any)."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _lib.VstError(f"{fn}: {name} must be a device tensor; the HIP path has no CPU fallback")
+    if t.dtype != dtype or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
+        want = "" if shape is None else f" {tuple(shape)}"
+        raise _lib.VstError(f"{fn}: {name} must be contiguous {dtype}{want}, got {t.dtype} {tuple(t.shape)} stride "
+                            f"{t.stride()}")
+    return t
+
+
+def _schedule(sigmas, step_idx, fn):
+    _flat(sigmas, F32, None, "sigmas", fn)
+    _flat(step_idx, torch.int32, (1,), "step_idx", fn)
+    if sigmas.dim() != 1 or sigmas.numel() < 2:
+        raise _lib.VstError(f"{fn}: sigmas must be a 1-D table of num_steps + 1 entries, got {tuple(sigmas.shape)}")
+
+
+def noise_latents(z0, eps, sigmas, step_idx, out=None):
+    """fp32 z0 + sigmas[step_idx] * eps (the start latents of a source-clip run; sigma is read on the device)."""
+    fn = "noise_latents"
+    _flat(z0, F32, None, "z0", fn)
+    _flat(eps, F32, z0.shape, "eps", fn)
+    _schedule(sigmas, step_idx, fn)
+    if z0.numel() == 0:
+        raise _lib.VstError(f"{fn}: empty latents")
+    if out is None:
+        out = torch.empty_like(z0)
+    _flat(out, F32, z0.shape, "out", fn)
+    _lib.call("vst_noise_latents", _p(z0), _p(eps), _p(sigmas), _p(step_idx), _p(out), z0.numel(), _stream())
+    return out
+
+
+def euler_cfg_step_masked(noise, lat, sigmas, step_idx, z0, eps, mask, *, guidance=7.5, ncopy=2):
+    """euler_cfg_step, then lat = mask * lat + (1 - mask) * (z0 + sigmas[step + 1] * eps) in fp32: mask
+    (1 or B, F, H, W) in [0, 1] over the channels of lat / z0 / eps (B, Cl, F, H, W); 1 = free, 0 = keep z0."""
+    fn = "euler_cfg_step_masked"
+    _flat(lat, F32, None, "lat", fn)
+    if lat.dim() != 5 or lat.numel() == 0:
+        raise _lib.VstError(f"{fn}: lat must be (B, Cl, F, H, W), got {tuple(lat.shape)}")
+    B, Cl, F, H, W = lat.shape
+    if ncopy not in (1, 2):
+        raise _lib.VstError(f"{fn}: ncopy {ncopy} (1 or 2)")
+    _flat(noise, BF16, (ncopy * B * F * H * W, Cl), "noise", fn)
+    _flat(z0, F32, lat.shape, "z0", fn)
+    _flat(eps, F32, lat.shape, "eps", fn)
+    _flat(mask, F32, None, "mask", fn)
+    if mask.dim() != 4 or mask.shape[0] not in (1, B) or tuple(mask.shape[1:]) != (F, H, W):
+        raise _lib.VstError(f"{fn}: mask {tuple(mask.shape)} vs (1 or {B}, {F}, {H}, {W})")
+    _schedule(sigmas, step_idx, fn)
+    _lib.call("vst_euler_cfg_step_masked", _p(noise), ncopy, float(guidance), _p(lat), B, Cl, F, H * W, _p(sigmas),
+              _p(step_idx), _p(z0), _p(eps), _p(mask), mask.shape[0], _stream())
+
+
 # ---- ceiling probes (bench.py: measured peaks next to the vendor figures) ----
 def probe_mfma_tflops(device, grid=1024, iters=20000, reps=3):
     """Best-of-`reps` bf16 MFMA rate of vst_probe_mfma (16 independent 16x16x32 chains per wave)."""
@@ -1338,6 +1394,23 @@ def frames_to_u8(x: torch.Tensor, n: int, C: int, H: int, W: int) -> torch.Tenso
         raise _lib.VstError(f"frames_to_u8: x {tuple(x.shape)} (ld {_ld(x)}) vs n*H*W = {n * H * W} rows of >= C channels")
     out = torch.empty((n, H, W, C), dtype=torch.uint8, device=x.device)
     _lib.call("vst_frames_to_u8", _p(x), _ld(x), n, C, H * W, _p(out), _stream())
+    return out
+
+
+def u8_to_frames(x: torch.Tensor, ldd: int | None = None) -> torch.Tensor:
+    """uint8 (n, H, W, C) frames -> bf16 [n*H*W, ldd] rows in [-1, 1] (channels >= C zero): the encoder's input,
+    (v / 255 - 0.5) / 0.5 as video_dataset.py:117-118 normalises, rounded to bf16."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise _lib.VstError("u8_to_frames: x must be a device tensor; the HIP path has no CPU fallback")
+    if x.dtype != torch.uint8 or x.dim() != 4 or not x.is_contiguous() or x.numel() == 0:
+        raise _lib.VstError(f"u8_to_frames: x must be a contiguous uint8 (n, H, W, C) tensor, got {x.dtype} "
+                            f"{tuple(x.shape)} stride {x.stride()}")
+    n, H, W, C = x.shape
+    ldd = C if ldd is None else int(ldd)
+    if ldd < C:
+        raise _lib.VstError(f"u8_to_frames: ldd {ldd} < C {C}")
+    out = torch.empty((n * H * W, ldd), dtype=BF16, device=x.device)
+    _lib.call("vst_u8_to_frames", _p(x), n, C, H * W, _p(out), ldd, _stream())
     return out
 
 

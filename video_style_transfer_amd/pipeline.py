@@ -19,7 +19,7 @@ from typing import Optional
 import torch
 
 from . import kernels as K
-from .scheduler import EulerDiscreteScheduler
+from .scheduler import EulerDiscreteScheduler, start_index
 from .unet_motion import TemporalContext, UNetMotionModel, as_cross_frame, check_clip_length, check_cross_frame
 
 BF16 = torch.bfloat16
@@ -73,6 +73,12 @@ class AnimateDiffDenoiser:
         self.sigmas = self.scheduler.sigmas.to(dev, torch.float32).contiguous()
         self.enc = None
         self.graph = None
+        # video-to-video state (set_source): the first step of the run, and the static device buffers of the source
+        # latents, their noise and the keep mask (allocated on first use, never reallocated: a captured step holds
+        # their pointers)
+        self.t_start = 0
+        self.src = self.eps = self.mask = None
+        self.masked = False
 
     def set_prompt_embeds(self, cond_embeds, cond_pooled, uncond_embeds=None, uncond_pooled=None):
         """(1 or num_clips, L, D) text states and (1 or num_clips, P) pooled embeds per branch
@@ -102,14 +108,20 @@ class AnimateDiffDenoiser:
         emb = self.unet.embed(self.timesteps, self.pooled, self.time_ids, B, step_idx=self.step_idx)
         noise = self.unet.forward_tokens(self.x, B, self.F, self.h, self.w, emb, self.enc, shard=self.shard,
                                          temporal_context=self.context, cross_frame=self.cross_frame)
-        K.euler_cfg_step(noise, self.lat, self.sigmas, self.step_idx, guidance=self.guidance, ncopy=self.ncopy)
+        if self.masked:
+            K.euler_cfg_step_masked(noise, self.lat, self.sigmas, self.step_idx, self.src, self.eps, self.mask,
+                                    guidance=self.guidance, ncopy=self.ncopy)
+        else:
+            K.euler_cfg_step(noise, self.lat, self.sigmas, self.step_idx, guidance=self.guidance, ncopy=self.ncopy)
         K.step_advance(self.step_idx, self.num_steps)
 
     def capture(self):
         """Warm up (fills every derived-weight cache), then capture one step into a HIP graph.  Frame-sharded over
         several ranks: piecewise (frame_shard.PiecewiseGraph), the graphs split at the collectives, which run between
-        them."""
+        them.  The latents and the step counter are put back afterwards, so a run entered part-way (set_source)
+        starts where it was set."""
         saved = self.lat.clone()
+        saved_step = self.step_idx.clone()
         s = torch.cuda.Stream(device=self.device)
         s.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(s):
@@ -125,7 +137,61 @@ class AnimateDiffDenoiser:
                 self._step()
             self.graph = g
         self.lat.copy_(saved)
-        self.step_idx.zero_()
+        self.step_idx.copy_(saved_step)
+
+    def _set_masked(self, on: bool):
+        if on != self.masked:  # another Euler kernel: the captured step no longer fits
+            self.masked = on
+            self.graph = None
+
+    def _local(self, t, axis, name):
+        """Whole-clip or local-frame tensor -> this rank's frames along `axis`."""
+        if t.shape[axis] == self.F_total and self.F != self.F_total:
+            t = t.narrow(axis, self.f0, self.F)
+        if t.shape[axis] != self.F:
+            raise ValueError(f"{name}: {t.shape[axis]} frames, expected {self.F_total} (whole clip) or {self.F}")
+        return t
+
+    def set_source(self, latents, strength: float, mask=None, seed: int = 42):
+        """Start from a source clip instead of noise (SDEdit / img2img; DESIGN.md "Video-to-video").
+        latents: the source z0, (num_clips, C, F_total, h, w) or this rank's (num_clips, C, F_local, h, w), already
+        times scaling_factor (AutoencoderKL.encode_frames).  The run enters the schedule at
+        t_start = scheduler.start_index(num_steps, strength) with lat = z0 + sigmas[t_start] * eps,
+        eps = randn(whole clip, CPU generator(seed)) as init_latents draws it (no init_noise_sigma factor).
+        mask: optional keep mask (1 or num_clips, F_total or F_local, h, w) in [0, 1] over the channels; 1 = free to
+        change, 0 = keep the source: after every Euler update lat = m * lat + (1 - m) * (z0 + sigmas[i + 1] * eps).
+        A new strength, source or mask values reuse a captured step; adding or removing the mask drops it."""
+        t_start = start_index(self.num_steps, strength)
+        C = self.lat.shape[1]
+        z0 = torch.as_tensor(latents)
+        if z0.dim() != 5 or z0.shape[0] != self.nclips or z0.shape[1] != C or tuple(z0.shape[3:]) != (self.h, self.w):
+            raise ValueError(f"source latents {tuple(z0.shape)}, expected ({self.nclips}, {C}, {self.F_total} or "
+                             f"{self.F}, {self.h}, {self.w})")
+        z0 = self._local(z0, 2, "source latents").to(self.device, torch.float32)
+        m = None
+        if mask is not None:
+            m = torch.as_tensor(mask)
+            if m.dim() != 4 or m.shape[0] not in (1, self.nclips) or tuple(m.shape[2:]) != (self.h, self.w):
+                raise ValueError(f"mask {tuple(m.shape)}, expected (1 or {self.nclips}, {self.F_total} or {self.F}, "
+                                 f"{self.h}, {self.w})")
+            m = self._local(m, 1, "mask").to(self.device, torch.float32)
+            if not bool(((m >= 0) & (m <= 1)).all()):
+                raise ValueError("mask values must lie in [0, 1]")
+        g = torch.Generator(device="cpu").manual_seed(seed)
+        eps = torch.randn((self.nclips, C, self.F_total, self.h, self.w), generator=g)
+        eps = eps[:, :, self.f0:self.f0 + self.F]
+        if self.src is None:
+            self.src, self.eps = torch.empty_like(self.lat), torch.empty_like(self.lat)
+        self.src.copy_(z0)
+        self.eps.copy_(eps)
+        if m is not None:
+            if self.mask is None:
+                self.mask = torch.empty(self.nclips, self.F, self.h, self.w, dtype=torch.float32, device=self.device)
+            self.mask.copy_(m.expand_as(self.mask))
+        self._set_masked(m is not None)
+        self.t_start = t_start
+        self.step_idx.fill_(t_start)
+        K.noise_latents(self.src, self.eps, self.sigmas, self.step_idx, out=self.lat)
 
     def set_latents(self, latents):
         """latents: (num_clips, C, F_total, h, w) for whole clips (this rank keeps its frames) or
@@ -135,6 +201,8 @@ class AnimateDiffDenoiser:
             lat = lat[:, :, self.f0:self.f0 + self.F]
         self.lat.copy_(lat.reshape(self.lat.shape))
         self.step_idx.zero_()
+        self.t_start = 0
+        self._set_masked(False)
 
     def init_latents(self, seed: int = 42):
         """randn((1,4,F,h,w), generator=seed) * init_noise_sigma (inference_animatediff.py:88-95); with
@@ -146,7 +214,8 @@ class AnimateDiffDenoiser:
         return lat
 
     def run_steps(self, n: Optional[int] = None):
-        n = self.num_steps if n is None else n
+        """n steps from where the counter stands (default: to the end of the schedule, num_steps - t_start)."""
+        n = self.num_steps - self.t_start if n is None else n
         if self.use_graph and self.graph is None:
             self.capture()
         for _ in range(n):
@@ -156,8 +225,16 @@ class AnimateDiffDenoiser:
                 self._step()
         return self.lat
 
-    def __call__(self, latents=None, seed: int = 42):
-        if latents is None:
+    def __call__(self, latents=None, seed: int = 42, *, source=None, strength: Optional[float] = None, mask=None):
+        """Plain run from `latents` (or from noise drawn with `seed`), or, with `source` and `strength` (and an
+        optional keep `mask`), a video-to-video run (set_source)."""
+        if source is not None:
+            if latents is not None or strength is None:
+                raise ValueError("a source run takes `source` and `strength`, and no `latents`")
+            self.set_source(source, strength, mask, seed)
+        elif strength is not None or mask is not None:
+            raise ValueError("`strength` and `mask` need a `source`")
+        elif latents is None:
             self.init_latents(seed)
         else:
             self.set_latents(latents)

@@ -8,8 +8,26 @@ these tables through a device step counter so a captured HIP graph replays every
 """
 from __future__ import annotations
 
+import math
+
 import numpy as np
 import torch
+
+
+def start_index(num_inference_steps: int, strength: float) -> int:
+    """First step of a run that starts from a source clip (diffusers img2img `get_timesteps`): with
+    k = min(int(N * strength), N) steps to run, t_start = max(N - k, 0).  strength in (0, 1]; one that leaves no step
+    to run is refused."""
+    n = int(num_inference_steps)
+    s = float(strength)
+    if n <= 0:
+        raise ValueError(f"num_inference_steps {num_inference_steps} must be positive")
+    if not (math.isfinite(s) and 0.0 < s <= 1.0):
+        raise ValueError(f"strength {strength} must be in (0, 1]")
+    k = min(int(n * s), n)
+    if k == 0:
+        raise ValueError(f"strength {strength} leaves no step to run at {n} inference steps")
+    return max(n - k, 0)
 
 
 class EulerDiscreteScheduler:

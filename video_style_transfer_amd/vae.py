@@ -5,6 +5,8 @@ Reference calls (diffusers AutoencoderKL, loaded fp32):
   decode: inference_animatediff.py:137-144 -- latents / scaling_factor, one `vae.decode(frame).sample` per frame,
           then (x / 2 + 0.5).clamp(0, 1) * 255 -> uint8;
   encode: train_animatediff.py:219-224 -- `vae.encode(frames).latent_dist.sample() * scaling_factor`.
+`encode_frames` (uint8 frames -> scaled latents, the counterpart of `decode_to_frames`) is the entry of the
+video-to-video path (pipeline.AnimateDiffDenoiser.set_source); the reference has no such call.
 Module tree and parameter names follow diffusers AutoencoderKL (encoder / decoder / quant_conv / post_quant_conv), so
 a real `vae/diffusion_pytorch_model.safetensors` loads with `load_state_dict`.
 
@@ -294,17 +296,39 @@ class AutoencoderKL(nn.Module):
         if not x.is_cuda:
             raise K._lib.VstError("AutoencoderKL.encode: the HIP path has no CPU fallback")
         n, _, H, W = x.shape
+        dist = self._encode_rows(lambda i, c: K.nchw_to_nhwc(x[i:i + c].float().contiguous(), 1.0), n, H, W)
+        return AutoencoderKLOutput(dist) if return_dict else (dist,)
+
+    def _encode_rows(self, rows, n, H, W) -> DiagonalGaussianDistribution:
+        """`rows(i, c)`: the encoder's input for frames [i, i + c), bf16 NHWC rows [c*H*W, in_channels]."""
         wq, bq = _padded_kernel_weight(self.quant_conv, 8)
         moms = []
         step = self._chunk(n, H, W, 1)
         h = w = None
         for i in range(0, n, step):
             c = min(step, n - i)
-            xi = K.nchw_to_nhwc(x[i:i + c].float().contiguous(), 1.0)
-            m, h, w = self.encoder.run(xi, c, H, W)
+            m, h, w = self.encoder.run(rows(i, c), c, H, W)
             moms.append(K.linear(m, wq, bq))
-        dist = DiagonalGaussianDistribution(torch.cat(moms), n, h, w)
-        return AutoencoderKLOutput(dist) if return_dict else (dist,)
+        return DiagonalGaussianDistribution(torch.cat(moms), n, h, w)
+
+    def encode_frames(self, frames_u8: torch.Tensor, generator: torch.Generator | None = None) -> torch.Tensor:
+        """The counterpart of decode_to_frames: uint8 frames (F, H, W, 3) or (clips, F, H, W, 3) on the device ->
+        source latents fp32 (clips, 4, F, h, w), already times scaling_factor (what AnimateDiffDenoiser.set_source
+        takes).  The frames are normalised to [-1, 1] as video_dataset.py:117-118 does, on the way into the encoder's
+        bf16 rows.  Default: the distribution's mode; with a `generator` (on the frames' device) a sample."""
+        if not isinstance(frames_u8, torch.Tensor) or not frames_u8.is_cuda:
+            raise K._lib.VstError("AutoencoderKL.encode_frames: the HIP path has no CPU fallback")
+        if frames_u8.dtype != torch.uint8 or frames_u8.dim() not in (4, 5) or \
+                frames_u8.shape[-1] != self.cfg.in_channels:
+            raise K._lib.VstError(f"AutoencoderKL.encode_frames: frames must be uint8 ([clips,] F, H, W, "
+                                  f"{self.cfg.in_channels}), got {frames_u8.dtype} {tuple(frames_u8.shape)}")
+        x = frames_u8 if frames_u8.dim() == 5 else frames_u8.unsqueeze(0)
+        clips, F, H, W, C = x.shape
+        x = x.reshape(clips * F, H, W, C).contiguous()
+        dist = self._encode_rows(lambda i, c: K.u8_to_frames(x[i:i + c]), clips * F, H, W)
+        sf = self.cfg.scaling_factor
+        z = dist.mode(sf) if generator is None else dist.sample(generator, sf)
+        return z.reshape(clips, F, *z.shape[1:]).permute(0, 2, 1, 3, 4).contiguous()
 
 
 def build_vae(cfg: VAEConfig | None = None, state_dict=None, seed: int = 0, device="cuda") -> AutoencoderKL:
