@@ -74,6 +74,24 @@ int vst_gemm_lora(const void* x, int ldx, const void* Acat, int ld_acat, int P, 
                   const void* W, int ldw, int M, int N, int K, const float* bias, const void* R, int ldr,
                   void* C, int ldc, void* stream);
 int vst_gemm_lora_supported(int M, int N, int K, int P, int group_n, int group_r);
+/* vst_gemm_lora with a per-row gate on the down-projection (per-frame content / style strength):
+ *   C = [x | u'] . W^T (+bias) (+R),  u = bf16(x.Acat^T),  u'[m][c] = bf16(gate[m / gate_div][c] * float(u[m][c])),
+ * gate: fp32 [ceil(M / gate_div)][ld_gate], ld_gate >= P and a multiple of 4, base 16-byte aligned; any finite
+ * value (1 = identity, 0 removes the column's term exactly).  The gate multiplies the already rounded u (fp32
+ * product, round-to-nearest-even), so the result is that of vst_lora_gate on an explicit u followed by the
+ * K-augmented GEMM.  Same kernel, tile choice and refusals as vst_gemm_lora (vst_gemm_lora_supported answers for
+ * both: the gate does not change the path); returns 1 (VST_ERR_ARG) before any launch for a NULL or misaligned
+ * gate, gate_div <= 0, ld_gate < P or ld_gate % 4 != 0. */
+int vst_gemm_lora_gated(const void* x, int ldx, const void* Acat, int ld_acat, int P, int group_n, int group_r,
+                        const void* W, int ldw, int M, int N, int K, const float* bias, const void* R, int ldr,
+                        void* C, int ldc, const float* gate, int ld_gate, int gate_div, void* stream);
+/* The row gate on an explicit down-projection (the paths that keep u as a tensor: vst_layernorm_lora's u, the
+ * separate x.Acat^T pass before the K-augmented vst_gemm_ex):
+ *   y[m][c] = bf16(gate[m / gate_div][c] * float(u[m][c])),  c < P,
+ * u, y: bf16 [M][P] views (row strides ldu, ldy >= P, multiples of 8; P % 8 == 0; y == u allowed); gate as in
+ * vst_gemm_lora_gated.  All three bases 16-byte aligned. */
+int vst_lora_gate(const void* u, int ldu, int M, int P, const float* gate, int ld_gate, int gate_div, void* y,
+                  int ldy, void* stream);
 /* Test / A-B knob: force the 8-phase kernel's tile width (256, 192 or 320 where legal; 0 = automatic policy) for
  * every later GEMM of this process; returns the previous setting.  Not on the product path. */
 int vst_p8_force_bn(int bn);
@@ -114,6 +132,15 @@ int vst_gemm_cross_attention(const void* x, int ldx, const void* Acat, int ld_ac
                              int ldo, void* stream);
 int vst_gemm_cross_attention_supported(int M, int N, int K, int lora, int P, int group_n, int group_r, int Nq,
                                        int Nk);
+/* vst_gemm_cross_attention with the row gate of vst_gemm_lora_gated on the q projection's u (Acat must be
+ * non-NULL: returns 1 otherwise, as for a bad gate).  The text K/V of a gated model differ per frame (to_k / to_v
+ * carry the delta too), so callers pass kv_div = 1 with one K/V block per frame; the kernel does not require it.
+ * _supported answers for both entries. */
+int vst_gemm_cross_attention_gated(const void* x, int ldx, const void* Acat, int ld_acat, int P, int group_n,
+                                   int group_r, const void* W, int ldw, const float* bias, int M, int N, int K,
+                                   const void* Kt, const void* Vt, int ldkv, int nkv_rows, int Nq, int Nk, int kv_div,
+                                   float scale, void* O, int ldo, const float* gate, int ld_gate, int gate_div,
+                                   void* stream);
 
 /* Diagnostics: short name of the kernel (tile shape, epilogue, split-K) that a vst_gemm_ex
  * (kind 0 linear, 1 GEGLU) or vst_conv3x3_ex (kind 2, kind 3 = Cin not a multiple of 64) call with

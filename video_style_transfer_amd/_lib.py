@@ -24,9 +24,13 @@ SIGNATURES = {
     "vst_gemm_workspace_bytes": (_S, [_I, _I, _I]),
     "vst_gemm_lora": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _I, _P, _I, _P]),
     "vst_gemm_lora_supported": (_I, [_I, _I, _I, _I, _I, _I]),
+    "vst_gemm_lora_gated": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _I, _P, _I, _P, _I, _I, _P]),
+    "vst_lora_gate": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _I, _P]),
     "vst_gemm_cross_attention": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I,
                                       _F, _P, _I, _P]),
     "vst_gemm_cross_attention_supported": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I]),
+    "vst_gemm_cross_attention_gated": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _P, _P, _I, _I, _I, _I,
+                                            _I, _F, _P, _I, _P, _I, _I, _P]),
     "vst_gemm_temporal_attention": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _F, _P, _I, _P]),
     "vst_gemm_temporal_attention_supported": (_I, [_I, _I, _I, _I, _I, _I, _I]),
     "vst_gemm_kernel_name": (ctypes.c_char_p, [_I, _I, _I, _I, _I, _I, _S]),

@@ -28,7 +28,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import kernels as K
-from .lora_linear import LoRACompatibleLinear, build_ops, run_ops
+from .lora_linear import LoRACompatibleLinear, build_ops, gate_operands, run_ops
 
 
 class Attention(nn.Module):
@@ -98,6 +98,9 @@ class AnimateDiffAttnProcessor2_0:
         fused_residual = kwargs.pop("_vst_residual", None)
         lora_u = kwargs.pop("_vst_lora_u", None)  # x @ Acat^T of the q(/k/v) ops, from K.layer_norm_lora
         cross_frame = kwargs.pop("_vst_cross_frame", None)  # attn1 only: (CrossFrameAttention, frames per clip)
+        gate = kwargs.pop("_vst_lora_gate", None)  # lora_gate.LoraGate, one row per image of the batch
+        if gate is not None and gate.rows != hidden_states.shape[0]:
+            raise K._lib.VstError(f"LoRA gate: {gate.rows} rows for a batch of {hidden_states.shape[0]} images")
         if attn.spatial_norm is not None or attn.group_norm is not None or attn.norm_cross:
             raise NotImplementedError("spatial_norm/group_norm/norm_cross are inert for SDXL (attention_processor.py:30-60)")
         if attention_mask is not None:
@@ -114,7 +117,7 @@ class AnimateDiffAttnProcessor2_0:
         if encoder_hidden_states is None:
             if cross_frame is not None and hd != 64:
                 raise K._lib.VstError("cross_frame: the cross-frame attention kernel is specialised for head_dim 64")
-            qkv = run_ops(x, build_ops([attn.to_q, attn.to_k, attn.to_v], s), u=lora_u)
+            qkv = run_ops(x, build_ops([attn.to_q, attn.to_k, attn.to_v], s), u=lora_u, gate=gate)
             if cross_frame is not None:
                 # the frame's own tokens plus those of the source frames of the same clip, read in place
                 cf, Fr = cross_frame
@@ -131,20 +134,23 @@ class AnimateDiffAttnProcessor2_0:
             if batch % be:
                 raise ValueError(f"encoder batch {be} does not divide hidden batch {batch}")
             q_ops = build_ops([attn.to_q], s)
-            kv = _text_kv(attn, enc, s)
+            # (with a gate the text K/V carry each frame's own gates: one block per image, kv_div 1)
+            kv = _text_kv(attn, enc, s, gate)
+            kv_div = batch // (kv.shape[0] // L)
             if hd != 64:
                 raise NotImplementedError("spatial cross-attention kernel is specialised for head_dim 64 (SDXL)")
             if lora_u is None and _cross_fusable(q_ops, batch * N, N, L):
                 # q projection (+ in-GEMM UnZipLoRA) and the text cross-attention as one launch: q stays on chip
+                g, gdiv = gate_operands(q_ops, gate, batch * N)
                 o = K.linear_cross_attention(x, q_ops.w, q_ops.a, q_ops.gn, q_ops.gr, q_ops.bias, kv[:, :inner],
-                                             kv[:, inner:], Nq=N, Nk=L, kv_div=batch // be, scale=hd ** -0.5,
-                                             r_alg=q_ops.r)
+                                             kv[:, inner:], Nq=N, Nk=L, kv_div=kv_div, scale=hd ** -0.5,
+                                             r_alg=q_ops.r, gate=g, gate_div=gdiv)
             else:
-                q = run_ops(x, q_ops, u=lora_u)
-                o = K.spatial_attention(q, kv[:, :inner], kv[:, inner:], batch, heads, N, L, batch // be,
+                q = run_ops(x, q_ops, u=lora_u, gate=gate)
+                o = K.spatial_attention(q, kv[:, :inner], kv[:, inner:], batch, heads, N, L, kv_div,
                                         scale=hd ** -0.5)
         res2d = None if fused_residual is None else fused_residual.reshape(batch * N, -1)
-        out = run_ops(o, build_ops([attn.to_out[0]], s), residual=res2d)
+        out = run_ops(o, build_ops([attn.to_out[0]], s), residual=res2d, gate=gate)
         out = out.view(batch, N, -1)
         if input_ndim == 4:
             out = out.transpose(-1, -2).reshape(b4, c4, h4, w4)
@@ -169,7 +175,41 @@ def input_lora_ops(attn, self_attention: bool, scale: float = 1.0):
     return build_ops([attn.to_q, attn.to_k, attn.to_v] if self_attention else [attn.to_q], s)
 
 
-def _text_kv(attn, enc, s):
+def _text_kv_gated(attn, enc, ops, gate):
+    """_text_kv under a LoRA gate: every image's text K/V ([gate.rows * L, 2 inner], gate row per L text rows), from
+    the repeated text rows the gate keeps for all layers.  Cached per (text, operands, gate object); when the gate's
+    values have changed since, the projection is redone into the SAME buffer (a captured step holds it)."""
+    import weakref
+    cache = attn.__dict__.setdefault("_vst_text_kv_gated", [])
+    for c in cache:
+        ref, ver, ops_c, gref, kv = c[:5]
+        if ref() is enc and ver == enc._version and ops_c is ops and gref() is gate:
+            if c[5] != gate.version:
+                run_ops(gate.text_rows(enc), ops, out=kv, gate=gate)
+                c[5] = gate.version
+            return kv
+    kv = run_ops(gate.text_rows(enc), ops, gate=gate)
+    # (entries go when their text or their gate object does: a captured step of a live denoiser reads kv)
+    live = [c for c in cache if c[0]() is not None and c[3]() is not None]
+    cache[:] = live + [[weakref.ref(enc), enc._version, ops, weakref.ref(gate), kv, gate.version]]
+    return kv
+
+
+def refresh_text_kv(model, gate):
+    """Re-project, into their existing buffers, the gated text K/V that the attn2 layers of `model` cached under
+    older values of `gate` (AnimateDiffDenoiser.set_lora_gates: before a captured step is replayed).  Under
+    K.row_invariant, as the forward that first projected them ran: without it these small GEMMs may split K and
+    round differently."""
+    with K.row_invariant():
+        for m in model.modules():
+            for c in m.__dict__.get("_vst_text_kv_gated", ()):
+                enc = c[0]()
+                if enc is not None and c[3]() is gate and c[5] != gate.version and c[1] == enc._version:
+                    run_ops(gate.text_rows(enc), c[2], out=c[4], gate=gate)
+                    c[5] = gate.version
+
+
+def _text_kv(attn, enc, s, gate=None):
     """Cross-attention K/V of the text states (to_k/to_v + LoRA on encoder_hidden_states).
 
     They depend only on the prompt and the weights, not on the latents, so across the 50 denoise
@@ -180,6 +220,8 @@ def _text_kv(attn, enc, s):
     pipeline.py), oldest dropped first."""
     import weakref
     ops = build_ops([attn.to_k, attn.to_v], s)
+    if gate is not None and (ops.gated or ops.folded):  # (folded: run_ops refuses the gate)
+        return _text_kv_gated(attn, enc, ops, gate)
     cache = attn.__dict__.setdefault("_vst_text_kv", [])
     for ref, ver, ops_c, kv in cache:
         if ref() is enc and ver == enc._version and ops_c is ops:

@@ -150,6 +150,25 @@ __global__ __launch_bounds__(256) void add_row_table_kernel(const bf16_t* __rest
   }
 }
 
+// Row gate on an explicit LoRA down-projection u (the paths where u is a tensor: vst_layernorm_lora's, the skinny
+// gemm_lora_down pass): y[m][c] = bf16(gate[m / div][c] * float(u[m][c])), c < P, fp32 product, RNE -- the bits of the
+// gated lora_post of gemm_p8.hip on the same u.  In place (y == u) is allowed: a thread writes only the chunk it read.
+__global__ __launch_bounds__(256) void lora_gate_kernel(const bf16_t* u, int ldu, int P, const float* __restrict__ gate,
+                                                        int ld_gate, int div, bf16_t* y, int ldy, size_t total_chunks) {
+  const int CH = P / 8;
+  for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total_chunks; idx += (size_t)gridDim.x * 256) {
+    const size_t row = idx / CH;
+    const int c = (int)(idx - row * CH) * 8;
+    float f[8];
+    unpack8(*reinterpret_cast<const u32x4*>(u + row * ldu + c), f);
+    const f32x4* g = reinterpret_cast<const f32x4*>(gate + (row / div) * ld_gate + c);
+    const f32x4 g0 = g[0], g1 = g[1];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { f[e] *= g0[e]; f[e + 4] *= g1[e]; }
+    *reinterpret_cast<u32x4*>(y + row * ldy + c) = pack8(f);
+  }
+}
+
 // bf16 token rows ((b*F + f)*HW + p, C) -> fp32 (B, C, F, HW): the inverse of pack_latents (the 5-D
 // output of UNetMotionModel / TemporalTransformer).  64-pixel x 64-channel tiles transposed through
 // LDS so both the 16-B row reads and the fp32 pixel-run writes are coalesced.
@@ -520,6 +539,18 @@ extern "C" int vst_add_row_table(const void* x, int ldx, int C, int rows, const 
   const int grid = (int)std::min<size_t>((total + 255) / 256, 16384);
   hipLaunchKernelGGL(add_row_table_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, ldx, C,
                      table, div, mod, (bf16_t*)y, ldy, total);
+  return launch_status();
+}
+
+extern "C" int vst_lora_gate(const void* u, int ldu, int M, int P, const float* gate, int ld_gate, int gate_div,
+                             void* y, int ldy, void* stream) {
+  if (!u || !y || !gate || M <= 0 || P <= 0 || (P & 7) || (ldu & 7) || (ldy & 7) || ldu < P || ldy < P || gate_div <= 0 ||
+      ld_gate < P || (ld_gate & 3) || (((uintptr_t)u | (uintptr_t)y | (uintptr_t)gate) & 15))
+    return VST_ERR_ARG;
+  const size_t total = (size_t)M * (P / 8);
+  const int grid = (int)std::min<size_t>((total + 255) / 256, 16384);
+  hipLaunchKernelGGL(lora_gate_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)u, ldu, P, gate,
+                     ld_gate, gate_div, (bf16_t*)y, ldy, total);
   return launch_status();
 }
 

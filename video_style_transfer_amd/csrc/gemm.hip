@@ -904,11 +904,18 @@ extern "C" int vst_gemm_lora_supported(int M, int N, int K, int P, int group_n, 
   return lora_ingemm_bn(M, N, K, P, group_n, group_r);
 }
 
-extern "C" int vst_gemm_lora(const void* x, int ldx, const void* Acat, int ld_acat, int P, int group_n, int group_r,
-                             const void* W, int ldw, int M, int N, int K, const float* bias, const void* R, int ldr,
-                             void* C, int ldc, void* stream) {
+// The row gate of the _gated entries (GemmArgs::gate): checked before any launch; the same for both entries
+static bool lora_gate_args_ok(const float* gate, int ld_gate, int gate_div, int P) {
+  return gate && gate_div > 0 && ld_gate >= P && !(ld_gate & 3) && !((uintptr_t)gate & 15);
+}
+
+// vst_gemm_lora (gated = false, gate NULL) and vst_gemm_lora_gated: one implementation, the same tile either way
+static int gemm_lora_impl(const void* x, int ldx, const void* Acat, int ld_acat, int P, int group_n, int group_r,
+                          const void* W, int ldw, int M, int N, int K, const float* bias, const void* R, int ldr,
+                          void* C, int ldc, bool gated, const float* gate, int ld_gate, int gate_div, void* stream) {
   Fit31 fit;
   if (!x || !Acat || !W || !C || M <= 0 || N <= 0 || K <= 0) return VST_ERR_ARG;
+  if (gated && !lora_gate_args_ok(gate, ld_gate, gate_div, P)) return VST_ERR_ARG;
   if ((ldx & 7) || (ld_acat & 7) || (ldw & 7) || (ldc & 7) || ldx < K || ld_acat < K || ldw < K + P) return VST_ERR_ARG;
   if (R && ((ldr & 7) || ldr < N)) return VST_ERR_ARG;
   const int bn = lora_ingemm_bn(M, N, K, P, group_n, group_r);
@@ -923,12 +930,28 @@ extern "C" int vst_gemm_lora(const void* x, int ldx, const void* Acat, int ld_ac
   a.r_bytes = R ? fit(((size_t)(M - 1) * ldr + N) * 2) : 0;
   a.la = (const bf16_t*)Acat; a.lda_la = ld_acat; a.la_p = P; a.la_gn = group_n; a.la_gr = group_r;
   a.la_bytes = fit((size_t)P * ld_acat * 2);
+  if (gated) { a.gate = gate; a.ld_gate = ld_gate; a.gate_div = gate_div; }
   if (fit.over) return VST_ERR_ARG;  // past the 32-bit buffer offsets (not chunked here): refuse
   a.stride = 1; a.splits = 1;
   a.ablate = gemm_knobs().ablate;  // (reaches the kernel in the diagnostics build only, -DVST_P8_TRACE)
   a.group_m = gemm_knobs().group_m;
   const bool persist = bn == 320 && p8_lora_persist_on() && p8_persist_applies(M, N, K, 0, bn, false, (size_t)M * ldc * 2);
   return launch_gemm_p8_lora(a, bn, persist, (hipStream_t)stream);
+}
+
+extern "C" int vst_gemm_lora(const void* x, int ldx, const void* Acat, int ld_acat, int P, int group_n, int group_r,
+                             const void* W, int ldw, int M, int N, int K, const float* bias, const void* R, int ldr,
+                             void* C, int ldc, void* stream) {
+  return gemm_lora_impl(x, ldx, Acat, ld_acat, P, group_n, group_r, W, ldw, M, N, K, bias, R, ldr, C, ldc, false,
+                        nullptr, 0, 1, stream);
+}
+
+extern "C" int vst_gemm_lora_gated(const void* x, int ldx, const void* Acat, int ld_acat, int P, int group_n,
+                                   int group_r, const void* W, int ldw, int M, int N, int K, const float* bias,
+                                   const void* R, int ldr, void* C, int ldc, const float* gate, int ld_gate,
+                                   int gate_div, void* stream) {
+  return gemm_lora_impl(x, ldx, Acat, ld_acat, P, group_n, group_r, W, ldw, M, N, K, bias, R, ldr, C, ldc, true, gate,
+                        ld_gate, gate_div, stream);
 }
 
 // ---- attn2: q projection (+ in-GEMM LoRA) with the cross-attention over the text tokens as its epilogue ----
@@ -946,12 +969,14 @@ extern "C" int vst_gemm_cross_attention_supported(int M, int N, int K, int lora,
   return xattn_ok(M, N, K, lora ? (const void*)1 : nullptr, P, group_n, group_r, Nq, Nk) ? 1 : 0;
 }
 
-extern "C" int vst_gemm_cross_attention(const void* x, int ldx, const void* Acat, int ld_acat, int P, int group_n,
-                                        int group_r, const void* W, int ldw, const float* bias, int M, int N, int K,
-                                        const void* Kt, const void* Vt, int ldkv, int nkv_rows, int Nq, int Nk,
-                                        int kv_div, float scale, void* O, int ldo, void* stream) {
+static int gemm_cross_attention_impl(const void* x, int ldx, const void* Acat, int ld_acat, int P, int group_n,
+                                     int group_r, const void* W, int ldw, const float* bias, int M, int N, int K,
+                                     const void* Kt, const void* Vt, int ldkv, int nkv_rows, int Nq, int Nk,
+                                     int kv_div, float scale, void* O, int ldo, bool gated, const float* gate,
+                                     int ld_gate, int gate_div, void* stream) {
   Fit31 fit;
   if (!x || !W || !Kt || !Vt || !O || M <= 0 || N <= 0 || K <= 0 || kv_div <= 0 || nkv_rows <= 0) return VST_ERR_ARG;
+  if (gated && (!Acat || !lora_gate_args_ok(gate, ld_gate, gate_div, P))) return VST_ERR_ARG;  // (the gate scales u)
   if ((ldx & 7) || (ldw & 7) || (ldo & 7) || (ldkv & 7) || ldx < K || ldo < N || ldkv < N) return VST_ERR_ARG;
   if (Acat && ((ld_acat & 7) || ld_acat < K || ldw < K + P)) return VST_ERR_ARG;
   if (!Acat && ldw < K) return VST_ERR_ARG;
@@ -967,6 +992,7 @@ extern "C" int vst_gemm_cross_attention(const void* x, int ldx, const void* Acat
     a.wtail_bytes = fit(((size_t)(N - 1) * ldw + K + P) * 2);
     a.la = (const bf16_t*)Acat; a.lda_la = ld_acat; a.la_p = P; a.la_gn = group_n; a.la_gr = group_r;
     a.la_bytes = fit((size_t)P * ld_acat * 2);
+    if (gated) { a.gate = gate; a.ld_gate = ld_gate; a.gate_div = gate_div; }
   }
   a.xa_k = (const bf16_t*)Kt; a.xa_v = (const bf16_t*)Vt; a.xa_ldkv = ldkv; a.xa_nk = Nk; a.xa_nq = Nq;
   a.xa_kvdiv = kv_div; a.xa_scale_log2 = scale * 1.4426950408889634f;
@@ -975,6 +1001,23 @@ extern "C" int vst_gemm_cross_attention(const void* x, int ldx, const void* Acat
   a.stride = 1; a.splits = 1;
   a.ablate = gemm_knobs().ablate;  // (diagnostics build only)
   return launch_gemm_p8_xattn(a, (hipStream_t)stream);
+}
+
+extern "C" int vst_gemm_cross_attention(const void* x, int ldx, const void* Acat, int ld_acat, int P, int group_n,
+                                        int group_r, const void* W, int ldw, const float* bias, int M, int N, int K,
+                                        const void* Kt, const void* Vt, int ldkv, int nkv_rows, int Nq, int Nk,
+                                        int kv_div, float scale, void* O, int ldo, void* stream) {
+  return gemm_cross_attention_impl(x, ldx, Acat, ld_acat, P, group_n, group_r, W, ldw, bias, M, N, K, Kt, Vt, ldkv,
+                                   nkv_rows, Nq, Nk, kv_div, scale, O, ldo, false, nullptr, 0, 1, stream);
+}
+
+extern "C" int vst_gemm_cross_attention_gated(const void* x, int ldx, const void* Acat, int ld_acat, int P,
+                                              int group_n, int group_r, const void* W, int ldw, const float* bias,
+                                              int M, int N, int K, const void* Kt, const void* Vt, int ldkv,
+                                              int nkv_rows, int Nq, int Nk, int kv_div, float scale, void* O, int ldo,
+                                              const float* gate, int ld_gate, int gate_div, void* stream) {
+  return gemm_cross_attention_impl(x, ldx, Acat, ld_acat, P, group_n, group_r, W, ldw, bias, M, N, K, Kt, Vt, ldkv,
+                                   nkv_rows, Nq, Nk, kv_div, scale, O, ldo, true, gate, ld_gate, gate_div, stream);
 }
 
 // The motion modules' q/k/v projection + frame-axis attention in one launch (EPI 5 of the 8-phase kernel): 16 frames

@@ -30,6 +30,10 @@ struct GemmArgs {
   const bf16_t* la;
   int lda_la, la_p, la_gn, la_gr;
   uint32_t la_bytes, wtail_bytes;
+  // row gate on u (gemm_p8.hip GATE, vst_gemm_lora_gated): gate [ceil(M / gate_div)][ld_gate] fp32, ld_gate >= la_p and a
+  // multiple of 4, 16-byte aligned; row m's u column c is scaled by gate[m / gate_div][c].  NULL: no gate
+  const float* gate;
+  int ld_gate, gate_div;
   // cross-attention epilogue (gemm_p8.hip EPI 4, vst_gemm_cross_attention): the GEMM output is the q of a
   // BasicTransformerBlock's attn2; instead of storing it, each tile writes softmax(q K^T scale) V of its heads over
   // the xa_nk text keys of text batch (m / xa_nq) / xa_kvdiv (K/V rows [batch * xa_nk + key], row stride xa_ldkv)

@@ -577,13 +577,23 @@ __device__ __forceinline__ void tattn_epilogue(const GemmArgs& p, char* smem, co
 // so a 64-deep k-tile is one tap of one source.  Each A slot's DMAs are issued for consecutive k-tiles, so a (tap,
 // channel) cursor per slot advances by 64 per issue and its pieces' row bases are recomputed only when the tap or the
 // source changes (padding rows read out of range: zeros).  Same k order as the ring kernel's conv: same bits.
-template <int EPI, int BN, bool LORA = false, int BM = 256, bool CONV = false, bool PERSIST = false>
+// GATE (vst_gemm_lora_gated, vst_gemm_cross_attention_gated): u' = bf16(gate[m / gate_div][col] * float(bf16(u))), a
+// per-row, per-u-column fp32 factor on the already-rounded u (so the result is that of vst_lora_gate on an explicit u).
+// Each lane reads the 4 gate values of the two u rows it holds (one 16-B load each) before the tile's k-loop and keeps
+// them in 8 VGPRs until lora_post, so the loads' latency lies under the k-loop and not between the loop and the u . V
+// step of every tile.  They are plain loads, which the compiler counts: before the multiply it places its own
+// s_waitcnt (vmcnt(1) in the persistent grid: the loop may issue nothing on some path, so only the second gate load is
+// known to be younger), which there also covers the next tile's first k-tiles, issued one to two k-tiles earlier.  An
+// extra load in flight only makes the loop's counted waits stricter.  Compiled in with `if constexpr`: the ungated
+// instantiations are the code they were.
+template <int EPI, int BN, bool LORA = false, int BM = 256, bool CONV = false, bool PERSIST = false, bool GATE = false>
 __global__ __launch_bounds__(512, 1) void gemm_p8_kernel(GemmArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   using Cfg = P8Cfg<BN, BM>;
   static_assert(!CONV || (!LORA && EPI == 0), "conv: plain epilogue");
   static_assert(EPI != 1 || BN == 256, "GEGLU needs 64-column [hidden | gate] blocks");
   static_assert(!LORA || EPI != 1, "in-GEMM LoRA: linear epilogue");
+  static_assert(!GATE || LORA, "the gate scales the in-GEMM LoRA's u");
   static_assert(!PERSIST || (!CONV && EPI != 4 && EPI != 5 && (!LORA || (EPI == 0 && BN == 320))),
                 "persistent tiles: plain / GEGLU / GELU, and the in-GEMM LoRA on 128x320 tiles");
   static_assert(!(PERSIST && LORA) || Cfg::U_END <= 160 * 1024, "LoRA persistent LDS");
@@ -798,6 +808,19 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_kernel(GemmArgs p) {
 
   f32x4 acc[Cfg::MI][Cfg::NJ];
   f32x4 acc_u[2];   // LORA: u of row block wc of row quadrants 0 / 1 (this wave's row half)
+  f32x4 ug[2];      // GATE: the gates of this lane's u elements (rows of acc_u[0 / 1], u columns ub0 + 4 fq .. + 3)
+  // GATE: issued once the tile's ub0 is set (setup_tile), before its k-loop; rows past M take the last row's gate row
+  // (their u is zero and never stored), waves wc >= MQR hold an unused u and read nothing
+  auto gate_load = [&](int m0) {
+    if constexpr (GATE) {
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const int m = min(m0 + wr * Cfg::WM + q * HALF + wc * 16 + fr, p.M - 1);
+        ug[q] = f32x4{1.f, 1.f, 1.f, 1.f};
+        if (wc < MQR) ug[q] = *reinterpret_cast<const f32x4*>(p.gate + (size_t)(m / p.gate_div) * p.ld_gate + ub0 + 4 * fq);
+      }
+    }
+  };
   bf16x8 fl[2];     // LORA: Acat fragments of the current k-tile (16 u columns x 2 k-halves)
   // A fragments of the current row quadrant (mq): MQR x 16 rows x 2 k-halves.  LORA: wave column wc reads the
   // quadrant's row blocks rotated by wc (fa[i] = block (i + wc) mod MQR), so fa[0] is block wc, whose 16 u rows this
@@ -983,6 +1006,11 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_kernel(GemmArgs p) {
       u32x2 v;
       v[0] = pack2bf(acc_u[q][0], acc_u[q][1]);
       v[1] = pack2bf(acc_u[q][2], acc_u[q][3]);
+      if constexpr (GATE) {  // u' = bf16(g * float(bf16(u))), the same RNE
+#pragma unroll
+        for (int e = 0; e < 2; ++e)
+          v[e] = pack2bf(ug[q][2 * e] * __uint_as_float(v[e] << 16), ug[q][2 * e + 1] * __uint_as_float(v[e] & 0xffff0000u));
+      }
       if (wc < MQR) *reinterpret_cast<u32x2*>(U + (wr * Cfg::WM + q * HALF + wc * 16 + fr) * 32 + fq * 8) = v;
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1025,6 +1053,7 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_kernel(GemmArgs p) {
       has_next = jn < cnt;
       if (has_next) tile_origin(beg + jn, nm0, nn0);
       bias_n0 = n0;
+      gate_load(m0);  // (ub0 is this tile's here: setup_tile switches it to the next tile's inside the k-loop)
       run_segment(0, nk, first);
 #ifdef VST_ABL_NOEPI  // diagnostics build only: no epilogue (a guarded store of every accumulator's first lane
                       // element keeps all the MFMAs live)
@@ -1066,6 +1095,7 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_kernel(GemmArgs p) {
   }
   tile_origin(xcd_remap(blockIdx.x, ntiles), m0, n0);
   setup_tile(m0, n0);
+  gate_load(m0);
   run_segment(0, nk, true);
   VST_P8_STAMP(2)
   if constexpr (LORA) lora_post(smem);  // (the drained ring)
@@ -1090,18 +1120,18 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_kernel(GemmArgs p) {
 
 // One workgroup per tile: every conv, cross- and temporal-attention launch, and the shapes the persistent grid does not
 // take (p8_persist_applies).
-template <int EPI, int BN, bool LORA, int BM, bool CONV = false>
+template <int EPI, int BN, bool LORA, int BM, bool CONV = false, bool GATE = false>
 static int launch_p8_tile_per_wg(const GemmArgs& a, hipStream_t s) {
   static bool attr = false;
   using Cfg = P8Cfg<BN, BM>;
   constexpr int lds = EPI == 4 ? 160 * 1024 : (LORA ? Cfg::LDS_LORA : Cfg::LDS);
   if (!attr) {
-    (void)hipFuncSetAttribute((const void*)gemm_p8_kernel<EPI, BN, LORA, BM, CONV>,
+    (void)hipFuncSetAttribute((const void*)gemm_p8_kernel<EPI, BN, LORA, BM, CONV, false, GATE>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     attr = true;
   }
   const int nwg = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
-  hipLaunchKernelGGL((gemm_p8_kernel<EPI, BN, LORA, BM, CONV>), dim3(nwg), dim3(512), lds, s, a);
+  hipLaunchKernelGGL((gemm_p8_kernel<EPI, BN, LORA, BM, CONV, false, GATE>), dim3(nwg), dim3(512), lds, s, a);
   return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
 }
 
@@ -1111,36 +1141,41 @@ static int launch_p8_tile_per_wg(const GemmArgs& a, hipStream_t s) {
 // faster per launch on the step's multi-round shapes (K = 320 / 640 most), the denoise step -0.9 ms same-box; the
 // convs stay on one workgroup per tile (their persistent variant spilled SGPRs and ran 2 % slower).  Which launches
 // take it is the plan's decision (gemm.hip p8_persist_applies).
-template <int EPI, int BN, int BM, bool LORA = false>
+template <int EPI, int BN, int BM, bool LORA = false, bool GATE = false>
 static int launch_p8_persist(const GemmArgs& a, hipStream_t s) {
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute((const void*)gemm_p8_kernel<EPI, BN, LORA, BM, false, true>,
+    (void)hipFuncSetAttribute((const void*)gemm_p8_kernel<EPI, BN, LORA, BM, false, true, GATE>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr = true;
   }
   const int ntiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
   const int grid = ntiles < p8_cus() ? (ntiles & ~7) : p8_cus();
   if (grid < 8) return VST_ERR_ARG;
-  hipLaunchKernelGGL((gemm_p8_kernel<EPI, BN, LORA, BM, false, true>), dim3(grid), dim3(512), 160 * 1024, s, a);
+  hipLaunchKernelGGL((gemm_p8_kernel<EPI, BN, LORA, BM, false, true, GATE>), dim3(grid), dim3(512), 160 * 1024, s, a);
   return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
 }
 
 // BN = 320 runs 128-row tiles (P8Cfg).  The persistent grid exists for the plain / GEGLU / GELU epilogues and for the
 // in-GEMM LoRA on 128x320 tiles.
-template <int EPI, int BN, bool LORA = false>
+template <int EPI, int BN, bool LORA = false, bool GATE = false>
 static int launch_p8_epi(const GemmArgs& a, bool persist, hipStream_t s) {
   constexpr int BM = BN == 320 ? 128 : 256;
   if constexpr (!LORA && EPI != 4 && EPI != 5)
     if (persist) return launch_p8_persist<EPI, BN, BM>(a, s);
   if constexpr (LORA && EPI == 0 && BN == 320)
-    if (persist) return launch_p8_persist<EPI, BN, BM, true>(a, s);
-  return persist ? VST_ERR_ARG : launch_p8_tile_per_wg<EPI, BN, LORA, BM>(a, s);
+    if (persist) return launch_p8_persist<EPI, BN, BM, true, GATE>(a, s);
+  return persist ? VST_ERR_ARG : launch_p8_tile_per_wg<EPI, BN, LORA, BM, false, GATE>(a, s);
 }
 
-// in-GEMM LoRA down-projection (a.la set): epilogue 0 (bias / residual), bn 256, 192 or 320
+// in-GEMM LoRA down-projection (a.la set): epilogue 0 (bias / residual), bn 256, 192 or 320; a.gate set: the gated
+// instantiation of the same tile
 int launch_gemm_p8_lora(const GemmArgs& a, int bn, bool persist, hipStream_t s) {
   if (!a.la) return VST_ERR_ARG;
+  if (a.gate) {
+    if (bn == 320) return launch_p8_epi<0, 320, true, true>(a, persist, s);
+    return bn == 192 ? launch_p8_epi<0, 192, true, true>(a, persist, s) : launch_p8_epi<0, 256, true, true>(a, persist, s);
+  }
   if (bn == 320) return launch_p8_epi<0, 320, true>(a, persist, s);
   return bn == 192 ? launch_p8_epi<0, 192, true>(a, persist, s) : launch_p8_epi<0, 256, true>(a, persist, s);
 }
@@ -1153,7 +1188,8 @@ int launch_gemm_p8_tattn(const GemmArgs& a, hipStream_t s) {
 
 // cross-attention epilogue (a.xa_k set), 256x192 tiles, with or without the in-GEMM LoRA
 int launch_gemm_p8_xattn(const GemmArgs& a, hipStream_t s) {
-  if (!a.xa_k || !a.xa_v) return VST_ERR_ARG;
+  if (!a.xa_k || !a.xa_v || (a.gate && !a.la)) return VST_ERR_ARG;
+  if (a.gate) return launch_p8_epi<4, 192, true, true>(a, false, s);
   return a.la ? launch_p8_epi<4, 192, true>(a, false, s) : launch_p8_epi<4, 192, false>(a, false, s);
 }
 

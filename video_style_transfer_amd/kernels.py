@@ -366,11 +366,47 @@ def gemm_lora_tile(M, N, K, P, group_n, group_r):
     return bn
 
 
+def _check_gate(gate, gate_div, M, P, what):
+    """The row gate of the gated entries: fp32 [>= ceil(M / gate_div), >= P] on the device, unit column stride, row
+    stride a multiple of 4, 16-byte aligned."""
+    if not isinstance(gate, torch.Tensor) or gate.dtype != F32 or not gate.is_cuda or gate.dim() != 2:
+        raise _lib.VstError(f"{what}: gate must be a 2-D fp32 device tensor")
+    if int(gate_div) <= 0:
+        raise _lib.VstError(f"{what}: gate_div {gate_div}")
+    ng = (M + int(gate_div) - 1) // int(gate_div)
+    if gate.shape[0] < ng or gate.shape[1] < P:
+        raise _lib.VstError(f"{what}: gate {tuple(gate.shape)} for {ng} gate rows x {P} u columns")
+    if gate.stride(1) != 1 or (gate.shape[0] > 1 and (gate.stride(0) < P or gate.stride(0) & 3)) or gate.data_ptr() & 15:
+        raise _lib.VstError(f"{what}: gate strides {gate.stride()} / alignment")
+
+
+def _gate_ld(gate, P):
+    return gate.stride(0) if gate.shape[0] > 1 else P  # (one gate row: its stride is never used)
+
+
+def lora_gate(u: torch.Tensor, gate: torch.Tensor, gate_div: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """out[m, c] = bf16(gate[m // gate_div, c] * float(u[m, c])) (vst_lora_gate): the per-row content / style gate on
+    an explicit LoRA down-projection u [M, P]; out may be u itself."""
+    _dev(u, BF16, "u")
+    M, P = u.shape
+    _check_gate(gate, gate_div, M, P, "lora_gate")
+    if out is None:
+        out = torch.empty((M, P), dtype=BF16, device=u.device)
+    _out(out, (M, P), BF16, "out", "lora_gate")
+    with _Rec("lora_gate", 1.0 * M * P, 4.0 * M * P, lambda: "lora_gate", (M, P)):
+        _lib.call("vst_lora_gate", _p(u), _ld(u), M, P, _p(gate), _gate_ld(gate, P), int(gate_div), _p(out), _ld(out),
+                  _stream())
+    return out
+
+
 def linear_lora(x: torch.Tensor, w: torch.Tensor, a: torch.Tensor, group_n: int, group_r: int,
                 bias: torch.Tensor | None = None, *, residual: torch.Tensor | None = None,
-                out: torch.Tensor | None = None, r_alg: int | None = None) -> torch.Tensor:
+                out: torch.Tensor | None = None, r_alg: int | None = None, gate: torch.Tensor | None = None,
+                gate_div: int = 1) -> torch.Tensor:
     """out = [x | bf16(x @ a^T)] @ w^T + bias (+ residual), the down-projection computed inside the GEMM
-    (vst_gemm_lora).  w: [N, K + P] = [W | V], a: [P, K]; output columns n use u columns of group n // group_n."""
+    (vst_gemm_lora).  w: [N, K + P] = [W | V], a: [P, K]; output columns n use u columns of group n // group_n.
+    gate (fp32 [ceil(M / gate_div), >= P]): row m's u column c is scaled by gate[m // gate_div, c] after its bf16
+    rounding and rounded again (vst_gemm_lora_gated); the same tile as without."""
     _dev(x, BF16, "x")
     _dev(w, BF16, "w")
     _dev(a, BF16, "a")
@@ -388,6 +424,8 @@ def linear_lora(x: torch.Tensor, w: torch.Tensor, a: torch.Tensor, group_n: int,
         _dev(residual, BF16, "residual")
         if residual.shape != (M, N):
             raise _lib.VstError("linear_lora: residual shape mismatch")
+    if gate is not None:
+        _check_gate(gate, gate_div, M, P, "linear_lora")
     bn = gemm_lora_tile(M, N, K, P, group_n, group_r)
     if not bn:
         raise _lib.VstError(f"linear_lora: shape M={M} N={N} K={K} P={P} groups ({group_n}, {group_r}) unsupported")
@@ -396,9 +434,16 @@ def linear_lora(x: torch.Tensor, w: torch.Tensor, a: torch.Tensor, group_n: int,
     flops = 2.0 * M * N * (K + r) + 2.0 * M * K * r
     nbytes = 2.0 * (M * K + N * (K + r) + r * K + M * N * (2 if residual is not None else 1))
     sym = f"gemm_p8<128x{bn},lora>" if bn == 320 else f"gemm_p8<256x{bn},lora>"
+    if gate is not None:
+        sym = sym[:-1] + ",gate>"
     with _Rec("gemm_lora", flops, nbytes, lambda: sym, (M, N, K + P)):
-        _lib.call("vst_gemm_lora", _p(x), _ld(x), _p(a), _ld(a), P, group_n, group_r, _p(w), _ld(w), M, N, K,
-                  _p(bias), _p(residual), 0 if residual is None else _ld(residual), _p(out), _ld(out), _stream())
+        if gate is None:
+            _lib.call("vst_gemm_lora", _p(x), _ld(x), _p(a), _ld(a), P, group_n, group_r, _p(w), _ld(w), M, N, K,
+                      _p(bias), _p(residual), 0 if residual is None else _ld(residual), _p(out), _ld(out), _stream())
+        else:
+            _lib.call("vst_gemm_lora_gated", _p(x), _ld(x), _p(a), _ld(a), P, group_n, group_r, _p(w), _ld(w), M, N, K,
+                      _p(bias), _p(residual), 0 if residual is None else _ld(residual), _p(out), _ld(out), _p(gate),
+                      _gate_ld(gate, P), int(gate_div), _stream())
     return out
 
 
@@ -419,10 +464,12 @@ def cross_attention_fusable(M, N, K, lora, P, group_n, group_r, Nq, Nk):
 def linear_cross_attention(x: torch.Tensor, w: torch.Tensor, a: torch.Tensor | None, group_n: int, group_r: int,
                            bias: torch.Tensor | None, k: torch.Tensor, v: torch.Tensor, *, Nq: int, Nk: int,
                            kv_div: int, scale: float, out: torch.Tensor | None = None,
-                           r_alg: int | None = None) -> torch.Tensor:
+                           r_alg: int | None = None, gate: torch.Tensor | None = None,
+                           gate_div: int = 1) -> torch.Tensor:
     """o = softmax(q_h k_h^T scale) v_h per head (head_dim 64) with q = [x | bf16(x a^T)] w^T + bias computed in the
     same launch (vst_gemm_cross_attention); k / v: [text_batches * Nk, N] views (row stride >= N), the text batch of
-    frame f = (m // Nq) is f // kv_div."""
+    frame f = (m // Nq) is f // kv_div.  gate / gate_div: the row gate of linear_lora on q's down-projection
+    (vst_gemm_cross_attention_gated; needs a)."""
     _dev(x, BF16, "x")
     _dev(w, BF16, "w")
     _dev(k, BF16, "k")
@@ -442,6 +489,10 @@ def linear_cross_attention(x: torch.Tensor, w: torch.Tensor, a: torch.Tensor | N
         raise _lib.VstError(f"linear_cross_attention: M={M} Nq={Nq} kv_div={kv_div} vs {k.shape[0] // Nk} text rows")
     if bias is not None and (bias.dtype != F32 or bias.numel() != N or not bias.is_cuda):
         raise _lib.VstError("linear_cross_attention: bias must be fp32 [N] on device")
+    if gate is not None:
+        if a is None:
+            raise _lib.VstError("linear_cross_attention: a gate needs the LoRA operand a")
+        _check_gate(gate, gate_div, M, P, "linear_cross_attention")
     if not cross_attention_fusable(M, N, K, a is not None, P, group_n, group_r, Nq, Nk):
         raise _lib.VstError(f"linear_cross_attention: M={M} N={N} K={K} Nq={Nq} Nk={Nk} not fusable")
     if out is None:
@@ -451,10 +502,17 @@ def linear_cross_attention(x: torch.Tensor, w: torch.Tensor, a: torch.Tensor | N
     flops = 2.0 * M * N * (K + r) + 2.0 * M * K * r + 4.0 * M * N * Nk
     nbytes = 2.0 * (M * K + N * (K + r) + r * K + 2 * (k.shape[0]) * N + M * N)
     sym = "gemm_p8<256x192,lora,xattn>" if a is not None else "gemm_p8<256x192,xattn>"
+    if gate is not None:
+        sym = "gemm_p8<256x192,lora,gate,xattn>"
     with _Rec("gemm_xattn", flops, nbytes, lambda: sym, (M, N, K + P)):
-        _lib.call("vst_gemm_cross_attention", _p(x), _ld(x), _p(a), 0 if a is None else _ld(a), P, group_n, group_r,
-                  _p(w), _ld(w), _p(bias), M, N, K, _p(k), _p(v), _ld(k), k.shape[0], Nq, Nk, kv_div, float(scale),
-                  _p(out), _ld(out), _stream())
+        if gate is None:
+            _lib.call("vst_gemm_cross_attention", _p(x), _ld(x), _p(a), 0 if a is None else _ld(a), P, group_n,
+                      group_r, _p(w), _ld(w), _p(bias), M, N, K, _p(k), _p(v), _ld(k), k.shape[0], Nq, Nk, kv_div,
+                      float(scale), _p(out), _ld(out), _stream())
+        else:
+            _lib.call("vst_gemm_cross_attention_gated", _p(x), _ld(x), _p(a), _ld(a), P, group_n, group_r, _p(w),
+                      _ld(w), _p(bias), M, N, K, _p(k), _p(v), _ld(k), k.shape[0], Nq, Nk, kv_div, float(scale),
+                      _p(out), _ld(out), _p(gate), _gate_ld(gate, P), int(gate_div), _stream())
     return out
 
 

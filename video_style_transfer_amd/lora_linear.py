@@ -100,6 +100,12 @@ class ProjOps:
     r: int = 0                       # real (unpadded) low-rank width
     gn: int = 0                      # output columns per projection when every projection has the same width and
     gr: int = 0                      # rank (u columns [g gr, (g+1) gr) feed rows [g gn, (g+1) gn)); 0 = irregular
+    keys: tuple = ()                 # per u column (len P): 0 content, 1 style (UnZipLoRA terms), -1 ungated
+    folded: bool = False             # a low-rank delta was merged into w ("folded" mode): there is no u to gate
+
+    @property
+    def gated(self) -> bool:
+        return any(k >= 0 for k in self.keys)
 
 
 def _linear_parts(lin):
@@ -132,19 +138,28 @@ def build_ops(lins: Sequence[nn.Module], scale: float = 1.0, mode: Optional[str]
     if hit is not None and hit[0] == skey:
         return hit[1]
     with torch.no_grad():
-        Ws, bs, As, Vs = [], [], [], []
+        Ws, bs, As, Vs, keys = [], [], [], [], []
+        folded = False
         for l in lins:
             W, b, lora = _linear_parts(l)
             Wf = W.float()
             A = V = None
+            lkeys = []
             if lora is not None:
                 s = scale if not hasattr(lora, "is_temporal_lora") else 1.0
                 A, V = lora.lowrank_factors(s)
                 if A.shape[0] == 0:
                     A = V = None
+                elif hasattr(lora, "active_terms"):  # UnZipLoRA: [content r | style r] of the active terms
+                    lkeys = [i for key, _ in lora.active_terms() for i in [0 if key == "content" else 1] * lora.rank]
+                else:
+                    lkeys = [-1] * A.shape[0]
             if mode == "folded" and A is not None:
                 Wf = Wf + V @ A
                 A = V = None
+                folded = True
+                lkeys = []
+            keys += lkeys
             Ws.append(Wf)
             bs.append(None if b is None else b.float())
             As.append(A)
@@ -177,7 +192,9 @@ def build_ops(lins: Sequence[nn.Module], scale: float = 1.0, mode: Optional[str]
         if a_bf is not None and len({w.shape[0] for w in Ws}) == 1 and \
                 len({0 if a is None else a.shape[0] for a in As}) == 1:
             gn, gr = Ws[0].shape[0], As[0].shape[0]
-        ops = ProjOps(W_all.to(torch.bfloat16).contiguous(), a_bf, bias, K1, N, R if a_bf is not None else 0, gn, gr)
+        ckeys = tuple(keys) + (-1,) * (a_bf.shape[0] - len(keys)) if a_bf is not None else ()
+        ops = ProjOps(W_all.to(torch.bfloat16).contiguous(), a_bf, bias, K1, N, R if a_bf is not None else 0, gn, gr,
+                      ckeys, folded)
     if cacheable:
         cache[key] = (skey, ops)
     return ops
@@ -190,15 +207,36 @@ def lora_in_gemm(ops: ProjOps, rows: int) -> bool:
         K.gemm_lora_tile(rows, ops.n, ops.k1, ops.a.shape[0], ops.gn, ops.gr) > 0
 
 
-def run_ops(x2d: torch.Tensor, ops: ProjOps, residual=None, out=None, geglu=False, u=None) -> torch.Tensor:
+def gate_operands(ops: ProjOps, gate, rows: int):
+    """(fp32 gate table [gate.rows, P] or None, rows per gate row) of a lora_gate.LoraGate for these operands over
+    `rows` rows.  None when the operands carry no content / style column (plain or temporal LoRA, no LoRA): the
+    projection then runs as without a gate.  A folded weight has no down-projection to gate: refused."""
+    if gate is None:
+        return None, 1
+    if ops.folded:
+        raise K._lib.VstError('a LoRA gate needs the low-rank delta in the GEMM: set_lora_mode("fused"), not "folded"')
+    if not ops.gated:
+        return None, 1
+    if rows % gate.rows:
+        raise K._lib.VstError(f"LoRA gate: {rows} rows over {gate.rows} gate rows")
+    return gate.expanded(ops.keys), rows // gate.rows
+
+
+def run_ops(x2d: torch.Tensor, ops: ProjOps, residual=None, out=None, geglu=False, u=None, gate=None) -> torch.Tensor:
     """`u` = x2d @ ops.a^T when the producer already computed it (K.layer_norm_lora); otherwise the down-projection
-    runs inside the projection GEMM where the shape allows (K.linear_lora), else as its own skinny GEMM."""
+    runs inside the projection GEMM where the shape allows (K.linear_lora), else as its own skinny GEMM.
+    `gate` (lora_gate.LoraGate, its rows dividing x2d's): the content / style columns of u are scaled per row, on
+    whichever of the three paths runs (the same bits: the gate multiplies the rounded u)."""
+    g, gdiv = gate_operands(ops, gate, x2d.shape[0])
     if ops.a is None:
         return K.linear(x2d, ops.w, ops.bias, residual=residual, out=out, geglu=geglu)
     if u is None and not geglu and lora_in_gemm(ops, x2d.shape[0]):
-        return K.linear_lora(x2d, ops.w, ops.a, ops.gn, ops.gr, ops.bias, residual=residual, out=out, r_alg=ops.r)
+        return K.linear_lora(x2d, ops.w, ops.a, ops.gn, ops.gr, ops.bias, residual=residual, out=out, r_alg=ops.r,
+                             gate=g, gate_div=gdiv)
     if u is None:
         u = K.linear(x2d, ops.a, kind="gemm_lora_down", alg_n=ops.r)
+    if g is not None:
+        u = K.lora_gate(u, g, gdiv, out=u)  # (u is this call's own: the producer made it for these operands)
     return K.linear(x2d, ops.w, ops.bias, x2=u, residual=residual, out=out, geglu=geglu, alg_k2=ops.r)
 
 

@@ -19,6 +19,8 @@ from typing import Optional
 import torch
 
 from . import kernels as K
+from .attention_processor import refresh_text_kv
+from .lora_gate import LoraGate
 from .scheduler import EulerDiscreteScheduler, start_index
 from .unet_motion import TemporalContext, UNetMotionModel, as_cross_frame, check_clip_length, check_cross_frame
 
@@ -79,6 +81,8 @@ class AnimateDiffDenoiser:
         self.t_start = 0
         self.src = self.eps = self.mask = None
         self.masked = False
+        # per-frame content / style strength (set_lora_gates): None = the plain step
+        self.lora_gate = None
 
     def set_prompt_embeds(self, cond_embeds, cond_pooled, uncond_embeds=None, uncond_pooled=None):
         """(1 or num_clips, L, D) text states and (1 or num_clips, P) pooled embeds per branch
@@ -107,7 +111,8 @@ class AnimateDiffDenoiser:
         K.pack_latents(self.lat, self.x, sigmas=self.sigmas, step_idx=self.step_idx, ncopy=self.ncopy)
         emb = self.unet.embed(self.timesteps, self.pooled, self.time_ids, B, step_idx=self.step_idx)
         noise = self.unet.forward_tokens(self.x, B, self.F, self.h, self.w, emb, self.enc, shard=self.shard,
-                                         temporal_context=self.context, cross_frame=self.cross_frame)
+                                         temporal_context=self.context, cross_frame=self.cross_frame,
+                                         lora_gate=self.lora_gate)
         if self.masked:
             K.euler_cfg_step_masked(noise, self.lat, self.sigmas, self.step_idx, self.src, self.eps, self.mask,
                                     guidance=self.guidance, ncopy=self.ncopy)
@@ -151,6 +156,45 @@ class AnimateDiffDenoiser:
         if t.shape[axis] != self.F:
             raise ValueError(f"{name}: {t.shape[axis]} frames, expected {self.F_total} (whole clip) or {self.F}")
         return t
+
+    def _gate_rows(self, value, name):
+        """A gate argument -> fp32 CPU [ncopy * num_clips * F_local] in UNet batch order (both CFG copies alike)."""
+        t = torch.as_tensor(value, dtype=torch.float32).detach().cpu()
+        if t.dim() == 0:
+            t = t.expand(self.nclips, self.F)
+        elif t.dim() == 1:
+            t = self._local(t, 0, f"{name} gate").unsqueeze(0).expand(self.nclips, self.F)
+        elif t.dim() == 2 and t.shape[0] == self.nclips:
+            t = self._local(t, 1, f"{name} gate")
+        else:
+            raise ValueError(f"{name} gate: shape {tuple(t.shape)}, expected a scalar, ({self.F_total},), "
+                             f"({self.nclips}, {self.F_total}) or ({self.nclips}, {self.F})")
+        if not bool(torch.isfinite(t).all()):
+            raise ValueError(f"{name} gate: values must be finite")
+        return t.unsqueeze(0).expand(self.ncopy, self.nclips, self.F).reshape(-1)
+
+    def set_lora_gates(self, content=1.0, style=1.0):
+        """Per-frame strength of the content and the style term of the UnZipLoRA delta.  Each is a
+        scalar, (F_total,), (num_clips, F_total) or this rank's (num_clips, F_local); any finite value (1 = as
+        trained, 0 = the term removed, above 1 over-drives, negative subtracts).  Both CFG branches of a clip use the
+        same gates.  Under forward type "both" the gated terms are the merger-weighted ones, so content 1 / style 0
+        is not set_forward("content"), which drops the merger.
+        The first call drops a captured step (the gated step runs other kernels); later calls rewrite the gate
+        tables in place, re-project the text K/V of every attn2 into their buffers, and keep it, so a schedule can
+        be driven from the host: run_steps(k), set_lora_gates(...), run_steps()."""
+        c = self._gate_rows(content, "content")
+        s = self._gate_rows(style, "style")
+        if self.lora_gate is None:
+            self.lora_gate = LoraGate(self.ncopy * self.nclips * self.F, self.device)
+            self.graph = None
+        self.lora_gate.set(c, s)
+        refresh_text_kv(self.unet, self.lora_gate)
+
+    def clear_lora_gates(self):
+        """Back to the plain step (drops a captured gated step)."""
+        if self.lora_gate is not None:
+            self.lora_gate = None
+            self.graph = None
 
     def set_source(self, latents, strength: float, mask=None, seed: int = 42):
         """Start from a source clip instead of noise (SDEdit / img2img; DESIGN.md "Video-to-video").
@@ -225,9 +269,14 @@ class AnimateDiffDenoiser:
                 self._step()
         return self.lat
 
-    def __call__(self, latents=None, seed: int = 42, *, source=None, strength: Optional[float] = None, mask=None):
+    def __call__(self, latents=None, seed: int = 42, *, source=None, strength: Optional[float] = None, mask=None,
+                 content_scale=None, style_scale=None):
         """Plain run from `latents` (or from noise drawn with `seed`), or, with `source` and `strength` (and an
-        optional keep `mask`), a video-to-video run (set_source)."""
+        optional keep `mask`), a video-to-video run (set_source).  `content_scale` / `style_scale`: set_lora_gates
+        for this and later runs (the one not given is 1)."""
+        if content_scale is not None or style_scale is not None:
+            self.set_lora_gates(1.0 if content_scale is None else content_scale,
+                                1.0 if style_scale is None else style_scale)
         if source is not None:
             if latents is not None or strength is None:
                 raise ValueError("a source run takes `source` and `strength`, and no `latents`")

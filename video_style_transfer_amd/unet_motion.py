@@ -214,6 +214,7 @@ class FwdCtx:
     temb: Optional[dict] = None     # ResnetBlock2D -> fp32 [B, Cout] view of the batched time_emb_proj output
     temporal_context: Optional[TemporalContext] = None  # motion attention inside sliding windows when F > length
     cross_frame: Optional[CrossFrameAttention] = None   # spatial attn1 also attends to source frames when F > 1
+    lora_gate: Optional[object] = None  # lora_gate.LoraGate ([B * F] rows): per-frame content / style strength
 
 
 # --------------------------------------------------------------------------------------- blocks
@@ -311,9 +312,11 @@ class BasicTransformerBlock(nn.Module):
             n, u = self.norm1.run_lora(x, input_lora_ops(self.attn1, True, scale))
             cf = ctx.cross_frame
             kw = dict(_vst_cross_frame=(cf, ctx.F)) if cf is not None and cf.active(ctx.F) else {}
-            x = self.attn1(n.view(nimg, N, C), _vst_residual=x, _vst_lora_u=u, **kw, **ctx.cross_kwargs).view(-1, C)
+            gkw = dict(_vst_lora_gate=ctx.lora_gate) if ctx.lora_gate is not None else {}
+            x = self.attn1(n.view(nimg, N, C), _vst_residual=x, _vst_lora_u=u, **kw, **gkw,
+                           **ctx.cross_kwargs).view(-1, C)
             n, u = self.norm2.run_lora(x, input_lora_ops(self.attn2, False, scale))
-            x = self.attn2(n.view(nimg, N, C), encoder_hidden_states=ctx.enc, _vst_residual=x, _vst_lora_u=u,
+            x = self.attn2(n.view(nimg, N, C), encoder_hidden_states=ctx.enc, _vst_residual=x, _vst_lora_u=u, **gkw,
                            **ctx.cross_kwargs).view(-1, C)
         n = self.norm3.run(x)
         return self.ff.run(n, residual=x)
@@ -686,15 +689,19 @@ class UNetMotionModel(nn.Module):
 
     # ---- core (NHWC tokens) -----------------------------------------------------------------
     def forward_tokens(self, x, B, F, h, w, emb_silu, enc, cross_kwargs=None, shard=None, fusion_world=None,
-                       temporal_context=None, cross_frame=None):
+                       temporal_context=None, cross_frame=None, lora_gate=None):
         """x: [B*F*h*w, in_channels] bf16 -> noise prediction [B*F*h*w, out_channels] bf16.
         With `shard` (frame_shard.FrameShard), F is this rank's frames of each clip.  `fusion_world` P (default: the
         shard's world size, else 1): take the shape-dependent fusion decisions a P-way frame-sharded rank takes
         (kernels.fusion_world), so an unsharded forward equals a P-way sharded one bit for bit.  `cross_frame`
         (CrossFrameAttention or its sources): attn1 of the spatial transformer blocks also attends to the source
-        frames of the same clip."""
+        frames of the same clip.  `lora_gate` (lora_gate.LoraGate with B * F rows, one per (batch element, frame) in
+        row order; under a shard this rank's frames): the content / style strength of the UnZipLoRA delta of the
+        spatial transformer blocks' projections, per row.  The motion modules are not gated."""
         cross_frame = as_cross_frame(cross_frame)
         check_cross_frame(self, F * (shard.world if shard is not None else 1), cross_frame, shard)
+        if lora_gate is not None and lora_gate.rows != B * F:
+            raise K._lib.VstError(f"lora_gate: {lora_gate.rows} rows, expected B * F = {B * F}")
         if self.config.motion_modules:
             check_clip_length(F * (shard.world if shard is not None else 1), self.config.motion_max_seq_length,
                               temporal_context)
@@ -704,7 +711,7 @@ class UNetMotionModel(nn.Module):
         K.colstat_reset()
         with K.row_invariant(), K.fusion_world(fusion_world):
             ctx = FwdCtx(B, F, emb_silu, enc, cross_kwargs or {}, shard, self.batched_temb(emb_silu),
-                         temporal_context, cross_frame)
+                         temporal_context, cross_frame, lora_gate)
             nimg = B * F
             H, W = h, w
             x = self.conv_in.run(x, nimg, H, W)
@@ -720,12 +727,13 @@ class UNetMotionModel(nn.Module):
 
     def forward(self, sample, timestep, encoder_hidden_states, timestep_cond=None, attention_mask=None,
                 cross_attention_kwargs=None, added_cond_kwargs=None, return_dict=True, frame_shard=None,
-                fusion_world=None, temporal_context=None, cross_frame=None, **kwargs):
+                fusion_world=None, temporal_context=None, cross_frame=None, lora_gate=None, **kwargs):
         """diffusers UNetMotionModel.forward signature (inference_animatediff.py:110-121).  With
         `frame_shard` (frame_shard.FrameShard) `sample` holds this rank's frames of each clip; `fusion_world`: see
         forward_tokens; `temporal_context` (TemporalContext): the motion modules attend inside sliding windows when the
         clip is longer than its length; `cross_frame` (CrossFrameAttention or its sources, e.g. ("first",)): attn1 of the
-        spatial transformer blocks also attends to the source frames of the same clip."""
+        spatial transformer blocks also attends to the source frames of the same clip; `lora_gate`: see
+        forward_tokens."""
         if not sample.is_cuda:
             raise K._lib.VstError("UNetMotionModel: sample is on CPU; the HIP path has no CPU fallback")
         B, Cin, F, h, w = sample.shape
@@ -749,6 +757,6 @@ class UNetMotionModel(nn.Module):
         K.pack_latents(sample.float().contiguous(), x)
         y = self.forward_tokens(x, B, F, h, w, emb_silu, enc, cross_attention_kwargs, shard=frame_shard,
                                 fusion_world=fusion_world, temporal_context=temporal_context,
-                                cross_frame=cross_frame)
+                                cross_frame=cross_frame, lora_gate=lora_gate)
         out = y.view(B, F, h, w, -1).permute(0, 4, 1, 2, 3).contiguous().to(sample.dtype)
         return UNetMotionOutput(out) if return_dict else (out,)
