@@ -417,6 +417,29 @@ int vst_euler_cfg_step_masked(const void* noise, int ncopy, float guidance, floa
                               const float* mask, int mask_clips, void* stream);
 int vst_u8_to_frames(const void* src, int n, int C, int HW, void* dst, int ldd, void* stream);
 
+/* ---- Few-step sampling: table-driven sampler step and guidance rescale.
+ * vst_sampler_step: one fused launch for every sampler that steps on the denoised estimate D = x - sigma * eps_hat:
+ *   e = u + g (c - u) (ncopy 1: the only row);  e *= factor[b] (factor non-NULL; needs ncopy 2);
+ *   D = lat - sigmas[s] e;  lat' = a lat + b D + c hist;  hist = D;
+ *   lat = m lat' + (1 - m) (z0 + sigmas[s+1] eps)  (mask non-NULL, as vst_euler_cfg_step_masked)
+ *   with (a, b, c) = coef[3 s ..], s = *step_idx read on the device.  coef for "dpmpp_2m" is DPM-Solver++(2M) as
+ *   k-diffusion's sample_dpmpp_2m steps it (scheduler.sampler_coefficients); for "euler" it restates the update of
+ *   vst_euler_cfg_step (EulerDiscreteScheduler.step, inference_animatediff.py:121).  hist (fp32, the shape of lat,
+ *   never lat itself) is not read where c == 0.  z0 / eps / mask are all given or all NULL; mask_clips 1 or B.
+ * vst_cfg_rescale_factor: factor[b] = phi * std(cond_b) / std(e_b) + (1 - phi), e = u + g (c - u), the factor
+ *   rescale_noise_cfg multiplies the guided noise by (animatediff/pipeline_animatediff_xl.py:377-379, :414-425); std
+ *   over all Cl * F * HW values of clip b, unbiased.  Two launches (per-block (count, mean, M2) partials, a
+ *   finalize), Chan merges in an order fixed by the indices, no atomics: the same bits on every call.  factor = 1
+ *   where std(e_b) == 0 (the reference gives NaN).  phi in [0, 1]; workspace of
+ *   vst_cfg_rescale_factor_workspace_bytes(B, Cl, F, HW) bytes, B the number of clips (noise holds 2 B of them).
+ * Every entry returns 1 before any launch on a NULL pointer, a non-positive size or a value outside its range. */
+int vst_sampler_step(const void* noise, int ncopy, float guidance, float* lat, float* hist, int B, int Cl, int F,
+                     int HW, const float* sigmas, const float* coef, const int* step_idx, const float* factor,
+                     const float* z0, const float* eps, const float* mask, int mask_clips, void* stream);
+size_t vst_cfg_rescale_factor_workspace_bytes(int B, int Cl, int F, int HW);
+int vst_cfg_rescale_factor(const void* noise, float guidance, float phi, int B, int Cl, int F, int HW, float* factor,
+                           void* workspace, void* stream);
+
 /* Ceiling probes (no reference counterpart; bench.py's measured peaks next to the vendor figures,
  * SURVEY §8(d)).  vst_probe_mfma: `grid` workgroups x 8 waves, each wave `iters` x 16 independent
  * 16x16x32 bf16 MFMAs (flops = grid*8*iters*16*16384).  vst_probe_hbm_read: streams `bytes` of `src`

@@ -100,6 +100,9 @@ SIGNATURES = {
     "vst_noise_latents": (_I, [_P, _P, _P, _P, _P, _S, _P]),
     "vst_euler_cfg_step_masked": (_I, [_P, _I, _F, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P]),
     "vst_u8_to_frames": (_I, [_P, _I, _I, _I, _P, _I, _P]),
+    "vst_sampler_step": (_I, [_P, _I, _F, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "vst_cfg_rescale_factor_workspace_bytes": (_S, [_I, _I, _I, _I]),
+    "vst_cfg_rescale_factor": (_I, [_P, _F, _F, _I, _I, _I, _I, _P, _P, _P]),
     "vst_probe_mfma": (_I, [_I, _I, _P, _P]),
     "vst_probe_hbm_read": (_I, [_P, _S, _I, _P, _P]),
     "vst_probe_fetch": (_I, [_I, _P, _I, _I, _I, _P, _P]),

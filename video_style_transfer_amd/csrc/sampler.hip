@@ -1,0 +1,259 @@
+// Few-step sampling: the fused sampler step of the denoise loop for table-driven samplers (Euler
+// and DPM-Solver++ 2M on the denoised estimate) and the per-clip factor of guidance rescale.  Every per-step scalar
+// is read through the device step counter, so one captured step replays for the whole schedule.
+#include "vst_common.h"
+
+namespace vst {
+
+__device__ __forceinline__ float cfg_mix(float u, float c, float guidance) { return u + guidance * (c - u); }
+
+// z0 + s1 * eps rounded twice (product, then sum): the value torch computes, so a kept pixel is reproducible bit for
+// bit on the host at every step, not only where s1 == 0.
+__device__ __forceinline__ float renoise(float z0, float s1, float eps) {
+#pragma clang fp contract(off)
+  const float t = s1 * eps;
+  return z0 + t;
+}
+
+// One thread per pixel (b, f, p), laid out as euler_cfg_masked_kernel (source_clip.hip): the pixel's noise row(s) are
+// read once (CL4: one 8-byte load per CFG copy), then the Cl channel planes of lat / hist / z0 / eps are walked, each
+// plane access coalesced in p.  coef rows are (a, b, c):
+//   e = u + g (c - u);  e *= factor[b];  D = lat - sigma[s] e;  lat' = a lat + b D + c hist;  hist = D;
+//   MASKED: lat = m lat' + (1 - m) (z0 + sigma[s+1] eps)
+// hist is not read when c == 0 (the step a run enters at): whatever it holds then never reaches the latents.
+template <bool CL4, bool MASKED>
+__global__ __launch_bounds__(256) void sampler_step_kernel(const bf16_t* __restrict__ noise, int ncopy, float guidance,
+                                                           float* __restrict__ lat, float* __restrict__ hist, int B,
+                                                           int Cl, int F, int HW, const float* __restrict__ sigmas,
+                                                           const float* __restrict__ coef,
+                                                           const int* __restrict__ step,
+                                                           const float* __restrict__ factor,
+                                                           const float* __restrict__ z0,
+                                                           const float* __restrict__ eps,
+                                                           const float* __restrict__ mask, int mask_clips) {
+  const size_t npix = (size_t)B * F * HW;
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= npix) return;
+  const int p = (int)(t % HW);
+  const size_t bf = t / HW;  // b * F + f
+  const int f = (int)(bf % F);
+  const int b = (int)(bf / F);
+  const int s = *step;
+  const float sg = sigmas[s];
+  const float ca = coef[3 * s], cb = coef[3 * s + 1], cc = coef[3 * s + 2];
+  const bool use_hist = cc != 0.0f;
+  const float fac = factor ? factor[b] : 1.0f;
+  float s1 = 0.0f, m = 1.0f, keep = 0.0f;
+  if (MASKED) {
+    s1 = sigmas[s + 1];
+    m = mask[((size_t)(mask_clips == 1 ? 0 : b) * F + f) * HW + p];
+    keep = 1.0f - m;
+  }
+  const size_t plane = (size_t)F * HW;
+  size_t li = ((size_t)b * Cl * F + f) * HW + p;
+  const bf16_t* nu = noise + t * Cl;           // uncond (or the only) row
+  const bf16_t* nc = noise + (npix + t) * Cl;  // cond row (ncopy == 2)
+
+  auto update = [&](float e) {
+    if (factor) e *= fac;
+    const float x = lat[li];
+    const float D = x - sg * e;
+    const float h = use_hist ? hist[li] : 0.0f;
+    float ln = ca * x + cb * D;
+    if (use_hist) ln += cc * h;
+    hist[li] = D;
+    if (MASKED) ln = m * ln + keep * renoise(z0[li], s1, eps[li]);
+    lat[li] = ln;
+  };
+
+  if (CL4) {
+    const u32x2 u2 = *reinterpret_cast<const u32x2*>(nu);
+    float e[4] = {__uint_as_float(u2.x << 16), __uint_as_float(u2.x & 0xffff0000u), __uint_as_float(u2.y << 16),
+                  __uint_as_float(u2.y & 0xffff0000u)};
+    if (ncopy == 2) {
+      const u32x2 c2 = *reinterpret_cast<const u32x2*>(nc);
+      const float c[4] = {__uint_as_float(c2.x << 16), __uint_as_float(c2.x & 0xffff0000u),
+                          __uint_as_float(c2.y << 16), __uint_as_float(c2.y & 0xffff0000u)};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) e[k] = cfg_mix(e[k], c[k], guidance);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k, li += plane) update(e[k]);
+  } else {
+    for (int k = 0; k < Cl; ++k, li += plane) {
+      float e = bf2f(nu[k]);
+      if (ncopy == 2) e = cfg_mix(e, bf2f(nc[k]), guidance);
+      update(e);
+    }
+  }
+}
+
+// ---- guidance rescale: factor[b] = phi * std(cond_b) / std(e_b) + (1 - phi) ----
+// A clip's cond rows and uncond rows are each one contiguous run of n = Cl * F * HW bf16 values, so the statistics are
+// those of two flat arrays.  Partials are (count, mean, M2) merged with Chan's formula (a sum of squares would cancel
+// on a noise tensor with a mean); every merge order is fixed by the indices alone: lanes by a shuffle-down tree,
+// waves in order, blocks strided then by an LDS tree.  No atomics: a replayed graph gives the eager bits.
+struct Moments {
+  float n, mean, m2;
+};
+
+__device__ __forceinline__ Moments chan_merge(Moments a, Moments b) {
+  const float n = a.n + b.n;
+  const float w = n > 0.0f ? b.n / n : 0.0f;  // an empty side has mean 0 and M2 0 and leaves the other unchanged
+  const float d = b.mean - a.mean;
+  return {n, a.mean + d * w, a.m2 + b.m2 + d * d * a.n * w};
+}
+
+__device__ __forceinline__ Moments wave_merge(Moments v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const Moments other = {__shfl_down(v.n, o), __shfl_down(v.mean, o), __shfl_down(v.m2, o)};
+    v = chan_merge(v, other);  // lane 0 ends with the tree over all 64 lanes; the other lanes' values are unused
+  }
+  return v;
+}
+
+constexpr int kRescalePer = 4;                       // values per thread
+constexpr int kRescaleChunk = 256 * kRescalePer;     // values per block
+
+__device__ __forceinline__ Moments moments_of(const float* x, int cnt) {
+  float sum = 0.0f;
+#pragma unroll
+  for (int k = 0; k < kRescalePer; ++k) sum += k < cnt ? x[k] : 0.0f;
+  const float mean = cnt > 0 ? sum / (float)cnt : 0.0f;
+  float m2 = 0.0f;
+#pragma unroll
+  for (int k = 0; k < kRescalePer; ++k) {
+    const float d = x[k] - mean;
+    m2 += k < cnt ? d * d : 0.0f;
+  }
+  return {(float)cnt, mean, m2};
+}
+
+// grid (nblk, B): block (j, b) reduces values [j * chunk, min(n, (j + 1) * chunk)) of clip b into
+// ws[(b * nblk + j) * 6 ..] = cond (count, mean, M2), e (count, mean, M2).  Thread t holds values base + k * 256 + t.
+__global__ __launch_bounds__(256) void rescale_partials_kernel(const bf16_t* __restrict__ noise, float guidance, int B,
+                                                               size_t n, float* __restrict__ ws) {
+  __shared__ Moments part[2][4];
+  const int b = blockIdx.y;
+  const size_t base = (size_t)blockIdx.x * kRescaleChunk;
+  const bf16_t* u = noise + (size_t)b * n;
+  const bf16_t* c = noise + ((size_t)B + b) * n;
+  float xc[kRescalePer], xe[kRescalePer];
+  int cnt = 0;
+#pragma unroll
+  for (int k = 0; k < kRescalePer; ++k) {
+    const size_t i = base + (size_t)k * 256 + threadIdx.x;
+    xc[k] = xe[k] = 0.0f;
+    if (i < n) {  // i grows with k: the values in range are the first cnt
+      const float cv = bf2f(c[i]);
+      xc[k] = cv;
+      xe[k] = cfg_mix(bf2f(u[i]), cv, guidance);
+      ++cnt;
+    }
+  }
+  const Moments mc = wave_merge(moments_of(xc, cnt));
+  const Moments me = wave_merge(moments_of(xe, cnt));
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+    part[0][wave] = mc;
+    part[1][wave] = me;
+  }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    Moments acc = part[threadIdx.x][0];
+    for (int w = 1; w < 4; ++w) acc = chan_merge(acc, part[threadIdx.x][w]);
+    float* o = ws + ((size_t)b * gridDim.x + blockIdx.x) * 6 + threadIdx.x * 3;
+    o[0] = acc.n;
+    o[1] = acc.mean;
+    o[2] = acc.m2;
+  }
+}
+
+struct Moments64 {
+  double n, mean, m2;
+};
+
+__device__ __forceinline__ Moments64 chan_merge64(Moments64 a, Moments64 b) {
+  const double n = a.n + b.n;
+  const double w = n > 0.0 ? b.n / n : 0.0;
+  const double d = b.mean - a.mean;
+  return {n, a.mean + d * w, a.m2 + b.m2 + d * d * a.n * w};
+}
+
+// grid B: thread t merges the block partials t, t + 256, ... of its clip in that order, then an LDS tree over the 256
+// threads; in fp64, so a clip of any length keeps exact counts.  factor = 1 where std(e) == 0.
+__global__ __launch_bounds__(256) void rescale_finalize_kernel(const float* __restrict__ ws, int nblk, float phi,
+                                                               float* __restrict__ factor) {
+  __shared__ Moments64 red[2][256];
+  const int b = blockIdx.x, t = threadIdx.x;
+  Moments64 acc[2] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+  for (int j = t; j < nblk; j += 256) {
+    const float* o = ws + ((size_t)b * nblk + j) * 6;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) acc[q] = chan_merge64(acc[q], {(double)o[3 * q], (double)o[3 * q + 1], (double)o[3 * q + 2]});
+  }
+  red[0][t] = acc[0];
+  red[1][t] = acc[1];
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (t < o) {
+      red[0][t] = chan_merge64(red[0][t], red[0][t + o]);
+      red[1][t] = chan_merge64(red[1][t], red[1][t + o]);
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
+    const double m2c = red[0][0].m2, m2e = red[1][0].m2;  // the n - 1 of the two unbiased estimators cancels
+    factor[b] = m2e > 0.0 ? (float)((double)phi * sqrt(m2c / m2e) + (1.0 - (double)phi)) : 1.0f;
+  }
+}
+
+}  // namespace vst
+
+using namespace vst;
+
+static inline int rescale_blocks(size_t n) { return (int)((n + kRescaleChunk - 1) / kRescaleChunk); }
+
+extern "C" int vst_sampler_step(const void* noise, int ncopy, float guidance, float* lat, float* hist, int B, int Cl,
+                                int F, int HW, const float* sigmas, const float* coef, const int* step_idx,
+                                const float* factor, const float* z0, const float* eps, const float* mask,
+                                int mask_clips, void* stream) {
+  if (!noise || !lat || !hist || !sigmas || !coef || !step_idx || lat == hist) return VST_ERR_ARG;
+  if ((ncopy != 1 && ncopy != 2) || B <= 0 || Cl <= 0 || F <= 0 || HW <= 0) return VST_ERR_ARG;
+  const bool masked = mask != nullptr;
+  if (masked ? (!z0 || !eps || (mask_clips != 1 && mask_clips != B)) : (z0 || eps)) return VST_ERR_ARG;
+  if (factor && ncopy != 2) return VST_ERR_ARG;  // the rescale factor is defined on the CFG pair
+  const size_t npix = (size_t)B * F * HW;
+  const dim3 grid((unsigned)((npix + 255) / 256));
+  const hipStream_t s = (hipStream_t)stream;
+  const bf16_t* nz = (const bf16_t*)noise;
+  const bool cl4 = Cl == 4 && ((uintptr_t)noise & 7) == 0;
+#define VST_SAMPLER_LAUNCH(C4, M)                                                                                    \
+  hipLaunchKernelGGL((sampler_step_kernel<C4, M>), grid, dim3(256), 0, s, nz, ncopy, guidance, lat, hist, B, Cl, F, \
+                     HW, sigmas, coef, step_idx, factor, z0, eps, mask, mask_clips)
+  if (cl4 && masked) VST_SAMPLER_LAUNCH(true, true);
+  else if (cl4) VST_SAMPLER_LAUNCH(true, false);
+  else if (masked) VST_SAMPLER_LAUNCH(false, true);
+  else VST_SAMPLER_LAUNCH(false, false);
+#undef VST_SAMPLER_LAUNCH
+  return launch_status();
+}
+
+extern "C" size_t vst_cfg_rescale_factor_workspace_bytes(int B, int Cl, int F, int HW) {
+  if (B <= 0 || Cl <= 0 || F <= 0 || HW <= 0) return 0;
+  return (size_t)B * rescale_blocks((size_t)Cl * F * HW) * 6 * sizeof(float);
+}
+
+extern "C" int vst_cfg_rescale_factor(const void* noise, float guidance, float phi, int B, int Cl, int F, int HW,
+                                      float* factor, void* workspace, void* stream) {
+  if (!noise || !factor || !workspace) return VST_ERR_ARG;
+  if (B <= 0 || B > 65535 || Cl <= 0 || F <= 0 || HW <= 0 || !(phi >= 0.0f && phi <= 1.0f)) return VST_ERR_ARG;
+  const size_t n = (size_t)Cl * F * HW;
+  const int nblk = rescale_blocks(n);
+  const hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(rescale_partials_kernel, dim3(nblk, B), dim3(256), 0, s, (const bf16_t*)noise, guidance, B, n,
+                     (float*)workspace);
+  hipLaunchKernelGGL(rescale_finalize_kernel, dim3(B), dim3(256), 0, s, (const float*)workspace, nblk, phi, factor);
+  return launch_status();
+}

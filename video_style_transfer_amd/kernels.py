@@ -1334,6 +1334,77 @@ def euler_cfg_step_masked(noise, lat, sigmas, step_idx, z0, eps, mask, *, guidan
               _p(step_idx), _p(z0), _p(eps), _p(mask), mask.shape[0], _stream())
 
 
+# ---- few-step sampling: the table-driven sampler step and guidance rescale (pipeline._step) ----
+def sampler_step(noise, lat, hist, sigmas, coef, step_idx, *, guidance=7.5, ncopy=2, factor=None, z0=None, eps=None,
+                 mask=None):
+    """One fused sampler step on lat and hist (B, Cl, F, H, W) fp32, in place: e = u + guidance * (c - u) (times
+    factor[b] when given), D = lat - sigmas[s] * e, lat = a * lat + b * D + c * hist with (a, b, c) = coef[s]
+    (scheduler.sampler_coefficients as fp32 [n, 3]), hist = D; with z0 / eps / mask (all three) the keep-mask blend of
+    euler_cfg_step_masked follows.  hist is not read where c == 0."""
+    fn = "sampler_step"
+    _flat(lat, F32, None, "lat", fn)
+    if lat.dim() != 5 or lat.numel() == 0:
+        raise _lib.VstError(f"{fn}: lat must be (B, Cl, F, H, W), got {tuple(lat.shape)}")
+    B, Cl, F, H, W = lat.shape
+    if ncopy not in (1, 2):
+        raise _lib.VstError(f"{fn}: ncopy {ncopy} (1 or 2)")
+    _flat(noise, BF16, (ncopy * B * F * H * W, Cl), "noise", fn)
+    _flat(hist, F32, lat.shape, "hist", fn)
+    if hist.data_ptr() == lat.data_ptr():
+        raise _lib.VstError(f"{fn}: hist must not be lat")
+    _schedule(sigmas, step_idx, fn)
+    _flat(coef, F32, (sigmas.numel() - 1, 3), "coef", fn)
+    if factor is not None:
+        _flat(factor, F32, (B,), "factor", fn)
+        if ncopy != 2:
+            raise _lib.VstError(f"{fn}: a rescale factor needs both CFG branches (ncopy 2)")
+    given = [t is not None for t in (z0, eps, mask)]
+    if any(given) and not all(given):
+        raise _lib.VstError(f"{fn}: z0, eps and mask go together")
+    mask_clips = 0
+    if mask is not None:
+        _flat(z0, F32, lat.shape, "z0", fn)
+        _flat(eps, F32, lat.shape, "eps", fn)
+        _flat(mask, F32, None, "mask", fn)
+        if mask.dim() != 4 or mask.shape[0] not in (1, B) or tuple(mask.shape[1:]) != (F, H, W):
+            raise _lib.VstError(f"{fn}: mask {tuple(mask.shape)} vs (1 or {B}, {F}, {H}, {W})")
+        mask_clips = mask.shape[0]
+    _lib.call("vst_sampler_step", _p(noise), ncopy, float(guidance), _p(lat), _p(hist), B, Cl, F, H * W, _p(sigmas),
+              _p(coef), _p(step_idx), _p(factor), _p(z0), _p(eps), _p(mask), mask_clips, _stream())
+
+
+def cfg_rescale_workspace(lat_shape, device):
+    """The fp32 workspace cfg_rescale_factor needs for latents of this (B, Cl, F, H, W) shape."""
+    B, Cl, F, H, W = lat_shape
+    nbytes = int(_lib.load().vst_cfg_rescale_factor_workspace_bytes(B, Cl, F, H * W))
+    return torch.empty((nbytes + 3) // 4, dtype=F32, device=device)
+
+
+def cfg_rescale_factor(noise, lat_shape, *, guidance, phi, out=None, workspace=None):
+    """fp32 [B]: phi * std(cond_b) / std(e_b) + (1 - phi) per clip, e = u + guidance * (c - u), from the CFG pair's
+    UNet output rows noise (2 * B * F * H * W, Cl) bf16 (1 where std(e_b) is 0).  The same bits on every call."""
+    fn = "cfg_rescale_factor"
+    if len(lat_shape) != 5 or min(lat_shape) <= 0:
+        raise _lib.VstError(f"{fn}: latent shape {tuple(lat_shape)} must be (B, Cl, F, H, W), all positive")
+    B, Cl, F, H, W = lat_shape
+    _flat(noise, BF16, (2 * B * F * H * W, Cl), "noise", fn)
+    phi = float(phi)
+    if not 0.0 <= phi <= 1.0:  # also refuses NaN
+        raise _lib.VstError(f"{fn}: phi {phi} outside [0, 1]")
+    if out is None:
+        out = torch.empty(B, dtype=F32, device=noise.device)
+    _flat(out, F32, (B,), "out", fn)
+    if workspace is None:
+        workspace = cfg_rescale_workspace(lat_shape, noise.device)
+    _flat(workspace, F32, None, "workspace", fn)
+    need = int(_lib.load().vst_cfg_rescale_factor_workspace_bytes(B, Cl, F, H * W))
+    if workspace.numel() * 4 < need:
+        raise _lib.VstError(f"{fn}: workspace of {workspace.numel() * 4} bytes, {need} needed")
+    _lib.call("vst_cfg_rescale_factor", _p(noise), float(guidance), phi, B, Cl, F, H * W, _p(out), _p(workspace),
+              _stream())
+    return out
+
+
 # ---- ceiling probes (bench.py: measured peaks next to the vendor figures) ----
 def probe_mfma_tflops(device, grid=1024, iters=20000, reps=3):
     """Best-of-`reps` bf16 MFMA rate of vst_probe_mfma (16 independent 16x16x32 chains per wave)."""

@@ -11,20 +11,45 @@ Euler step (two B=1 UNet calls, :109-121).  Here one step is:
 Because every per-step scalar lives in device tables indexed by the device counter, the whole step
 is captured once into a HIP graph and replayed for all 50 steps (no per-launch host overhead).
 Latents stay fp32 on the device (the reference keeps them in the UNet dtype between steps).
+With sampler="dpmpp_2m" or guidance_rescale > 0 the update is vst_sampler_step instead, after
+vst_cfg_rescale_factor when rescaling: its coefficients, its history and the rescale factor live on the device too.
 """
 from __future__ import annotations
 
 from typing import Optional
+
+import math
 
 import torch
 
 from . import kernels as K
 from .attention_processor import refresh_text_kv
 from .lora_gate import LoraGate
-from .scheduler import EulerDiscreteScheduler, start_index
+from .scheduler import SAMPLERS, EulerDiscreteScheduler, sampler_coefficients, start_index
 from .unet_motion import TemporalContext, UNetMotionModel, as_cross_frame, check_clip_length, check_cross_frame
 
 BF16 = torch.bfloat16
+
+
+def check_sampler(sampler, guidance_scale, guidance_rescale, shard=None) -> float:
+    """The sampler arguments of AnimateDiffDenoiser, refused here before anything is allocated.  Returns
+    guidance_rescale as a float."""
+    if sampler not in SAMPLERS:
+        raise ValueError(f"sampler {sampler!r}: one of {SAMPLERS}")
+    try:
+        phi = float(guidance_rescale)
+    except (TypeError, ValueError):
+        raise ValueError(f"guidance_rescale {guidance_rescale!r} is not a number") from None
+    if not (math.isfinite(phi) and 0.0 <= phi <= 1.0):
+        raise ValueError(f"guidance_rescale {guidance_rescale} must be a finite value in [0, 1]")
+    if phi > 0.0:
+        if not guidance_scale > 1.0:
+            raise ValueError(f"guidance_rescale {phi} rescales the guided noise against the cond branch: it needs "
+                             f"classifier-free guidance (guidance_scale > 1, got {guidance_scale})")
+        if shard is not None and shard.world > 1:
+            raise ValueError("guidance_rescale takes the std over whole clips; under a frame shard of world "
+                             f"{shard.world} the other ranks hold part of every clip")
+    return phi
 
 
 class AnimateDiffDenoiser:
@@ -32,7 +57,8 @@ class AnimateDiffDenoiser:
                  num_inference_steps: int = 50, guidance_scale: float = 7.5, device=None,
                  scheduler: Optional[EulerDiscreteScheduler] = None, use_graph: bool = True, shard=None,
                  num_clips: int = 1, context_length: Optional[int] = None, context_stride: int = 4,
-                 context_weighting: str = "pyramid", cross_frame=None):
+                 context_weighting: str = "pyramid", cross_frame=None, sampler: str = "euler",
+                 guidance_rescale: float = 0.0):
         """`num_clips` clips are denoised together (the reference loop is one clip, B=1).
         `shard` (frame_shard.FrameShard): this process denoises frames [f0, f0 + F/P) of every clip and
         exchanges with the other ranks inside every motion module.
@@ -43,7 +69,13 @@ class AnimateDiffDenoiser:
         clips"); without it a clip longer than the motion modules' positional table is refused here.
         `cross_frame` (e.g. ("first",) or ("first", "prev"); unet_motion.CrossFrameAttention, DESIGN.md "Cross-frame
         spatial self-attention"): every frame's spatial self-attention also attends to those frames of its clip.  It
-        is static, so a captured step replays it unchanged."""
+        is static, so a captured step replays it unchanged.
+        `sampler` "euler" or "dpmpp_2m" (second-order multistep, DPM-Solver++ 2M; meant for 20-25 steps on
+        EulerDiscreteScheduler(sigma_schedule="karras")) and `guidance_rescale` in [0, 1] (rescale_noise_cfg of the
+        reference's pipeline; needs CFG and whole clips on this rank) are fixed at construction.
+        With "euler" and 0 the step is the one it always was."""
+        self.guidance_rescale = check_sampler(sampler, guidance_scale, guidance_rescale, shard)
+        self.sampler = sampler
         self.context = None if context_length is None else TemporalContext(int(context_length), int(context_stride),
                                                                            context_weighting)
         if unet.config.motion_modules:
@@ -79,10 +111,22 @@ class AnimateDiffDenoiser:
         # latents, their noise and the keep mask (allocated on first use, never reallocated: a captured step holds
         # their pointers)
         self.t_start = 0
+        self.steps_run = 0  # steps since the run was entered (host side; run_steps' default finishes the schedule)
         self.src = self.eps = self.mask = None
         self.masked = False
         # per-frame content / style strength (set_lora_gates): None = the plain step
         self.lora_gate = None
+        # table-driven sampler step: the previous step's denoised estimate, the (a, b, c) rows, the
+        # per-clip rescale factor and its workspace; allocated here once, a captured step holds their pointers
+        self.table_step = sampler != "euler" or self.guidance_rescale > 0.0
+        self.hist = self.coef = self.factor = self.rescale_ws = None
+        if self.table_step:
+            self.hist = torch.zeros_like(self.lat)
+            self.coef = torch.empty(num_inference_steps, 3, dtype=torch.float32, device=dev)
+            self._write_coef(0)
+            if self.guidance_rescale > 0.0:
+                self.factor = torch.ones(num_clips, dtype=torch.float32, device=dev)
+                self.rescale_ws = K.cfg_rescale_workspace(self.lat.shape, dev)
 
     def set_prompt_embeds(self, cond_embeds, cond_pooled, uncond_embeds=None, uncond_pooled=None):
         """(1 or num_clips, L, D) text states and (1 or num_clips, P) pooled embeds per branch
@@ -113,7 +157,14 @@ class AnimateDiffDenoiser:
         noise = self.unet.forward_tokens(self.x, B, self.F, self.h, self.w, emb, self.enc, shard=self.shard,
                                          temporal_context=self.context, cross_frame=self.cross_frame,
                                          lora_gate=self.lora_gate)
-        if self.masked:
+        if self.table_step:
+            if self.factor is not None:
+                K.cfg_rescale_factor(noise, self.lat.shape, guidance=self.guidance, phi=self.guidance_rescale,
+                                     out=self.factor, workspace=self.rescale_ws)
+            src, eps, mask = (self.src, self.eps, self.mask) if self.masked else (None, None, None)
+            K.sampler_step(noise, self.lat, self.hist, self.sigmas, self.coef, self.step_idx, guidance=self.guidance,
+                           ncopy=self.ncopy, factor=self.factor, z0=src, eps=eps, mask=mask)
+        elif self.masked:
             K.euler_cfg_step_masked(noise, self.lat, self.sigmas, self.step_idx, self.src, self.eps, self.mask,
                                     guidance=self.guidance, ncopy=self.ncopy)
         else:
@@ -124,8 +175,10 @@ class AnimateDiffDenoiser:
         """Warm up (fills every derived-weight cache), then capture one step into a HIP graph.  Frame-sharded over
         several ranks: piecewise (frame_shard.PiecewiseGraph), the graphs split at the collectives, which run between
         them.  The latents and the step counter are put back afterwards, so a run entered part-way (set_source)
-        starts where it was set."""
+        starts where it was set; so is the sampler's history, which the warm-up step overwrites (a run interrupted
+        by run_steps(k) and recaptured goes on from the history it had)."""
         saved = self.lat.clone()
+        saved_hist = None if self.hist is None else self.hist.clone()
         saved_step = self.step_idx.clone()
         s = torch.cuda.Stream(device=self.device)
         s.wait_stream(torch.cuda.current_stream(self.device))
@@ -142,7 +195,14 @@ class AnimateDiffDenoiser:
                 self._step()
             self.graph = g
         self.lat.copy_(saved)
+        if saved_hist is not None:
+            self.hist.copy_(saved_hist)
         self.step_idx.copy_(saved_step)
+
+    def _write_coef(self, first_step: int):
+        """Rewrite the coefficient table in place for a run entered at `first_step` (first order there: no history)."""
+        if self.coef is not None:
+            self.coef.copy_(sampler_coefficients(self.scheduler.sigmas, self.sampler, first_step).to(torch.float32))
 
     def _set_masked(self, on: bool):
         if on != self.masked:  # another Euler kernel: the captured step no longer fits
@@ -234,7 +294,9 @@ class AnimateDiffDenoiser:
             self.mask.copy_(m.expand_as(self.mask))
         self._set_masked(m is not None)
         self.t_start = t_start
+        self.steps_run = 0
         self.step_idx.fill_(t_start)
+        self._write_coef(t_start)
         K.noise_latents(self.src, self.eps, self.sigmas, self.step_idx, out=self.lat)
 
     def set_latents(self, latents):
@@ -246,6 +308,8 @@ class AnimateDiffDenoiser:
         self.lat.copy_(lat.reshape(self.lat.shape))
         self.step_idx.zero_()
         self.t_start = 0
+        self.steps_run = 0
+        self._write_coef(0)
         self._set_masked(False)
 
     def init_latents(self, seed: int = 42):
@@ -258,8 +322,12 @@ class AnimateDiffDenoiser:
         return lat
 
     def run_steps(self, n: Optional[int] = None):
-        """n steps from where the counter stands (default: to the end of the schedule, num_steps - t_start)."""
-        n = self.num_steps - self.t_start if n is None else n
+        """n steps from where the counter stands.  Default: to the end of the schedule, which is num_steps - t_start
+        steps after set_latents / init_latents / set_source and what is left of them after run_steps(k) (so
+        run_steps(k), set_lora_gates(...), run_steps() is one whole run)."""
+        total = self.num_steps - self.t_start
+        n = total - self.steps_run % total if n is None else n
+        self.steps_run += n
         if self.use_graph and self.graph is None:
             self.capture()
         for _ in range(n):

@@ -5,6 +5,8 @@ timestep spacing, steps_offset 1, epsilon prediction, linear sigma interpolation
 Host-side math only (once per schedule); the per-step arithmetic (scale_model_input, CFG
 combine, Euler update) runs in vst_pack_latents / vst_euler_cfg_step on the device, reading
 these tables through a device step counter so a captured HIP graph replays every step.
+Few-step sampling adds, opt-in, the Karras sigma table, the per-step coefficient table of the
+table-driven samplers (vst_sampler_step) and an fp32 restatement of that whole step for the tests.
 """
 from __future__ import annotations
 
@@ -32,7 +34,17 @@ def start_index(num_inference_steps: int, strength: float) -> int:
 
 class EulerDiscreteScheduler:
     def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, steps_offset=1,
-                 timestep_spacing="leading"):
+                 timestep_spacing="leading", sigma_schedule="discrete"):
+        """sigma_schedule "discrete": the interpolated training sigmas at the spaced timesteps (the reference's
+        config).  "karras": the rho = 7 schedule of Karras et al. 2022 (eq. 5) between the first and the last of
+        those sigmas, as diffusers' `_convert_to_karras` builds it,
+            sigma_i = (smax^(1/rho) + i / (n - 1) * (smin^(1/rho) - smax^(1/rho)))^rho,  then 0 appended,
+        with the fractional timesteps of diffusers' `_sigma_to_t`: with ls the log of the 1000 training sigmas and
+        k the last index with ls[k] <= log sigma (at most 998), w = clip((ls[k] - log sigma) / (ls[k] - ls[k+1]), 0, 1)
+        and t = (1 - w) * k + w * (k + 1).  (diffusers is not a dependency; this restates those two functions.)"""
+        if sigma_schedule not in ("discrete", "karras"):
+            raise ValueError(f"sigma_schedule {sigma_schedule!r}: 'discrete' or 'karras'")
+        self.sigma_schedule = sigma_schedule
         self.num_train_timesteps = num_train_timesteps
         betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
         self.alphas_cumprod = torch.cumprod(1.0 - betas, dim=0)
@@ -52,7 +64,11 @@ class EulerDiscreteScheduler:
         else:  # linspace
             ts = np.linspace(0, self.num_train_timesteps - 1, n, dtype=np.float32)[::-1].copy()
         sig = (((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5).numpy()
+        train = sig
         sig = np.interp(ts, np.arange(0, len(sig)), sig)
+        if self.sigma_schedule == "karras":
+            sig = karras_sigmas(sig[0], sig[-1], n)
+            ts = sigma_to_t(sig, np.log(train.astype(np.float64))).astype(np.float32)
         sig = np.concatenate([sig, [0.0]]).astype(np.float32)
         self.timesteps = torch.from_numpy(ts).to(device)
         self.sigmas = torch.from_numpy(sig).to(device)
@@ -77,3 +93,108 @@ class EulerDiscreteScheduler:
         while s.dim() < original_samples.dim():
             s = s.unsqueeze(-1)
         return original_samples + s * noise
+
+
+def karras_sigmas(sigma_max: float, sigma_min: float, n: int, rho: float = 7.0) -> np.ndarray:
+    """n float64 sigmas from sigma_max down to sigma_min, uniform in sigma^(1/rho) (Karras et al. 2022, eq. 5; diffusers
+    `_convert_to_karras`)."""
+    ramp = np.linspace(0.0, 1.0, n, dtype=np.float64)
+    hi, lo = float(sigma_max) ** (1.0 / rho), float(sigma_min) ** (1.0 / rho)
+    return (hi + ramp * (lo - hi)) ** rho
+
+
+def sigma_to_t(sigma, log_sigmas: np.ndarray) -> np.ndarray:
+    """Fractional training timestep of each sigma by linear interpolation in log sigma (diffusers `_sigma_to_t`)."""
+    ls = np.log(np.maximum(np.asarray(sigma, dtype=np.float64), 1e-10))
+    dists = ls[np.newaxis, :] - log_sigmas[:, np.newaxis]
+    low = np.cumsum(dists >= 0, axis=0).argmax(axis=0).clip(max=log_sigmas.shape[0] - 2)
+    lo, hi = log_sigmas[low], log_sigmas[low + 1]
+    w = np.clip((lo - ls) / (lo - hi), 0.0, 1.0)
+    return (1.0 - w) * low + w * (low + 1)
+
+
+SAMPLERS = ("euler", "dpmpp_2m")
+
+
+def sampler_coefficients(sigmas, sampler: str, first_step: int = 0) -> torch.Tensor:
+    """The per-step coefficients (a, b, c) of one sampler step in this project's VE latent convention,
+        x' = a * x + b * D + c * D_prev,   D = x - sigma_i * eps_hat   (the denoised estimate),
+    as a float64 table [n][3] for the n + 1 sigmas given (the last one 0); the device keeps it as fp32.
+    "euler": (s'/s, 1 - s'/s, 0) with s = sigma_i, s' = sigma_{i+1}: x + (s' - s) * eps_hat rewritten on D.
+    "dpmpp_2m": DPM-Solver++(2M) (Lu et al. 2022, alg. 2) as k-diffusion's `sample_dpmpp_2m` steps it: with
+    t = -ln sigma, h = t_{i+1} - t_i and r = (t_i - t_{i-1}) / h,
+        a = s'/s,  b = -expm1(-h) * (1 + 1 / (2 r)),  c = expm1(-h) / (2 r);
+    first order (b = -expm1(-h), c = 0) at `first_step`, the step a run enters at, where there is no D_prev (and at
+    step 0, which has no sigma before it); (0, 1, 0) where s' = 0 (the last step returns D).  a + b + c = 1 in
+    every row."""
+    if sampler not in SAMPLERS:
+        raise ValueError(f"sampler {sampler!r}: one of {SAMPLERS}")
+    sig = torch.as_tensor(sigmas).detach().cpu().to(torch.float64).reshape(-1)
+    n = sig.numel() - 1
+    if n < 1 or not bool((sig[:-1] > 0).all()) or not bool((sig[1:] < sig[:-1]).all()) or float(sig[-1]) < 0:
+        raise ValueError("sigmas must be positive and strictly decreasing, n + 1 entries with n >= 1")
+    if not 0 <= int(first_step) < n:
+        raise ValueError(f"first_step {first_step} outside the {n}-step schedule")
+    out = torch.zeros(n, 3, dtype=torch.float64)
+    for i in range(n):
+        s, s1 = float(sig[i]), float(sig[i + 1])
+        if s1 == 0.0:
+            out[i] = torch.tensor([0.0, 1.0, 0.0], dtype=torch.float64)
+            continue
+        a = s1 / s
+        if sampler == "euler":
+            out[i] = torch.tensor([a, 1.0 - a, 0.0], dtype=torch.float64)
+            continue
+        h = math.log(s) - math.log(s1)
+        e = math.expm1(-h)
+        if i == 0 or i == int(first_step):
+            out[i] = torch.tensor([a, -e, 0.0], dtype=torch.float64)
+        else:
+            r = (math.log(float(sig[i - 1])) - math.log(s)) / h
+            out[i] = torch.tensor([a, -e * (1.0 + 1.0 / (2.0 * r)), e / (2.0 * r)], dtype=torch.float64)
+    return out
+
+
+def rescale_factor_reference(noise, B: int, guidance: float, phi: float) -> torch.Tensor:
+    """fp32 [B]: phi * std(cond_b) / std(eps_hat_b) + (1 - phi) per clip, the factor `rescale_noise_cfg`
+    (animatediff/pipeline_animatediff_xl.py:414-425) multiplies eps_hat by; std is torch's default (unbiased) over all
+    of clip b.  noise: (2 * B * F * HW, Cl) UNet output rows, uncond clips then cond clips.  Deliberate difference: 1
+    where std(eps_hat_b) is 0 (the reference divides by it and gives NaN)."""
+    n2 = noise.float().reshape(2, B, -1)
+    e = n2[0] + guidance * (n2[1] - n2[0])
+    sc, se = n2[1].std(dim=1), e.std(dim=1)
+    ok = se > 0
+    return torch.where(ok, phi * sc / torch.where(ok, se, torch.ones_like(se)) + (1.0 - phi), torch.ones_like(se))
+
+
+def sampler_step_reference(noise, lat, hist, sigmas, coef, step: int, *, guidance: float = 7.5, ncopy: int = 2,
+                           guidance_rescale: float = 0.0, z0=None, eps=None, mask=None):
+    """One whole sampler step as vst_sampler_step (with vst_cfg_rescale_factor before it) defines it, fp32 torch:
+    noise (ncopy * B * F * HW, Cl) UNet output rows ((k * B + b) * F + f) * HW + p, k = 0 uncond, k = 1 cond;
+    lat / hist / z0 / eps (B, Cl, F, H, W); sigmas [n + 1]; coef [n][3] (sampler_coefficients); mask (1 or B, F, H, W).
+        eps_hat = u + g (c - u)                      (ncopy 1: the only row)
+        eps_hat *= factor[b]                         (guidance_rescale > 0: rescale_factor_reference)
+        D = lat - sigma_s * eps_hat
+        lat' = a_s * lat + b_s * D + c_s * hist      (hist is not read where c_s == 0)
+        lat' = m * lat' + (1 - m) * (z0 + sigma_{s+1} * eps)   (with a mask)
+    Returns (lat', D, factor or None): D is the history the next step reads."""
+    B, Cl, F, H, W = lat.shape
+    sig = torch.as_tensor(sigmas).float().cpu()
+    a, b, c = (float(v) for v in torch.as_tensor(coef)[step].float())
+    n5 = noise.float().reshape(ncopy, B, F, H, W, Cl).permute(0, 1, 5, 2, 3, 4)
+    e = n5[0] + guidance * (n5[1] - n5[0]) if ncopy == 2 else n5[0]
+    factor = None
+    if guidance_rescale > 0:
+        if ncopy != 2:
+            raise ValueError("guidance_rescale needs both CFG branches")
+        factor = rescale_factor_reference(noise, B, guidance, guidance_rescale)
+        e = e * factor.view(B, 1, 1, 1, 1)
+    lat = lat.float()
+    D = lat - sig[step] * e
+    new = a * lat + b * D
+    if c != 0.0:
+        new = new + c * hist.float()
+    if mask is not None:
+        m = mask.float().unsqueeze(1)
+        new = m * new + (1 - m) * (z0.float() + sig[step + 1] * eps.float())
+    return new, D, factor
