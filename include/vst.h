@@ -308,6 +308,11 @@ int vst_timestep_embedding(const float* t, const int* step_idx, int n, int dim, 
                            float downscale_freq_shift, void* out, int ld, int col0, int per_row, void* stream);
 int vst_pack_latents(const float* lat, int B, int Cl, int F, int HW, const float* sigmas, const int* step_idx,
                      float fixed_scale, int ncopy, void* out, void* stream);
+/* vst_euler_cfg_step: lat += (sigmas[s+1] - sigmas[s]) * eps_hat in place, eps_hat = u + g (c - u) (ncopy 1: the only
+ *   row), s = *step_idx read on the device; lat fp32 (B, Cl, F, HW), noise bf16 rows ((k*B + b)*F + f)*HW + p of Cl
+ *   channels, k = 0 uncond, k = 1 cond.  Returns 1 before any launch on a NULL pointer, a non-positive size or an
+ *   ncopy other than 1 or 2.  With vst_euler_cfg_step_masked and vst_sampler_step it is one kernel (csrc/sampler.hip);
+ *   the keep-mask blend those two add is described once, below. */
 int vst_euler_cfg_step(const void* noise, int ncopy, float guidance, float* lat, int B, int Cl, int F, int HW,
                        const float* sigmas, const int* step_idx, void* stream);
 int vst_step_advance(int* step_idx, int num_steps, void* stream);  // wraps to 0 at num_steps
@@ -402,11 +407,11 @@ int vst_vae_sample(const void* moments, int ld, int n, int HW, const float* eps,
  * inpaint pipelines.  Every entry returns 1 before any launch on a NULL pointer or a non-positive size; the step is
  * read on the device and must index the sigma table (the caller's counter, kept in range by vst_step_advance).
  * vst_noise_latents: lat[i] = z0[i] + sigmas[*step_idx] * eps[i] over n fp32 elements (the start latents).
- * vst_euler_cfg_step_masked: vst_euler_cfg_step followed by the blend with the re-noised source, in fp32:
- *   lat' = lat + (sigmas[s+1] - sigmas[s]) * eps_hat;  lat = m * lat' + (1 - m) * (z0 + sigmas[s+1] * eps)
- *   with noise rows as vst_euler_cfg_step reads them, lat / z0 / eps fp32 (B, Cl, F, HW), mask fp32
+ * The keep-mask blend (vst_euler_cfg_step_masked, and vst_sampler_step with a mask), in fp32 after the step's own
+ *   update lat': lat = m * lat' + (1 - m) * (z0 + sigmas[s+1] * eps), with z0 / eps fp32 of lat's shape, mask fp32
  *   (mask_clips, F, HW) in [0, 1] broadcast over channels (1 = free, 0 = keep the source), mask_clips 1 or B.
- *   m == 1 stores exactly vst_euler_cfg_step's bits; m == 0 at sigmas[s+1] == 0 stores z0's.
+ *   m == 1 stores exactly the unmasked step's bits; m == 0 at sigmas[s+1] == 0 stores z0's.
+ * vst_euler_cfg_step_masked: vst_euler_cfg_step's update, then the blend.
  * vst_u8_to_frames: uint8 frames (n, HW, C) -> bf16 rows [n*HW][ldd] = (v / 255 - 0.5) / 0.5 in fp32
  *   (video_dataset.py:117-118), channels C..ldd-1 zero-filled: the encoder's input, the inverse boundary of
  *   vst_frames_to_u8. */
@@ -421,7 +426,7 @@ int vst_u8_to_frames(const void* src, int n, int C, int HW, void* dst, int ldd, 
  * vst_sampler_step: one fused launch for every sampler that steps on the denoised estimate D = x - sigma * eps_hat:
  *   e = u + g (c - u) (ncopy 1: the only row);  e *= factor[b] (factor non-NULL; needs ncopy 2);
  *   D = lat - sigmas[s] e;  lat' = a lat + b D + c hist;  hist = D;
- *   lat = m lat' + (1 - m) (z0 + sigmas[s+1] eps)  (mask non-NULL, as vst_euler_cfg_step_masked)
+ *   then the keep-mask blend above (mask non-NULL; here a kept pixel is torch's fp32 z0 + sigmas[s+1] eps bit for bit)
  *   with (a, b, c) = coef[3 s ..], s = *step_idx read on the device.  coef for "dpmpp_2m" is DPM-Solver++(2M) as
  *   k-diffusion's sample_dpmpp_2m steps it (scheduler.sampler_coefficients); for "euler" it restates the update of
  *   vst_euler_cfg_step (EulerDiscreteScheduler.step, inference_animatediff.py:121).  hist (fp32, the shape of lat,

@@ -43,6 +43,8 @@ def test_wrappers_refuse_cpu_tensors():
         K.euler_cfg_step_masked(torch.zeros(2 * 18, 4, dtype=torch.bfloat16), z, sig, step, z.clone(), z.clone(),
                                 torch.ones(1, 2, 3, 3))
     with pytest.raises(_lib.VstError):
+        K.euler_cfg_step(torch.zeros(2 * 18, 4, dtype=torch.bfloat16), z, sig, step)
+    with pytest.raises(_lib.VstError):
         K.u8_to_frames(torch.zeros(1, 2, 2, 3, dtype=torch.uint8))
 
 
@@ -62,6 +64,14 @@ def test_entries_refuse_null_and_empty_without_gpu():
                 dict(mask=None), dict(ncopy=3), dict(ncopy=0), dict(B=0), dict(Cl=0), dict(F=-1), dict(HW=0),
                 dict(mc=3), dict(mc=0)):
         assert masked(**bad) == 1, bad
+
+    def plain(**kw):
+        a = dict(ok, **kw)
+        return lib.vst_euler_cfg_step(a["noise"], a["ncopy"], a["g"], a["lat"], a["B"], a["Cl"], a["F"], a["HW"],
+                                      a["sig"], a["step"], None)
+    for bad in (dict(noise=None), dict(lat=None), dict(sig=None), dict(step=None), dict(ncopy=3), dict(ncopy=0),
+                dict(B=0), dict(Cl=0), dict(F=-1), dict(HW=0)):
+        assert plain(**bad) == 1, bad
     assert lib.vst_u8_to_frames(None, 1, 3, 4, 1, 3, None) == 1
     assert lib.vst_u8_to_frames(1, 1, 3, 4, None, 3, None) == 1
     assert lib.vst_u8_to_frames(1, 0, 3, 4, 1, 3, None) == 1

@@ -121,8 +121,15 @@ def test_euler_cfg_step_masked_vs_torch(cuda, K, Cl, ncopy):
     for s in (0, 4, N - 1):
         lat = z0 + sig[s] * eps + 0.1 * torch.randn(shape, generator=g)  # latents as a run holds them at step s
         stb, step = guarded(torch.tensor([s], dtype=torch.int32), cuda)
-        plain = lat.to(cuda)
-        K.euler_cfg_step(nd, plain, sd_, step, guidance=7.5, ncopy=ncopy)  # the unchanged kernel, same inputs
+        # the plain step against the definition on its own: it shares the masked step's code, so identity 1 below
+        # does not test it independently
+        pb, plain = guarded(lat, cuda)
+        before = [b.clone() for b in (nb, sb, stb)]
+        K.euler_cfg_step(nd, plain, sd_, step, guidance=7.5, ncopy=ncopy)
+        name = f"plain Euler Cl={Cl} ncopy={ncopy} step={s}"
+        close_ulp(plain.cpu(), _ref_masked(noise, ncopy, 7.5, lat, sig, s, z0, eps, torch.ones(1, F_, H_, W_))[1], name)
+        assert guards_intact(pb, n), name
+        assert all(same_bytes(a, b) for a, b in zip(before, (nb, sb, stb))), name + ": input changed"
         for kind in ("zeros", "ones", "binary", "uniform"):
             for mc in (1, B_):
                 m = _masks(kind, mc, g)
@@ -149,6 +156,46 @@ def test_euler_cfg_step_masked_vs_torch(cuda, K, Cl, ncopy):
                         assert torch.equal(out, z0), name
 
 
+@pytest.mark.parametrize("ncopy", [1, 2])
+@pytest.mark.parametrize("entry", ["euler", "euler_masked", "sampler", "sampler_masked"])
+def test_misaligned_noise_stores_the_aligned_bytes(cuda, K, entry, ncopy):
+    """Cl = 4 with noise rows 2 bytes off an 8-byte boundary: the row loads must not assume the alignment, and every
+    entry point stores the bytes it stores on aligned noise.  m is fractional: the blend of the masked Euler step is
+    contractible and rounds differently in the 4-channel and the per-channel instance (one ulp), so equal bytes need
+    the 4-channel arithmetic on both sides, whatever the loads."""
+    from video_style_transfer_amd.scheduler import sampler_coefficients
+    g = torch.Generator().manual_seed(300 + ncopy)
+    sig = sigma_table(10)
+    coef = sampler_coefficients(sig, "dpmpp_2m").float().to(cuda)
+    shape = (B_, 4, F_, H_, W_)
+    lat, hist, z0, eps = (torch.randn(shape, generator=g).to(cuda) for _ in range(4))
+    m = torch.rand(B_, F_, H_, W_, generator=g).to(cuda)
+    noise = torch.randn(ncopy * B_ * F_ * H_ * W_, 4, generator=g).to(BF)
+    aligned = noise.to(cuda)
+    shifted = torch.empty(noise.numel() + 1, dtype=BF, device=cuda)[1:].view(noise.shape)
+    shifted.copy_(noise)
+    assert aligned.data_ptr() % 8 == 0 and shifted.data_ptr() % 8 == 2 and shifted.is_contiguous()
+    sd_, step = sig.to(cuda), torch.tensor([4], dtype=torch.int32, device=cuda)  # a second-order row: hist is read
+    assert float(coef[4, 2]) != 0.0
+    kw = dict(guidance=7.5, ncopy=ncopy)
+    fn = {"euler": lambda nz, x, h: K.euler_cfg_step(nz, x, sd_, step, **kw),
+          "euler_masked": lambda nz, x, h: K.euler_cfg_step_masked(nz, x, sd_, step, z0, eps, m, **kw),
+          "sampler": lambda nz, x, h: K.sampler_step(nz, x, h, sd_, coef, step, **kw),
+          "sampler_masked": lambda nz, x, h: K.sampler_step(nz, x, h, sd_, coef, step, z0=z0, eps=eps, mask=m, **kw)}[entry]
+    outs = []
+    for nz in (aligned, shifted):
+        x, h = lat.clone(), hist.clone()
+        fn(nz, x, h)
+        outs.append((x, h))
+    (xa, ha), (xs, hs) = outs
+    differ = (xa != xs).sum().item()
+    print(f"[source] {entry} ncopy={ncopy}, noise 2 bytes off: {differ} of {xa.numel()} latents differ, "
+          f"max|diff|={(xa - xs).abs().max().item():.3e} at max|lat|={xa.abs().max().item():.3e}")
+    assert torch.isfinite(xa).all() and not torch.equal(xa, lat)
+    assert same_bytes(xa, xs) and same_bytes(ha, hs)
+    assert same_bytes(shifted, aligned)
+
+
 def test_source_wrappers_refuse_bad_arguments(cuda, K):
     from video_style_transfer_amd._lib import VstError
     sig = sigma_table(10).to(cuda)
@@ -169,6 +216,12 @@ def test_source_wrappers_refuse_bad_arguments(cuda, K):
            lambda: K.euler_cfg_step_masked(noise, z, sig, step, z, z, torch.ones(3, F_, H_, W_, device=cuda)),
            lambda: K.euler_cfg_step_masked(noise, z, sig, step, z, z, m.transpose(2, 3)),
            lambda: K.euler_cfg_step_masked(noise, z[0], sig, step, z[0], z[0], m),
+           lambda: K.euler_cfg_step(noise.float(), z, sig, step),
+           lambda: K.euler_cfg_step(noise[:-1], z, sig, step),
+           lambda: K.euler_cfg_step(noise, z.transpose(3, 4), sig, step),
+           lambda: K.euler_cfg_step(noise, z, sig, step.long()),
+           lambda: K.euler_cfg_step(noise.cpu(), z, sig, step),
+           lambda: K.euler_cfg_step(noise, z.cpu(), sig, step),
            lambda: K.u8_to_frames(torch.zeros(1, 4, 4, 3, device=cuda)),
            lambda: K.u8_to_frames(torch.zeros(4, 4, 3, dtype=torch.uint8, device=cuda)),
            lambda: K.u8_to_frames(torch.zeros(1, 4, 4, 3, dtype=torch.uint8, device=cuda), ldd=2),

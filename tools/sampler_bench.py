@@ -5,14 +5,18 @@ calls): vst_sampler_step plain and masked, vst_cfg_rescale_factor (both launches
 min..max over the passes.
 Step: AnimateDiffDenoiser at the bench workload (16 x 512^2, CFG pair, whole-step HIP graph), three denoisers over one
 UNet, all captured up front and replayed alternately, `--steps` replays per pass:
-  euler          the default step (the bench.py path, untouched by the sampler: vst_euler_cfg_step), 50-step table
+  euler          the default step (the bench.py path: vst_euler_cfg_step), 50-step table
   dpmpp_2m       sampler="dpmpp_2m" on 20 Karras sigmas (vst_sampler_step)
   dpmpp_2m_resc  the same with guidance_rescale 0.7 (vst_cfg_rescale_factor + vst_sampler_step)
 A step's time does not depend on the length of its table, so steps/s at 20 against 50 steps follows from it.
+Bits (--md5, nothing timed): one JSON line per case with an md5 of lat (and of hist) after one call of each of the
+three step entry points on seeded CPU inputs, over shapes x ncopy x step x mask x mask_clips x factor.  Two builds
+(VST_LIB_AB, tools/ab_lib.sh) that print the same lines store the same bytes.
 
-  python tools/sampler_bench.py [--out profiles/sampler_<date>.json] [--passes 5] [--steps 4] [--no-step]
+  python tools/sampler_bench.py [--out profiles/sampler_<date>.json] [--passes 5] [--steps 4] [--no-step] [--md5]
 """
 import argparse
+import hashlib
 import json
 import os
 import statistics
@@ -78,6 +82,52 @@ def kernel_ab(passes, iters, dev):
     return rec
 
 
+MD5_SHAPES = [(2, 4, 3, 5, 7), (2, 5, 3, 5, 7), (1, 4, 16, 64, 64)]
+
+
+def md5(t):
+    return hashlib.md5(t.contiguous().view(torch.uint8).cpu().numpy().tobytes()).hexdigest()
+
+
+def md5_cases(dev):
+    """Every case's inputs come from its own generator, seeded by the case name."""
+    from video_style_transfer_amd.scheduler import EulerDiscreteScheduler, sampler_coefficients
+    sch = EulerDiscreteScheduler(sigma_schedule="karras")
+    sch.set_timesteps(FEW)
+    sig = sch.sigmas.float().to(dev)
+    coef = sampler_coefficients(sch.sigmas, "dpmpp_2m").float().to(dev)
+    for shape in MD5_SHAPES:
+        B, Cl, F, H, W = shape
+        for ncopy in (1, 2):
+            for s in (0, FEW // 2, FEW - 1):
+                for kind in (None, "binary", "uniform"):
+                    for mc in sorted({1, B}) if kind else (0,):
+                        # the plain Euler step takes no mask, the masked one needs one; a factor needs the CFG pair
+                        entries = ["euler_masked" if kind else "euler", "sampler"] + ["sampler_factor"] * (ncopy == 2)
+                        for entry in entries:
+                            name = f"{entry} {shape} ncopy={ncopy} step={s} mask={kind} mask_clips={mc}"
+                            g = torch.Generator().manual_seed(int(hashlib.md5(name.encode()).hexdigest()[:8], 16))
+                            lat, hist, z0, eps = (torch.randn(shape, generator=g).to(dev) for _ in range(4))
+                            noise = torch.randn(ncopy * B * F * H * W, Cl, generator=g).to(BF).to(dev)
+                            u = torch.rand(max(mc, 1), F, H, W, generator=g)
+                            mask = ((u < 0.5).float() if kind == "binary" else u).to(dev)
+                            factor = (0.5 + torch.rand(B, generator=g)).to(dev)
+                            step = torch.full((1,), s, dtype=torch.int32, device=dev)
+                            kw = dict(guidance=7.5, ncopy=ncopy)
+                            mkw = dict(z0=z0, eps=eps, mask=mask) if kind else {}
+                            if entry == "euler":
+                                K.euler_cfg_step(noise, lat, sig, step, **kw)
+                            elif entry == "euler_masked":
+                                K.euler_cfg_step_masked(noise, lat, sig, step, z0, eps, mask, **kw)
+                            else:
+                                K.sampler_step(noise, lat, hist, sig, coef, step, **kw, **mkw,
+                                               factor=factor if entry == "sampler_factor" else None)
+                            out = {"lat": md5(lat)}
+                            if entry.startswith("sampler"):
+                                out["hist"] = md5(hist)
+                            print(json.dumps({"case": name, "md5": out}), flush=True)
+
+
 def make_denoiser(unet, dev, **kw):
     from video_style_transfer_amd.pipeline import AnimateDiffDenoiser
     from video_style_transfer_amd.scheduler import EulerDiscreteScheduler
@@ -110,10 +160,13 @@ def main():
     ap.add_argument("--steps", type=int, default=4)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--no-step", action="store_true")
+    ap.add_argument("--md5", action="store_true")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("sampler_bench: no HIP device (timings need the GPU)")
     dev = torch.device("cuda")
+    if a.md5:
+        return md5_cases(dev)
     recs = [kernel_ab(a.passes, a.iters, dev)]
     if not a.no_step:
         from video_style_transfer_amd.utils import build_unet

@@ -5,7 +5,7 @@ denoisers over one UNet, all captured up front and replayed alternately, `--step
   plain        init_latents (the bench.py path: vst_euler_cfg_step)
   source       set_source(strength 0.5), no mask (the same launches as plain; only the start differs)
   source_mask  set_source(strength 0.5, random binary mask) (vst_euler_cfg_step_masked)
-Kernel: the two Euler kernels alone at that shape, alternating (device events around `iters` back-to-back calls), and
+Kernel: the two Euler steps (instances of one kernel) alone at that shape, alternating (device events around `iters` back-to-back calls), and
 vst_noise_latents.  Median and min..max over the passes.
 
   python tools/source_clip_bench.py [--out profiles/source_clip_<date>.json] [--passes 5] [--steps 4] [--no-step]

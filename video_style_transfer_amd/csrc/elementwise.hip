@@ -1,5 +1,5 @@
-// Small element-wise kernels around the UNet: timestep embeddings, latent packing,
-// the fused CFG-combine + Euler step of the denoise loop, and glue (silu, add, copy).
+// Small element-wise kernels around the UNet: timestep embeddings, latent packing
+// and glue (silu, add, copy); the update of the denoise loop is sampler.hip's.
 // Per-step scalars (timestep, sigma) are read from device tables indexed by a device
 // step counter, so one captured HIP graph of a denoise step replays for every step.
 #include "vst_common.h"
@@ -78,31 +78,6 @@ __global__ void pack_latents_kernel(const float* __restrict__ lat, int B, int Cl
   if (sigmas) { const float sg = sigmas[*step]; scale = rsqrtf(sg * sg + 1.0f); }
   const uint16_t v = f2bf(lat[idx] * scale);
   for (int k = 0; k < ncopy; ++k) out[((size_t)((k * B + b) * F + f) * HW + p) * Cl + c] = v;
-}
-
-// noise NHWC bf16 rows as above with ncopy=2 (k=0 uncond, k=1 cond) or 1 (no CFG).
-// latents += (sigma[step+1] - sigma[step]) * (u + g (c - u))   (Euler, epsilon prediction)
-__global__ void euler_cfg_kernel(const bf16_t* __restrict__ noise, int ncopy, float guidance, float* __restrict__ lat,
-                                 int B, int Cl, int F, int HW, const float* __restrict__ sigmas,
-                                 const int* __restrict__ step) {
-  const size_t n = (size_t)B * Cl * F * HW;
-  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= n) return;
-  const int p = (int)(idx % HW);
-  size_t r = idx / HW;
-  const int f = (int)(r % F); r /= F;
-  const int c = (int)(r % Cl);
-  const int b = (int)(r / Cl);
-  float eps;
-  if (ncopy == 2) {
-    const float u = bf2f(noise[((size_t)(b * F + f) * HW + p) * Cl + c]);
-    const float cc = bf2f(noise[((size_t)((B + b) * F + f) * HW + p) * Cl + c]);
-    eps = u + guidance * (cc - u);
-  } else {
-    eps = bf2f(noise[((size_t)(b * F + f) * HW + p) * Cl + c]);
-  }
-  const int s = *step;
-  lat[idx] += (sigmas[s + 1] - sigmas[s]) * eps;
 }
 
 // Row-block permutation for the frame <-> pixel shard exchange of the motion module.  Rows of C
@@ -500,15 +475,6 @@ extern "C" int vst_pack_latents(const float* lat, int B, int Cl, int F, int HW, 
   return launch_status();
 }
 
-extern "C" int vst_euler_cfg_step(const void* noise, int ncopy, float guidance, float* lat, int B, int Cl, int F,
-                                  int HW, const float* sigmas, const int* step_idx, void* stream) {
-  if (!noise || !lat || !sigmas || !step_idx || (ncopy != 1 && ncopy != 2)) return VST_ERR_ARG;
-  const size_t n = (size_t)B * Cl * F * HW;
-  hipLaunchKernelGGL(euler_cfg_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const bf16_t*)noise, ncopy, guidance, lat, B, Cl, F, HW, sigmas, step_idx);
-  return launch_status();
-}
-
 extern "C" int vst_step_advance(int* step_idx, int num_steps, void* stream) {
   if (!step_idx || num_steps <= 0) return VST_ERR_ARG;
   hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, step_idx, num_steps);
@@ -600,8 +566,6 @@ extern "C" int vst_sumpool2x2(const void* x, int nimg, int h, int w, int C, void
                      C, (bf16_t*)y);
   return launch_status();
 }
-
-static inline int grid_for(size_t total) { return (int)std::min<size_t>((total + 255) / 256, 16384); }
 
 extern "C" int vst_nchw_to_nhwc(const float* src, int n, int C, int HW, float mul, void* dst, int ldd, void* stream) {
   if (!src || !dst || n <= 0 || C <= 0 || HW <= 0 || ldd < C) return VST_ERR_ARG;

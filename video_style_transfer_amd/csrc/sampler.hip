@@ -1,33 +1,70 @@
-// Few-step sampling: the fused sampler step of the denoise loop for table-driven samplers (Euler
-// and DPM-Solver++ 2M on the denoised estimate) and the per-clip factor of guidance rescale.  Every per-step scalar
-// is read through the device step counter, so one captured step replays for the whole schedule.
+// The update of the denoise loop: one fused step kernel for the Euler step, the Euler step with a
+// per-pixel keep mask and the table-driven samplers (Euler and DPM-Solver++ 2M on the denoised estimate), and the
+// per-clip factor of guidance rescale.  Every per-step scalar is read through the device step counter, so one captured
+// step replays for the whole schedule.
 #include "vst_common.h"
 
 namespace vst {
 
-__device__ __forceinline__ float cfg_mix(float u, float c, float guidance) { return u + guidance * (c - u); }
+// What differs between the steps.  A rule is a kernel argument: the host sets its pointers, load() fills the per-step
+// scalars on the device, update() gives lat' for one element (li indexes lat and every tensor of its shape) and
+// renoise() the value of a kept pixel.  Each rule's expressions decide its rounding (where the compiler may contract
+// a * b + c into one FMA), so they change only with the bits.
 
-// z0 + s1 * eps rounded twice (product, then sum): the value torch computes, so a kept pixel is reproducible bit for
-// bit on the host at every step, not only where s1 == 0.
-__device__ __forceinline__ float renoise(float z0, float s1, float eps) {
+// lat' = lat + (sigma[s+1] - sigma[s]) e  (EulerDiscreteScheduler.step, epsilon prediction)
+struct EulerRule {
+  float ds;
+  __device__ __forceinline__ void load(const float* sigmas, int s, int) { ds = sigmas[s + 1] - sigmas[s]; }
+  __device__ __forceinline__ float update(float x, float e, size_t) const { return x + ds * e; }
+  static __device__ __forceinline__ float renoise(float z0, float s1, float eps) { return z0 + s1 * eps; }
+};
+
+// coef rows are (a, b, c):  e *= factor[b];  D = lat - sigma[s] e;  lat' = a lat + b D + c hist;  hist = D
+// hist is not read when c == 0 (the step a run enters at): whatever it holds then never reaches the latents.
+struct TableRule {
+  float* hist;
+  const float* coef;
+  const float* factor;  // per clip, or nullptr
+  float sg, ca, cb, cc, fac;
+  __device__ __forceinline__ void load(const float* sigmas, int s, int b) {
+    sg = sigmas[s];
+    ca = coef[3 * s], cb = coef[3 * s + 1], cc = coef[3 * s + 2];
+    fac = factor ? factor[b] : 1.0f;
+  }
+  __device__ __forceinline__ float update(float x, float e, size_t li) const {
+    const bool use_hist = cc != 0.0f;
+    if (factor) e *= fac;
+    const float D = x - sg * e;
+    const float h = use_hist ? hist[li] : 0.0f;
+    float ln = ca * x + cb * D;
+    if (use_hist) ln += cc * h;
+    hist[li] = D;
+    return ln;
+  }
+  // z0 + s1 * eps rounded twice (product, then sum): the value torch computes, so a kept pixel is reproducible bit
+  // for bit on the host at every step, not only where s1 == 0.
+  static __device__ __forceinline__ float renoise(float z0, float s1, float eps) {
 #pragma clang fp contract(off)
-  const float t = s1 * eps;
-  return z0 + t;
+    const float t = s1 * eps;
+    return z0 + t;
+  }
+};
+
+// The 4 channels of one noise row: one 8-byte load where the rows are 8-byte aligned (vec), four 2-byte loads otherwise.
+__device__ __forceinline__ u32x2 load_row4(const bf16_t* row, bool vec) {
+  if (vec) return *reinterpret_cast<const u32x2*>(row);
+  return u32x2{(uint32_t)row[0] | ((uint32_t)row[1] << 16), (uint32_t)row[2] | ((uint32_t)row[3] << 16)};
 }
 
-// One thread per pixel (b, f, p), laid out as euler_cfg_masked_kernel (source_clip.hip): the pixel's noise row(s) are
-// read once (CL4: one 8-byte load per CFG copy), then the Cl channel planes of lat / hist / z0 / eps are walked, each
-// plane access coalesced in p.  coef rows are (a, b, c):
-//   e = u + g (c - u);  e *= factor[b];  D = lat - sigma[s] e;  lat' = a lat + b D + c hist;  hist = D;
-//   MASKED: lat = m lat' + (1 - m) (z0 + sigma[s+1] eps)
-// hist is not read when c == 0 (the step a run enters at): whatever it holds then never reaches the latents.
-template <bool CL4, bool MASKED>
-__global__ __launch_bounds__(256) void sampler_step_kernel(const bf16_t* __restrict__ noise, int ncopy, float guidance,
-                                                           float* __restrict__ lat, float* __restrict__ hist, int B,
-                                                           int Cl, int F, int HW, const float* __restrict__ sigmas,
-                                                           const float* __restrict__ coef,
-                                                           const int* __restrict__ step,
-                                                           const float* __restrict__ factor,
+// One thread per pixel (b, f, p): the mask is read once, the pixel's noise row(s) once (CL4, Cl == 4: load_row4 per CFG
+// copy, and the 4 channels unrolled, so the stored bits do not depend on the alignment of noise), then the Cl channel planes of lat / z0 / eps (and what the rule holds) are walked, each plane access coalesced
+// in p.  noise rows are ((k*B + b)*F + f)*HW + p, Cl channels, k = 0 uncond, k = 1 cond:
+//   e = u + g (c - u);  lat' = rule.update(lat, e);  MASKED: lat = m lat' + (1 - m) rule.renoise(z0, sigma[s+1], eps)
+template <class Rule, bool CL4, bool MASKED>
+__global__ __launch_bounds__(256) void denoise_step_kernel(const bf16_t* __restrict__ noise, int ncopy, float guidance,
+                                                           float* __restrict__ lat, int B, int Cl, int F, int HW,
+                                                           const float* __restrict__ sigmas,
+                                                           const int* __restrict__ step, Rule rule,
                                                            const float* __restrict__ z0,
                                                            const float* __restrict__ eps,
                                                            const float* __restrict__ mask, int mask_clips) {
@@ -39,10 +76,7 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(const bf16_t* __restr
   const int f = (int)(bf % F);
   const int b = (int)(bf / F);
   const int s = *step;
-  const float sg = sigmas[s];
-  const float ca = coef[3 * s], cb = coef[3 * s + 1], cc = coef[3 * s + 2];
-  const bool use_hist = cc != 0.0f;
-  const float fac = factor ? factor[b] : 1.0f;
+  rule.load(sigmas, s, b);
   float s1 = 0.0f, m = 1.0f, keep = 0.0f;
   if (MASKED) {
     s1 = sigmas[s + 1];
@@ -55,25 +89,18 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(const bf16_t* __restr
   const bf16_t* nc = noise + (npix + t) * Cl;  // cond row (ncopy == 2)
 
   auto update = [&](float e) {
-    if (factor) e *= fac;
-    const float x = lat[li];
-    const float D = x - sg * e;
-    const float h = use_hist ? hist[li] : 0.0f;
-    float ln = ca * x + cb * D;
-    if (use_hist) ln += cc * h;
-    hist[li] = D;
-    if (MASKED) ln = m * ln + keep * renoise(z0[li], s1, eps[li]);
+    float ln = rule.update(lat[li], e, li);
+    if (MASKED) ln = m * ln + keep * Rule::renoise(z0[li], s1, eps[li]);
     lat[li] = ln;
   };
 
   if (CL4) {
-    const u32x2 u2 = *reinterpret_cast<const u32x2*>(nu);
-    float e[4] = {__uint_as_float(u2.x << 16), __uint_as_float(u2.x & 0xffff0000u), __uint_as_float(u2.y << 16),
-                  __uint_as_float(u2.y & 0xffff0000u)};
+    const bool vec = ((uintptr_t)noise & 7) == 0;  // rows are 8 bytes apart: the base decides for all of them
+    float e[4];
+    unpack4(load_row4(nu, vec), e);
     if (ncopy == 2) {
-      const u32x2 c2 = *reinterpret_cast<const u32x2*>(nc);
-      const float c[4] = {__uint_as_float(c2.x << 16), __uint_as_float(c2.x & 0xffff0000u),
-                          __uint_as_float(c2.y << 16), __uint_as_float(c2.y & 0xffff0000u)};
+      float c[4];
+      unpack4(load_row4(nc, vec), c);
 #pragma unroll
       for (int k = 0; k < 4; ++k) e[k] = cfg_mix(e[k], c[k], guidance);
     }
@@ -215,29 +242,63 @@ using namespace vst;
 
 static inline int rescale_blocks(size_t n) { return (int)((n + kRescaleChunk - 1) / kRescaleChunk); }
 
+// What every step takes, and the launch all three entry points share.  mask == nullptr: no blend.
+struct StepArgs {
+  const void* noise;
+  int ncopy;
+  float guidance;
+  float* lat;
+  int B, Cl, F, HW;
+  const float* sigmas;
+  const int* step_idx;
+  const float *z0, *eps, *mask;
+  int mask_clips;
+  void* stream;
+};
+
+template <class Rule>
+static int launch_step(const StepArgs& a, Rule rule) {
+  if (!a.noise || !a.lat || !a.sigmas || !a.step_idx || (a.ncopy != 1 && a.ncopy != 2)) return VST_ERR_ARG;
+  if (a.B <= 0 || a.Cl <= 0 || a.F <= 0 || a.HW <= 0) return VST_ERR_ARG;
+  if (a.mask && (!a.z0 || !a.eps || (a.mask_clips != 1 && a.mask_clips != a.B))) return VST_ERR_ARG;
+  const size_t npix = (size_t)a.B * a.F * a.HW;
+  const dim3 grid((unsigned)((npix + 255) / 256));
+  const bool cl4 = a.Cl == 4;
+#define VST_STEP_LAUNCH(C4, M)                                                                                     \
+  hipLaunchKernelGGL((denoise_step_kernel<Rule, C4, M>), grid, dim3(256), 0, (hipStream_t)a.stream,               \
+                     (const bf16_t*)a.noise, a.ncopy, a.guidance, a.lat, a.B, a.Cl, a.F, a.HW, a.sigmas, a.step_idx, \
+                     rule, a.z0, a.eps, a.mask, a.mask_clips)
+  if (cl4 && a.mask) VST_STEP_LAUNCH(true, true);
+  else if (cl4) VST_STEP_LAUNCH(true, false);
+  else if (a.mask) VST_STEP_LAUNCH(false, true);
+  else VST_STEP_LAUNCH(false, false);
+#undef VST_STEP_LAUNCH
+  return launch_status();
+}
+
+extern "C" int vst_euler_cfg_step(const void* noise, int ncopy, float guidance, float* lat, int B, int Cl, int F,
+                                  int HW, const float* sigmas, const int* step_idx, void* stream) {
+  return launch_step({noise, ncopy, guidance, lat, B, Cl, F, HW, sigmas, step_idx, nullptr, nullptr, nullptr, 0, stream},
+                     EulerRule{});
+}
+
+extern "C" int vst_euler_cfg_step_masked(const void* noise, int ncopy, float guidance, float* lat, int B, int Cl,
+                                         int F, int HW, const float* sigmas, const int* step_idx, const float* z0,
+                                         const float* eps, const float* mask, int mask_clips, void* stream) {
+  if (!mask) return VST_ERR_ARG;
+  return launch_step({noise, ncopy, guidance, lat, B, Cl, F, HW, sigmas, step_idx, z0, eps, mask, mask_clips, stream},
+                     EulerRule{});
+}
+
 extern "C" int vst_sampler_step(const void* noise, int ncopy, float guidance, float* lat, float* hist, int B, int Cl,
                                 int F, int HW, const float* sigmas, const float* coef, const int* step_idx,
                                 const float* factor, const float* z0, const float* eps, const float* mask,
                                 int mask_clips, void* stream) {
-  if (!noise || !lat || !hist || !sigmas || !coef || !step_idx || lat == hist) return VST_ERR_ARG;
-  if ((ncopy != 1 && ncopy != 2) || B <= 0 || Cl <= 0 || F <= 0 || HW <= 0) return VST_ERR_ARG;
-  const bool masked = mask != nullptr;
-  if (masked ? (!z0 || !eps || (mask_clips != 1 && mask_clips != B)) : (z0 || eps)) return VST_ERR_ARG;
+  if (!hist || !coef || lat == hist) return VST_ERR_ARG;
+  if (!mask && (z0 || eps)) return VST_ERR_ARG;
   if (factor && ncopy != 2) return VST_ERR_ARG;  // the rescale factor is defined on the CFG pair
-  const size_t npix = (size_t)B * F * HW;
-  const dim3 grid((unsigned)((npix + 255) / 256));
-  const hipStream_t s = (hipStream_t)stream;
-  const bf16_t* nz = (const bf16_t*)noise;
-  const bool cl4 = Cl == 4 && ((uintptr_t)noise & 7) == 0;
-#define VST_SAMPLER_LAUNCH(C4, M)                                                                                    \
-  hipLaunchKernelGGL((sampler_step_kernel<C4, M>), grid, dim3(256), 0, s, nz, ncopy, guidance, lat, hist, B, Cl, F, \
-                     HW, sigmas, coef, step_idx, factor, z0, eps, mask, mask_clips)
-  if (cl4 && masked) VST_SAMPLER_LAUNCH(true, true);
-  else if (cl4) VST_SAMPLER_LAUNCH(true, false);
-  else if (masked) VST_SAMPLER_LAUNCH(false, true);
-  else VST_SAMPLER_LAUNCH(false, false);
-#undef VST_SAMPLER_LAUNCH
-  return launch_status();
+  return launch_step({noise, ncopy, guidance, lat, B, Cl, F, HW, sigmas, step_idx, z0, eps, mask, mask_clips, stream},
+                     TableRule{hist, coef, factor});
 }
 
 extern "C" size_t vst_cfg_rescale_factor_workspace_bytes(int B, int Cl, int F, int HW) {

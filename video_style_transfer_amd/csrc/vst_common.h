@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <algorithm>
 
 namespace vst {
 
@@ -82,12 +83,22 @@ __device__ __forceinline__ void unpack8(const u32x4& v, float* f) {
     f[2 * i + 1] = __uint_as_float(v[i] & 0xffff0000u);
   }
 }
+__device__ __forceinline__ void unpack4(const u32x2& v, float* f) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    f[2 * i] = __uint_as_float(v[i] << 16);
+    f[2 * i + 1] = __uint_as_float(v[i] & 0xffff0000u);
+  }
+}
 __device__ __forceinline__ u32x4 pack8(const float* f) {
   u32x4 r;
 #pragma unroll
   for (int i = 0; i < 4; ++i) r[i] = pack2bf(f[2 * i], f[2 * i + 1]);
   return r;
 }
+
+// classifier-free guidance on one value: uncond + guidance * (cond - uncond)
+__device__ __forceinline__ float cfg_mix(float u, float c, float guidance) { return u + guidance * (c - u); }
 
 // x * sigmoid(x) on v_exp_f32 + v_rcp_f32 (the IEEE division would add a ~10-instruction fix-up sequence)
 __device__ __forceinline__ float silu(float x) {
@@ -156,4 +167,6 @@ __device__ __forceinline__ int xcd_remap(int orig, int nwg) {
 namespace vst {
 // Host side: the status an entry point returns after its launches.
 inline int launch_status() { return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH; }
+// Host side: 256-thread blocks for a grid-stride kernel over `total` items.
+inline int grid_for(size_t total) { return (int)std::min<size_t>((total + 255) / 256, 16384); }
 }  // namespace vst

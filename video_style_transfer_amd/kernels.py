@@ -1268,7 +1268,9 @@ def pack_latents(lat, out, *, sigmas=None, step_idx=None, fixed_scale=1.0, ncopy
 
 
 def euler_cfg_step(noise, lat, sigmas, step_idx, *, guidance=7.5, ncopy=2):
-    B, Cl, F, H, W = lat.shape
+    """lat += (sigmas[step + 1] - sigmas[step]) * e in place, e = u + guidance * (c - u) from the CFG pair's UNet
+    output rows noise (ncopy 1: the only rows)."""
+    B, Cl, F, H, W = _step_operands(noise, lat, sigmas, step_idx, ncopy, "euler_cfg_step")
     _lib.call("vst_euler_cfg_step", _p(noise), ncopy, float(guidance), _p(lat), B, Cl, F, H * W, _p(sigmas),
               _p(step_idx), _stream())
 
@@ -1298,6 +1300,31 @@ def _schedule(sigmas, step_idx, fn):
         raise _lib.VstError(f"{fn}: sigmas must be a 1-D table of num_steps + 1 entries, got {tuple(sigmas.shape)}")
 
 
+def _step_operands(noise, lat, sigmas, step_idx, ncopy, fn):
+    """What every denoise step takes: lat (B, Cl, F, H, W) fp32, ncopy 1 or 2, noise rows (ncopy * B * F * H * W, Cl)
+    bf16, the sigma table and the step counter.  Returns lat's dimensions."""
+    _flat(lat, F32, None, "lat", fn)
+    if lat.dim() != 5 or lat.numel() == 0:
+        raise _lib.VstError(f"{fn}: lat must be (B, Cl, F, H, W), got {tuple(lat.shape)}")
+    B, Cl, F, H, W = lat.shape
+    if ncopy not in (1, 2):
+        raise _lib.VstError(f"{fn}: ncopy {ncopy} (1 or 2)")
+    _flat(noise, BF16, (ncopy * B * F * H * W, Cl), "noise", fn)
+    _schedule(sigmas, step_idx, fn)
+    return B, Cl, F, H, W
+
+
+def _keep_mask(lat, z0, eps, mask, fn):
+    """The keep-mask triple of a step on lat: z0 and eps of lat's shape, mask (1 or B, F, H, W).  Returns mask_clips."""
+    B, _, F, H, W = lat.shape
+    _flat(z0, F32, lat.shape, "z0", fn)
+    _flat(eps, F32, lat.shape, "eps", fn)
+    _flat(mask, F32, None, "mask", fn)
+    if mask.dim() != 4 or mask.shape[0] not in (1, B) or tuple(mask.shape[1:]) != (F, H, W):
+        raise _lib.VstError(f"{fn}: mask {tuple(mask.shape)} vs (1 or {B}, {F}, {H}, {W})")
+    return mask.shape[0]
+
+
 def noise_latents(z0, eps, sigmas, step_idx, out=None):
     """fp32 z0 + sigmas[step_idx] * eps (the start latents of a source-clip run; sigma is read on the device)."""
     fn = "noise_latents"
@@ -1317,21 +1344,10 @@ def euler_cfg_step_masked(noise, lat, sigmas, step_idx, z0, eps, mask, *, guidan
     """euler_cfg_step, then lat = mask * lat + (1 - mask) * (z0 + sigmas[step + 1] * eps) in fp32: mask
     (1 or B, F, H, W) in [0, 1] over the channels of lat / z0 / eps (B, Cl, F, H, W); 1 = free, 0 = keep z0."""
     fn = "euler_cfg_step_masked"
-    _flat(lat, F32, None, "lat", fn)
-    if lat.dim() != 5 or lat.numel() == 0:
-        raise _lib.VstError(f"{fn}: lat must be (B, Cl, F, H, W), got {tuple(lat.shape)}")
-    B, Cl, F, H, W = lat.shape
-    if ncopy not in (1, 2):
-        raise _lib.VstError(f"{fn}: ncopy {ncopy} (1 or 2)")
-    _flat(noise, BF16, (ncopy * B * F * H * W, Cl), "noise", fn)
-    _flat(z0, F32, lat.shape, "z0", fn)
-    _flat(eps, F32, lat.shape, "eps", fn)
-    _flat(mask, F32, None, "mask", fn)
-    if mask.dim() != 4 or mask.shape[0] not in (1, B) or tuple(mask.shape[1:]) != (F, H, W):
-        raise _lib.VstError(f"{fn}: mask {tuple(mask.shape)} vs (1 or {B}, {F}, {H}, {W})")
-    _schedule(sigmas, step_idx, fn)
+    B, Cl, F, H, W = _step_operands(noise, lat, sigmas, step_idx, ncopy, fn)
+    mask_clips = _keep_mask(lat, z0, eps, mask, fn)
     _lib.call("vst_euler_cfg_step_masked", _p(noise), ncopy, float(guidance), _p(lat), B, Cl, F, H * W, _p(sigmas),
-              _p(step_idx), _p(z0), _p(eps), _p(mask), mask.shape[0], _stream())
+              _p(step_idx), _p(z0), _p(eps), _p(mask), mask_clips, _stream())
 
 
 # ---- few-step sampling: the table-driven sampler step and guidance rescale (pipeline._step, DESIGN.md §15) ----
@@ -1342,17 +1358,10 @@ def sampler_step(noise, lat, hist, sigmas, coef, step_idx, *, guidance=7.5, ncop
     (scheduler.sampler_coefficients as fp32 [n, 3]), hist = D; with z0 / eps / mask (all three) the keep-mask blend of
     euler_cfg_step_masked follows.  hist is not read where c == 0."""
     fn = "sampler_step"
-    _flat(lat, F32, None, "lat", fn)
-    if lat.dim() != 5 or lat.numel() == 0:
-        raise _lib.VstError(f"{fn}: lat must be (B, Cl, F, H, W), got {tuple(lat.shape)}")
-    B, Cl, F, H, W = lat.shape
-    if ncopy not in (1, 2):
-        raise _lib.VstError(f"{fn}: ncopy {ncopy} (1 or 2)")
-    _flat(noise, BF16, (ncopy * B * F * H * W, Cl), "noise", fn)
+    B, Cl, F, H, W = _step_operands(noise, lat, sigmas, step_idx, ncopy, fn)
     _flat(hist, F32, lat.shape, "hist", fn)
     if hist.data_ptr() == lat.data_ptr():
         raise _lib.VstError(f"{fn}: hist must not be lat")
-    _schedule(sigmas, step_idx, fn)
     _flat(coef, F32, (sigmas.numel() - 1, 3), "coef", fn)
     if factor is not None:
         _flat(factor, F32, (B,), "factor", fn)
@@ -1361,14 +1370,7 @@ def sampler_step(noise, lat, hist, sigmas, coef, step_idx, *, guidance=7.5, ncop
     given = [t is not None for t in (z0, eps, mask)]
     if any(given) and not all(given):
         raise _lib.VstError(f"{fn}: z0, eps and mask go together")
-    mask_clips = 0
-    if mask is not None:
-        _flat(z0, F32, lat.shape, "z0", fn)
-        _flat(eps, F32, lat.shape, "eps", fn)
-        _flat(mask, F32, None, "mask", fn)
-        if mask.dim() != 4 or mask.shape[0] not in (1, B) or tuple(mask.shape[1:]) != (F, H, W):
-            raise _lib.VstError(f"{fn}: mask {tuple(mask.shape)} vs (1 or {B}, {F}, {H}, {W})")
-        mask_clips = mask.shape[0]
+    mask_clips = _keep_mask(lat, z0, eps, mask, fn) if mask is not None else 0
     _lib.call("vst_sampler_step", _p(noise), ncopy, float(guidance), _p(lat), _p(hist), B, Cl, F, H * W, _p(sigmas),
               _p(coef), _p(step_idx), _p(factor), _p(z0), _p(eps), _p(mask), mask_clips, _stream())
 
