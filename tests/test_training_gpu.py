@@ -145,7 +145,10 @@ def test_geglu_fn_grads(cuda, M, C, Nh):
 
 
 @pytest.mark.parametrize("nclip,Fr,HW,C", [(2, 16, 8, 320), (1, 32, 4, 640), (1, 16, 2, 1280), (3, 5, 7, 64),
-                                           (1, 32, 4, 1280), (2, 24, 3, 128), (1, 16, 5, 512)])
+                                           (1, 32, 4, 1280), (2, 24, 3, 128), (1, 16, 5, 512),
+                                           # NT = 2 with 15 masked keys; a nearly empty NT = 1 tile; the widest head,
+                                           # one pixel (no F = 1: softmax over one key has zero gradients)
+                                           (1, 17, 3, 64), (2, 2, 5, 320), (1, 31, 1, 1280)])
 def test_temporal_attention_fn_grads(cuda, nclip, Fr, HW, C):
     import math
     from video_style_transfer_amd.autograd import TemporalAttentionFn
@@ -315,7 +318,13 @@ def test_resnet_block_backward_vs_oracle(cuda, cin, cout, H):
 
 @pytest.mark.parametrize("nb,heads,Nq,Nk,kv_div,kv_grad", [(2, 2, 256, 256, 1, True), (4, 3, 100, 77, 2, True),
                                                              (1, 1, 64, 130, 1, True), (2, 10, 1024, 1024, 1, True),
-                                                             (16, 2, 200, 77, 8, False), (3, 1, 17, 300, 3, True)])
+                                                             (16, 2, 200, 77, 8, False), (3, 1, 17, 300, 3, True),
+                                                             # tile boundaries: one query, key tail of 1; query tail
+                                                             # of 1 in a second 128-block, one partial key tile; exact
+                                                             # tiles, shared K/V; key tail of 1 in a second 128-key
+                                                             # workgroup, kv_div summing (no Nk = 1: zero gradients)
+                                                             (1, 1, 1, 65, 1, True), (1, 1, 129, 63, 1, True),
+                                                             (2, 1, 128, 64, 2, True), (4, 2, 33, 129, 4, True)])
 def test_spatial_attention_fn_grads(cuda, nb, heads, Nq, Nk, kv_div, kv_grad):
     """MFMA flash-attention backward (sa_bwd_dq_kernel / sa_bwd_dkv_kernel) vs torch.autograd in fp32 on the same
     bf16 operands; kv_grad=False is the frozen cross-attention case (the dK/dV pass is skipped)."""

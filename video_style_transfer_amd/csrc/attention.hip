@@ -20,8 +20,8 @@
 //    One wave per (b, p, head); F <= 32; head_dim = C/8 (40/80/160 for SDXL).
 //
 // The tile step of the two head_dim-64 forward kernels here and the softmax / P / V^T pieces of the two frame-axis
-// forwards (here and temporal_window.hip) are in attn_fwd.h.
-#include "attn_fwd.h"
+// forwards (here and temporal_window.hip) are in attn_fwd.h; the pieces of the three backward kernels are in attn_bwd.h.
+#include "attn_bwd.h"
 
 namespace vst {
 
@@ -266,6 +266,9 @@ __global__ __launch_bounds__(512) void temporal_attn_kernel(
 // (swapping the MFMA operands); the softmax statistics live in the transposed (query-column) tiles and reach the
 // key-column tiles by one ds_bpermute per row.  The d-major A operands (K^T, Q^T, dO^T) come from ds_read_b64_tr_b16
 // reads of the wave's own LDS copy of those rows, exactly like the forward's V^T.
+// A shell over the forward's frame-axis pieces (attn_fwd.h): the query-column mask / max / exp2 / sum is ta_softmax,
+// the three B operands are ta_pack_p (NT = 1: the unused upper 16 keys are literal zeros), the A fragments ta_vt_frag,
+// and dS = P (dP - D) is attn_ds (attn_bwd.h).  The key-column path below is this kernel's own.
 template <int NT, int D>
 __global__ __launch_bounds__(512) void temporal_attn_bwd_kernel(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V, int ldqkv,
@@ -342,15 +345,7 @@ __global__ __launch_bounds__(512) void temporal_attn_bwd_kernel(
         dpn[a][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(of[a], vf[c], dpn[a][c], 0, 0, 0);
       }
   }
-  // mask keys >= F: rows of st, columns (whole lanes) of sn
-#pragma unroll
-  for (int a = 0; a < NT; ++a)
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (a * 16 + g * 4 + i >= F) {
-#pragma unroll
-        for (int c = 0; c < NT; ++c) st[a][c][i] = -INFINITY;
-      }
+  // keys >= F are whole lanes (columns) of sn; ta_softmax masks them as rows of st
 #pragma unroll
   for (int c = 0; c < NT; ++c)
     if (c * 16 + fr >= F) {
@@ -360,28 +355,9 @@ __global__ __launch_bounds__(512) void temporal_attn_bwd_kernel(
 
   // ---- softmax statistics per query column; P^T and dS^T = P^T (dP^T - D) in place ----
   float mb[NT], inv[NT], dd[NT];
+  ta_softmax<NT>(st, F, scale_log2, inv, mb, lane);
 #pragma unroll
   for (int c = 0; c < NT; ++c) {
-    float mx = -INFINITY;
-#pragma unroll
-    for (int a = 0; a < NT; ++a)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) mx = fmaxf(mx, st[a][c][i]);
-    mx = fmaxf(mx, __shfl_xor(mx, 16));
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
-    mb[c] = mx * scale_log2;
-    float ls = 0.f;
-#pragma unroll
-    for (int a = 0; a < NT; ++a)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const float e = fast_exp2(st[a][c][i] * scale_log2 - mb[c]);
-        st[a][c][i] = e;
-        ls += e;
-      }
-    ls += __shfl_xor(ls, 16);
-    ls += __shfl_xor(ls, 32);
-    inv[c] = 1.0f / ls;
     float di = 0.f;
 #pragma unroll
     for (int a = 0; a < NT; ++a)
@@ -396,7 +372,7 @@ __global__ __launch_bounds__(512) void temporal_attn_bwd_kernel(
 #pragma unroll
     for (int a = 0; a < NT; ++a)
 #pragma unroll
-      for (int i = 0; i < 4; ++i) dpt[a][c][i] = st[a][c][i] * (dpt[a][c][i] - di);
+      for (int i = 0; i < 4; ++i) dpt[a][c][i] = attn_ds(st[a][c][i], dpt[a][c][i], di);
   }
   // ---- key-column tiles: row (query) 16a + 4g + i takes its statistics from lane 4g + i ----
 #pragma unroll
@@ -409,36 +385,24 @@ __global__ __launch_bounds__(512) void temporal_attn_bwd_kernel(
       for (int c = 0; c < NT; ++c) {
         const float pv = fast_exp2(sn[a][c][i] * scale_log2 - m) * iv;
         sn[a][c][i] = pv;
-        dpn[a][c][i] = pv * (dpn[a][c][i] - di);
+        dpn[a][c][i] = attn_ds(pv, dpn[a][c][i], di);
       }
     }
 
   // ---- B operands (32-deep k = the 16 or 32 frames; upper half zero for NT = 1) ----
   bf16x8 bq[NT], bk[NT], bv[NT];
-#pragma unroll
-  for (int c = 0; c < NT; ++c) {
-    const int a1 = NT - 1;
-    const float z = NT == 2 ? 1.f : 0.f;
-    bq[c] = pack_p8(dpt[0][c][0], dpt[0][c][1], dpt[0][c][2], dpt[0][c][3], z * dpt[a1][c][0], z * dpt[a1][c][1],
-                    z * dpt[a1][c][2], z * dpt[a1][c][3]);
-    bk[c] = pack_p8(dpn[0][c][0], dpn[0][c][1], dpn[0][c][2], dpn[0][c][3], z * dpn[a1][c][0], z * dpn[a1][c][1],
-                    z * dpn[a1][c][2], z * dpn[a1][c][3]);
-    bv[c] = pack_p8(sn[0][c][0], sn[0][c][1], sn[0][c][2], sn[0][c][3], z * sn[a1][c][0], z * sn[a1][c][1],
-                    z * sn[a1][c][2], z * sn[a1][c][3]);
-  }
+  ta_pack_p<NT>(dpt, bq);
+  ta_pack_p<NT>(dpn, bk);
+  ta_pack_p<NT>(sn, bv);
   // the staging stores (this wave only) complete before the transposed reads
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
 
   // ---- dQ^T = K^T dS^T, dK^T = Q^T dS, dV^T = dO^T P, per 16-wide d block ----
-  const int li = lane & 15;
-  const int r0 = g * 4 + (li >> 2);
 #pragma unroll
   for (int db = 0; db < DB; ++db) {
-    const int colb = (db * 16 + (li & 3) * 4) * 2;
-    const s16x4 z4{0, 0, 0, 0};
-    const bf16x8 kT = cat_tr(ds_read_tr(ks + r0 * VROW + colb), NT == 2 ? ds_read_tr(ks + (r0 + 16) * VROW + colb) : z4);
-    const bf16x8 qT = cat_tr(ds_read_tr(qs + r0 * VROW + colb), NT == 2 ? ds_read_tr(qs + (r0 + 16) * VROW + colb) : z4);
-    const bf16x8 oT = cat_tr(ds_read_tr(os + r0 * VROW + colb), NT == 2 ? ds_read_tr(os + (r0 + 16) * VROW + colb) : z4);
+    const bf16x8 kT = ta_vt_frag<NT>(ks, VROW, db, lane);
+    const bf16x8 qT = ta_vt_frag<NT>(qs, VROW, db, lane);
+    const bf16x8 oT = ta_vt_frag<NT>(os, VROW, db, lane);
     const int d = db * 16 + g * 4;
 #pragma unroll
     for (int c = 0; c < NT; ++c) {
@@ -472,17 +436,8 @@ __global__ __launch_bounds__(512) void temporal_attn_bwd_kernel(
 // Fragment conventions follow the forward: accumulators hold transposed tiles (lane column = the row token), P / dS
 // feed the B operand straight from the accumulators, and the A operands of the d-major products (K^T, dO^T, Q^T)
 // come from ds_read_b64_tr_b16 reads of a v_off-swizzled LDS copy.
-constexpr int SB_TILE = 64 * 64 * 2;  // one 64-row x 64-d bf16 tile, 8 KiB
-
-// one transposed A fragment: T^T[d = 16 db + li][rows 32 st + 4 g + {0..3}, 32 st + 16 + 4 g + {0..3}]
-__device__ __forceinline__ bf16x8 tr_frag(const char* T, int st, int db, int lane) {
-  const int li = lane & 15, g = lane >> 4;
-  const int r0 = st * 32 + g * 4 + (li >> 2);
-  const int col = db * 16 + (li & 3) * 4;
-  const int ch = col >> 3, within = (col & 7) * 2;
-  return cat_tr(ds_read_tr(T + v_off(r0, ch) + within), ds_read_tr(T + v_off(r0 + 16, ch) + within));
-}
-
+// Both kernels are shells over attn_bwd.h (its head comment lists which piece owns which rounding step): index math,
+// the LDS layout (SbStage flags), the mask and the loop are theirs.
 __global__ __launch_bounds__(256, 2) void sa_bwd_dq_kernel(
     const bf16_t* __restrict__ Q, int ldq, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V, int ldkv,
     const bf16_t* __restrict__ O, int ldo, const bf16_t* __restrict__ dO, int lddo, const float* __restrict__ lse,
@@ -502,23 +457,21 @@ __global__ __launch_bounds__(256, 2) void sa_bwd_dq_kernel(
   const auto rv = make_rsrc(V, kv_bytes);
 
   // Q^T / dO^T B fragments (lane column = query), D = dO . O, lse per query
-  bf16x8 qf[2][2], dof[2][2];
+  bf16x8 qf[2][2], dof[2][2], of[2][2];
   float Dq[2], l2[2];
   const int qbase = qblk * 128 + wid * 32;
+  sa_load_rows(qf, rq, b * Nq, qbase, Nq, ldq, h, lane);
+  sa_load_rows(dof, rdo, b * Nq, qbase, Nq, lddo, h, lane);
+  sa_load_rows(of, ro, b * Nq, qbase, Nq, ldo, h, lane);
 #pragma unroll
   for (int qb = 0; qb < 2; ++qb) {
     const int q = qbase + qb * 16 + fr;
     float dsum = 0.f;
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
-      const int col = h * 64 + kk * 32 + g * 8;
-      qf[qb][kk] = __builtin_bit_cast(bf16x8, buf_load16(rq, q < Nq ? ((b * Nq + q) * ldq + col) * 2 : kOOB));
-      const u32x4 dov = buf_load16(rdo, q < Nq ? ((b * Nq + q) * lddo + col) * 2 : kOOB);
-      const u32x4 ov = buf_load16(ro, q < Nq ? ((b * Nq + q) * ldo + col) * 2 : kOOB);
-      dof[qb][kk] = __builtin_bit_cast(bf16x8, dov);
       float a[8], c[8];
-      unpack8(dov, a);
-      unpack8(ov, c);
+      unpack8(__builtin_bit_cast(u32x4, dof[qb][kk]), a);
+      unpack8(__builtin_bit_cast(u32x4, of[qb][kk]), c);
 #pragma unroll
       for (int e = 0; e < 8; ++e) dsum += a[e] * c[e];
     }
@@ -530,66 +483,22 @@ __global__ __launch_bounds__(256, 2) void sa_bwd_dq_kernel(
     if (g == 0 && q < Nq) dvec[qi] = dsum;
   }
 
-  const int sc = tid & 7, sr = tid >> 3;  // staging: rows sr, sr + 32, 16-B chunk sc
-  u32x4 kreg[2], vreg[2];
-  auto load_kv = [&](int t) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int key = t * 64 + sr + 32 * i;
-      const int off = key < Nk ? ((bkv * Nk + key) * ldkv + h * 64 + sc * 8) * 2 : kOOB;
-      kreg[i] = buf_load16(rk, off);
-      vreg[i] = buf_load16(rv, off);
-    }
-  };
-  auto store_kv = [&](int buf) {
-    char* Kr = smem + buf * 3 * SB_TILE;
-    char* Kt = Kr + SB_TILE;
-    char* Vr = Kt + SB_TILE;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int row = sr + 32 * i;
-      *reinterpret_cast<u32x4*>(Kr + k_off(row, sc)) = kreg[i];
-      *reinterpret_cast<u32x4*>(Kt + v_off(row, sc)) = kreg[i];
-      *reinterpret_cast<u32x4*>(Vr + k_off(row, sc)) = vreg[i];
-    }
-  };
-
-  f32x4 acc[4][2];  // dQ^T [d-block][q-block]
-#pragma unroll
-  for (int d = 0; d < 4; ++d)
-#pragma unroll
-    for (int qb = 0; qb < 2; ++qb) acc[d][qb] = f32x4{0.f, 0.f, 0.f, 0.f};
+  SbStage<true, true, true, false> stg;  // LDS buffer: K rows, K transposed-read copy, V rows
+  f32x4 acc[4][2];                       // dQ^T [d-block][q-block]
+  sa_zero(acc);
 
   const int nt = (Nk + 63) / 64;
-  load_kv(0);
-  store_kv(0);
+  stg.load(rk, ldkv, rv, ldkv, bkv * Nk, 0, Nk, h, tid);
+  stg.store(smem, tid);
   __syncthreads();
   for (int t = 0; t < nt; ++t) {
     const int cur = t & 1;
-    if (t + 1 < nt) load_kv(t + 1);
-    const char* Kr = smem + cur * 3 * SB_TILE;
+    if (t + 1 < nt) stg.load(rk, ldkv, rv, ldkv, bkv * Nk, (t + 1) * 64, Nk, h, tid);
+    const char* Kr = smem + cur * stg.BYTES;
     const char* Kt = Kr + SB_TILE;
     const char* Vr = Kt + SB_TILE;
     f32x4 s[4][2], dp[4][2];  // S^T, dP^T: lane column q, rows key = 16 kt + 4 g + i
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt) {
-      bf16x8 kf[2], vf[2];
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        kf[kk] = *reinterpret_cast<const bf16x8*>(Kr + k_off(kt * 16 + fr, kk * 4 + g));
-        vf[kk] = *reinterpret_cast<const bf16x8*>(Vr + k_off(kt * 16 + fr, kk * 4 + g));
-      }
-#pragma unroll
-      for (int qb = 0; qb < 2; ++qb) {
-        f32x4 a{0.f, 0.f, 0.f, 0.f}, c{0.f, 0.f, 0.f, 0.f};
-        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[0], qf[qb][0], a, 0, 0, 0);
-        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[1], qf[qb][1], a, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[0], dof[qb][0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[1], dof[qb][1], c, 0, 0, 0);
-        s[kt][qb] = a;
-        dp[kt][qb] = c;
-      }
-    }
+    sb_scores(Kr, Vr, qf, dof, s, dp, lane);
     // dS^T = P^T * (dP^T - D), keys >= Nk masked
     const bool tail = (t + 1) * 64 > Nk;
 #pragma unroll
@@ -599,39 +508,24 @@ __global__ __launch_bounds__(256, 2) void sa_bwd_dq_kernel(
         const bool dead = tail && (t * 64 + kt * 16 + g * 4 + i >= Nk);
 #pragma unroll
         for (int qb = 0; qb < 2; ++qb) {
-          const float pv = dead ? 0.f : fast_exp2(s[kt][qb][i] * sl2 - l2[qb]);
-          s[kt][qb][i] = pv * (dp[kt][qb][i] - Dq[qb]);
+          const float pv = dead ? 0.f : sb_prob(s[kt][qb][i], sl2, l2[qb]);
+          s[kt][qb][i] = attn_ds(pv, dp[kt][qb][i], Dq[qb]);
         }
       }
     // dQ^T += K^T dS^T
 #pragma unroll
     for (int st = 0; st < 2; ++st) {
-      bf16x8 pf[2];
+      const bf16x8 pf[2] = {sa_pack2(s, st, 0), sa_pack2(s, st, 1)};
 #pragma unroll
-      for (int qb = 0; qb < 2; ++qb)
-        pf[qb] = pack_p8(s[2 * st][qb][0], s[2 * st][qb][1], s[2 * st][qb][2], s[2 * st][qb][3],
-                         s[2 * st + 1][qb][0], s[2 * st + 1][qb][1], s[2 * st + 1][qb][2], s[2 * st + 1][qb][3]);
-#pragma unroll
-      for (int db = 0; db < 4; ++db) {
-        const bf16x8 kt_f = tr_frag(Kt, st, db, lane);
-#pragma unroll
-        for (int qb = 0; qb < 2; ++qb)
-          acc[db][qb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kt_f, pf[qb], acc[db][qb], 0, 0, 0);
-      }
+      for (int db = 0; db < 4; ++db) sb_accum(acc, Kt, st, db, pf, lane);
     }
-    if (t + 1 < nt) store_kv(cur ^ 1);
+    if (t + 1 < nt) stg.store(smem + (cur ^ 1) * stg.BYTES, tid);
     __syncthreads();
   }
 #pragma unroll
   for (int qb = 0; qb < 2; ++qb) {
     const int q = qbase + qb * 16 + fr;
-    if (q >= Nq) continue;
-    bf16_t* row = dQ + (size_t)(b * Nq + q) * lddq + h * 64;
-#pragma unroll
-    for (int db = 0; db < 4; ++db) {
-      const f32x4 v = acc[db][qb] * scale;
-      *reinterpret_cast<u32x2*>(row + db * 16 + g * 4) = u32x2{pack2bf(v[0], v[1]), pack2bf(v[2], v[3])};
-    }
+    if (q < Nq) sa_store_row(acc, qb, scale, dQ + (size_t)(b * Nq + q) * lddq + h * 64, lane);
   }
 }
 
@@ -641,7 +535,8 @@ __global__ __launch_bounds__(256, 2) void sa_bwd_dkv_kernel(
     bf16_t* __restrict__ dK, bf16_t* __restrict__ dV, int lddkv, int nkv, int heads, int Nq, int Nk, int kv_div,
     float scale, float sl2, uint32_t q_bytes, uint32_t do_bytes, uint32_t kv_bytes) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int BUF = 4 * SB_TILE + 2 * 64 * 4;  // Q row, Q^T, dO row, dO^T, lse2[64], D[64]
+  using Stage = SbStage<true, true, true, true>;
+  constexpr int BUF = Stage::BYTES + 2 * 64 * 4;  // Q row, Q^T, dO row, dO^T, lse2[64], D[64]
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int nkb = (Nk + 127) / 128;
   const int wg = xcd_remap(blockIdx.x, nkb * heads * nkv);
@@ -656,30 +551,16 @@ __global__ __launch_bounds__(256, 2) void sa_bwd_dkv_kernel(
   // K / V B fragments (lane column = key)
   bf16x8 kf[2][2], vf[2][2];
   const int kbase = kblk * 128 + wid * 32;
-#pragma unroll
-  for (int kb = 0; kb < 2; ++kb) {
-    const int key = kbase + kb * 16 + fr;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      const int off = key < Nk ? ((bkv * Nk + key) * ldkv + h * 64 + kk * 32 + g * 8) * 2 : kOOB;
-      kf[kb][kk] = __builtin_bit_cast(bf16x8, buf_load16(rk, off));
-      vf[kb][kk] = __builtin_bit_cast(bf16x8, buf_load16(rv, off));
-    }
-  }
+  sa_load_rows(kf, rk, bkv * Nk, kbase, Nk, ldkv, h, lane);
+  sa_load_rows(vf, rv, bkv * Nk, kbase, Nk, ldkv, h, lane);
 
-  const int sc = tid & 7, sr = tid >> 3;
   const int nqt = (Nq + 63) / 64;
   const int ntiles = kv_div * nqt;  // (query batch bkv * kv_div + j, query tile)
-  u32x4 qreg[2], oreg[2];
+  Stage stg;
   float lreg = 0.f, dreg = 0.f;
   auto load_q = [&](int it) {
     const int b = bkv * kv_div + it / nqt, q0 = (it % nqt) * 64;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int q = q0 + sr + 32 * i;
-      qreg[i] = buf_load16(rq, q < Nq ? ((b * Nq + q) * ldq + h * 64 + sc * 8) * 2 : kOOB);
-      oreg[i] = buf_load16(rdo, q < Nq ? ((b * Nq + q) * lddo + h * 64 + sc * 8) * 2 : kOOB);
-    }
+    stg.load(rq, ldq, rdo, lddo, b * Nq, q0, Nq, h, tid);
     if (tid < 64) {
       const int q = q0 + tid;
       const size_t qi = (size_t)(b * heads + h) * Nq + q;
@@ -688,33 +569,17 @@ __global__ __launch_bounds__(256, 2) void sa_bwd_dkv_kernel(
     }
   };
   auto store_q = [&](int buf) {
-    char* Qr = smem + buf * BUF;
-    char* Qt = Qr + SB_TILE;
-    char* Or = Qt + SB_TILE;
-    char* Ot = Or + SB_TILE;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int row = sr + 32 * i;
-      *reinterpret_cast<u32x4*>(Qr + k_off(row, sc)) = qreg[i];
-      *reinterpret_cast<u32x4*>(Qt + v_off(row, sc)) = qreg[i];
-      *reinterpret_cast<u32x4*>(Or + k_off(row, sc)) = oreg[i];
-      *reinterpret_cast<u32x4*>(Ot + v_off(row, sc)) = oreg[i];
-    }
+    stg.store(smem + buf * BUF, tid);
     if (tid < 64) {
-      float* ls = reinterpret_cast<float*>(Ot + SB_TILE);
+      float* ls = reinterpret_cast<float*>(smem + buf * BUF + Stage::BYTES);
       ls[tid] = lreg;
       ls[64 + tid] = dreg;
     }
   };
 
   f32x4 dk[4][2], dv[4][2];  // dK^T, dV^T [d-block][key-block]
-#pragma unroll
-  for (int d = 0; d < 4; ++d)
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) {
-      dk[d][kb] = f32x4{0.f, 0.f, 0.f, 0.f};
-      dv[d][kb] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
+  sa_zero(dk);
+  sa_zero(dv);
 
   load_q(0);
   store_q(0);
@@ -728,25 +593,7 @@ __global__ __launch_bounds__(256, 2) void sa_bwd_dkv_kernel(
     const char* Ot = Or + SB_TILE;
     const float* ls = reinterpret_cast<const float*>(Ot + SB_TILE);
     f32x4 s[4][2], dp[4][2];  // S, dP: lane column key, rows q = 16 qt + 4 g + i
-#pragma unroll
-    for (int qt = 0; qt < 4; ++qt) {
-      bf16x8 qa[2], oa[2];
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        qa[kk] = *reinterpret_cast<const bf16x8*>(Qr + k_off(qt * 16 + fr, kk * 4 + g));
-        oa[kk] = *reinterpret_cast<const bf16x8*>(Or + k_off(qt * 16 + fr, kk * 4 + g));
-      }
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb) {
-        f32x4 a{0.f, 0.f, 0.f, 0.f}, c{0.f, 0.f, 0.f, 0.f};
-        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[0], kf[kb][0], a, 0, 0, 0);
-        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[1], kf[kb][1], a, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(oa[0], vf[kb][0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(oa[1], vf[kb][1], c, 0, 0, 0);
-        s[qt][kb] = a;
-        dp[qt][kb] = c;
-      }
-    }
+    sb_scores(Qr, Or, kf, vf, s, dp, lane);
     // P into s, dS into dp
 #pragma unroll
     for (int qt = 0; qt < 4; ++qt) {
@@ -756,31 +603,20 @@ __global__ __launch_bounds__(256, 2) void sa_bwd_dkv_kernel(
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
-          const float pv = fast_exp2(s[qt][kb][i] * sl2 - lq[i]);
+          const float pv = sb_prob(s[qt][kb][i], sl2, lq[i]);
           s[qt][kb][i] = pv;
-          dp[qt][kb][i] = pv * (dp[qt][kb][i] - dq[i]);
+          dp[qt][kb][i] = attn_ds(pv, dp[qt][kb][i], dq[i]);
         }
     }
     // dV^T += dO^T P,  dK^T += Q^T dS
 #pragma unroll
     for (int st = 0; st < 2; ++st) {
-      bf16x8 pf[2], sf[2];
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb) {
-        pf[kb] = pack_p8(s[2 * st][kb][0], s[2 * st][kb][1], s[2 * st][kb][2], s[2 * st][kb][3],
-                         s[2 * st + 1][kb][0], s[2 * st + 1][kb][1], s[2 * st + 1][kb][2], s[2 * st + 1][kb][3]);
-        sf[kb] = pack_p8(dp[2 * st][kb][0], dp[2 * st][kb][1], dp[2 * st][kb][2], dp[2 * st][kb][3],
-                         dp[2 * st + 1][kb][0], dp[2 * st + 1][kb][1], dp[2 * st + 1][kb][2], dp[2 * st + 1][kb][3]);
-      }
+      const bf16x8 pf[2] = {sa_pack2(s, st, 0), sa_pack2(s, st, 1)};
+      const bf16x8 sf[2] = {sa_pack2(dp, st, 0), sa_pack2(dp, st, 1)};
 #pragma unroll
       for (int db = 0; db < 4; ++db) {
-        const bf16x8 ot = tr_frag(Ot, st, db, lane);
-        const bf16x8 qtf = tr_frag(Qt, st, db, lane);
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-          dv[db][kb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ot, pf[kb], dv[db][kb], 0, 0, 0);
-          dk[db][kb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qtf, sf[kb], dk[db][kb], 0, 0, 0);
-        }
+        sb_accum(dv, Ot, st, db, pf, lane);
+        sb_accum(dk, Qt, st, db, sf, lane);
       }
     }
     if (it + 1 < ntiles) store_q(cur ^ 1);
@@ -790,15 +626,9 @@ __global__ __launch_bounds__(256, 2) void sa_bwd_dkv_kernel(
   for (int kb = 0; kb < 2; ++kb) {
     const int key = kbase + kb * 16 + fr;
     if (key >= Nk) continue;
-    bf16_t* krow = dK + (size_t)(bkv * Nk + key) * lddkv + h * 64;
-    bf16_t* vrow = dV + (size_t)(bkv * Nk + key) * lddkv + h * 64;
-#pragma unroll
-    for (int db = 0; db < 4; ++db) {
-      const f32x4 a = dk[db][kb] * scale;
-      const f32x4 c = dv[db][kb];
-      *reinterpret_cast<u32x2*>(krow + db * 16 + g * 4) = u32x2{pack2bf(a[0], a[1]), pack2bf(a[2], a[3])};
-      *reinterpret_cast<u32x2*>(vrow + db * 16 + g * 4) = u32x2{pack2bf(c[0], c[1]), pack2bf(c[2], c[3])};
-    }
+    const size_t row = (size_t)(bkv * Nk + key) * lddkv + h * 64;
+    sa_store_row(dk, kb, scale, dK + row, lane);
+    sa_store_row(dv, kb, 1.f, dV + row, lane);  // exact: x * 1 = x
   }
 }
 
@@ -813,6 +643,31 @@ static int launch_temporal(const bf16_t* Q, const bf16_t* K, const bf16_t* V, in
   hipLaunchKernelGGL((temporal_attn_kernel<NT, D>), dim3((units + wpg - 1) / wpg), dim3(64 * wpg), wpg * VBYTES, s,
                      Q, K, V, ld, O, ldo, nclip, F, HW, heads, sl2, bytes);
   return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
+}
+
+// The (NT, head_dim) instances of the frame-axis forward and backward: fn(TaShape<NT, D>{}) with NT = 1 for F <= 16,
+// else 2, for the head dims the kernels are built for
+template <int NT_, int D_>
+struct TaShape {
+  static constexpr int NT = NT_, D = D_;
+};
+template <class Fn>
+static int ta_dispatch(int F, int head_dim, Fn&& fn) {
+#define VST_TA(D) \
+  case D:         \
+    return F <= 16 ? fn(TaShape<1, D>{}) : fn(TaShape<2, D>{});
+  switch (head_dim) {
+    VST_TA(8)
+    VST_TA(16)
+    VST_TA(32)
+    VST_TA(40)
+    VST_TA(64)
+    VST_TA(80)
+    VST_TA(160)
+    default:
+      return VST_ERR_ARG;
+  }
+#undef VST_TA
 }
 
 }  // namespace vst
@@ -904,22 +759,10 @@ extern "C" int vst_temporal_attention(const void* q, const void* k, const void* 
   hipStream_t s = (hipStream_t)stream;
   const bf16_t *Q = (const bf16_t*)q, *K = (const bf16_t*)k, *V = (const bf16_t*)v;
   bf16_t* O = (bf16_t*)o;
-#define VST_TA(D)                                                                                    \
-  case D:                                                                                          \
-    return F <= 16 ? launch_temporal<1, D>(Q, K, V, ldqkv, O, ldo, nclip, F, HW, heads, sl2, bytes, s) \
-                   : launch_temporal<2, D>(Q, K, V, ldqkv, O, ldo, nclip, F, HW, heads, sl2, bytes, s);
-  switch (head_dim) {
-    VST_TA(8)
-    VST_TA(16)
-    VST_TA(32)
-    VST_TA(40)
-    VST_TA(64)
-    VST_TA(80)
-    VST_TA(160)
-    default:
-      return VST_ERR_ARG;
-  }
-#undef VST_TA
+  return ta_dispatch(F, head_dim, [&](auto sh) {
+    using S = decltype(sh);
+    return launch_temporal<S::NT, S::D>(Q, K, V, ldqkv, O, ldo, nclip, F, HW, heads, sl2, bytes, s);
+  });
 }
 
 extern "C" int vst_temporal_attention_bwd(const void* q, const void* k, const void* v, int ldqkv, const void* dout,
@@ -938,29 +781,16 @@ extern "C" int vst_temporal_attention_bwd(const void* q, const void* k, const vo
   hipStream_t s = (hipStream_t)stream;
   const bf16_t *Q = (const bf16_t*)q, *K = (const bf16_t*)k, *V = (const bf16_t*)v, *G = (const bf16_t*)dout;
   bf16_t *GQ = (bf16_t*)dq, *GK = (bf16_t*)dk, *GV = (bf16_t*)dv;
-  auto launch = [&](auto kern, int nf, int D) {
-    const int wave_bytes = 3 * nf * ((D + 15) / 16) * 32;  // K, Q, dO rows
+  return ta_dispatch(F, head_dim, [&](auto sh) {
+    using S = decltype(sh);
+    const int wave_bytes = 3 * 16 * S::NT * ((S::D + 15) / 16) * 32;  // K, Q, dO rows
     // all heads of a (clip, pixel) in one workgroup when they fit in 64 KiB, else as many units as do
     const int wpg = heads * wave_bytes <= 64 * 1024 ? std::min(heads, 8) : std::max(1, 64 * 1024 / wave_bytes);
-    hipLaunchKernelGGL(kern, dim3((unsigned)((units + wpg - 1) / wpg)), dim3(64 * wpg), wpg * wave_bytes, s, Q, K, V,
-                       ldqkv, G, lddo, GQ, GK, GV, lddqkv, nclip, F, HW, heads, scale, sl2, qkvb, dob);
+    hipLaunchKernelGGL((temporal_attn_bwd_kernel<S::NT, S::D>), dim3((unsigned)((units + wpg - 1) / wpg)),
+                       dim3(64 * wpg), wpg * wave_bytes, s, Q, K, V, ldqkv, G, lddo, GQ, GK, GV, lddqkv, nclip, F, HW,
+                       heads, scale, sl2, qkvb, dob);
     return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
-  };
-#define VST_TAB(D)                                                                              \
-  case D:                                                                                       \
-    return F <= 16 ? launch(temporal_attn_bwd_kernel<1, D>, 16, D) : launch(temporal_attn_bwd_kernel<2, D>, 32, D);
-  switch (head_dim) {
-    VST_TAB(8)
-    VST_TAB(16)
-    VST_TAB(32)
-    VST_TAB(40)
-    VST_TAB(64)
-    VST_TAB(80)
-    VST_TAB(160)
-    default:
-      return VST_ERR_ARG;
-  }
-#undef VST_TAB
+  });
 }
 
 // D = dO . O per query (written by the dQ kernel, read by the dK/dV kernel)

@@ -12,6 +12,9 @@
 //    (clip, pixel, head) holds the whole NT x NT score tile; the kernels share the masked one-pass softmax, the P
 //    packing and the transposed V fragment read (test_windowed_bit_anchors).  Their Q/K loads (position add) and their
 //    output paths (ring blend) differ and stay with the kernels.
+//
+// The backward kernels (attn_bwd.h) take from here what they round as the forward does: sa_load_rows, sa_zero,
+// sa_pack2, sa_store_row, and ta_softmax / ta_pack_p / ta_vt_frag.
 #pragma once
 #include "attn_common.h"
 
@@ -28,29 +31,41 @@ struct SaState {
   float mrun[2], mb[2], lrun[2];
 };
 
-__device__ __forceinline__ void sa_init(SaState& st) {
+// A transposed accumulator [d-block][row-block] (lane col = token row, rows d = 16db + 4g + i) from zero
+__device__ __forceinline__ void sa_zero(f32x4 (&acc)[4][2]) {
 #pragma unroll
   for (int d = 0; d < 4; ++d)
 #pragma unroll
-    for (int qb = 0; qb < 2; ++qb) st.o[d][qb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int cb = 0; cb < 2; ++cb) acc[d][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
+__device__ __forceinline__ void sa_init(SaState& st) {
+  sa_zero(st.o);
 #pragma unroll
   for (int qb = 0; qb < 2; ++qb) st.mrun[qb] = -INFINITY, st.mb[qb] = 0.f, st.lrun[qb] = 0.f;
 }
 
-// Q^T fragments (B operand of S^T = K.Q^T) of the wave's 32 queries qbase..qbase+31 of the batch whose first token row
-// is row0: lane (col q, group g) holds Q[q][32kk + 8g .. +7]
-__device__ __forceinline__ void sa_load_q(bf16x8 (&qf)[2][2], __amdgpu_buffer_rsrc_t rq, int row0, int qbase, int Nq,
-                                          int ldq, int h, int lane) {
+// B fragments of the wave's 32 token rows base..base+31 (of N) of the batch whose first token row is row0: lane (col
+// r, group g) holds X[r][32kk + 8g .. +7]; rows past N read zeros.  Q^T for S^T = K.Q^T, and every register operand of
+// the backward kernels.
+__device__ __forceinline__ void sa_load_rows(bf16x8 (&xf)[2][2], __amdgpu_buffer_rsrc_t rx, int row0, int base, int N,
+                                             int ld, int h, int lane) {
   const int fr = lane & 15, g = lane >> 4;
 #pragma unroll
-  for (int qb = 0; qb < 2; ++qb) {
-    const int q = qbase + qb * 16 + fr;
+  for (int cb = 0; cb < 2; ++cb) {
+    const int r = base + cb * 16 + fr;
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
-      const int off = q < Nq ? ((row0 + q) * ldq + h * 64 + kk * 32 + g * 8) * 2 : kOOB;
-      qf[qb][kk] = __builtin_bit_cast(bf16x8, buf_load16(rq, off));
+      const int off = r < N ? ((row0 + r) * ld + h * 64 + kk * 32 + g * 8) * 2 : kOOB;
+      xf[cb][kk] = __builtin_bit_cast(bf16x8, buf_load16(rx, off));
     }
   }
+}
+
+// The forward's Q^T fragments
+__device__ __forceinline__ void sa_load_q(bf16x8 (&qf)[2][2], __amdgpu_buffer_rsrc_t rq, int row0, int qbase, int Nq,
+                                          int ldq, int h, int lane) {
+  sa_load_rows(qf, rq, row0, qbase, Nq, ldq, h, lane);
   // The Q loads issue before the first K/V loads.  Sunk behind them, they are still in flight after the first tile's
   // LDS stores, and their s_waitcnt vmcnt lands inside the key loop, where on every later tile it waits for the
   // prefetch of the next one (sa_self_kernel 32x32: 146 -> 149 us).
@@ -114,6 +129,24 @@ __device__ __forceinline__ void sa_mask(f32x4 (&s)[4][2], int t, int Nk, int lan
     }
 }
 
+// The bf16 B fragment of 32-deep k-step ks from the accumulator tiles t[2ks][cb] (elements 0-3) and t[2ks+1][cb] (4-7):
+// P^T in the forward, P / dS in the backward
+__device__ __forceinline__ bf16x8 sa_pack2(const f32x4 (&t)[4][2], int ks, int cb) {
+  return pack_p8(t[2 * ks][cb][0], t[2 * ks][cb][1], t[2 * ks][cb][2], t[2 * ks][cb][3], t[2 * ks + 1][cb][0],
+                 t[2 * ks + 1][cb][1], t[2 * ks + 1][cb][2], t[2 * ks + 1][cb][3]);
+}
+
+// Column block cb of a transposed accumulator, times scale, as the 64 bf16 of the lane's token row
+__device__ __forceinline__ void sa_store_row(const f32x4 (&acc)[4][2], int cb, float scale, bf16_t* row, int lane) {
+  const int g = lane >> 4;
+#pragma unroll
+  for (int db = 0; db < 4; ++db) {
+    const f32x4 v = acc[db][cb] * scale;
+    u32x2 w{pack2bf(v[0], v[1]), pack2bf(v[2], v[3])};
+    *reinterpret_cast<u32x2*>(row + db * 16 + g * 4) = w;
+  }
+}
+
 // One 64-key tile from the K and V tiles at Ks / Vs: S^T, the caller's mask on it, online softmax, O^T += V^T.P^T.
 template <class Mask>
 __device__ __forceinline__ void sa_tile(const char* Ks, const char* Vs, const bf16x8 (&qf)[2][2], const int (&voff)[4],
@@ -175,9 +208,7 @@ __device__ __forceinline__ void sa_tile(const char* Ks, const char* Vs, const bf
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-    for (int qb = 0; qb < 2; ++qb)
-      pf[ks][qb] = pack_p8(s[2 * ks][qb][0], s[2 * ks][qb][1], s[2 * ks][qb][2], s[2 * ks][qb][3],
-                           s[2 * ks + 1][qb][0], s[2 * ks + 1][qb][1], s[2 * ks + 1][qb][2], s[2 * ks + 1][qb][3]);
+    for (int qb = 0; qb < 2; ++qb) pf[ks][qb] = sa_pack2(s, ks, qb);
 #pragma unroll
   for (int db = 0; db < 4; ++db) {
     const char* vp = Vs + voff[db];  // rows +16 / +32 keep the swizzle: immediate offsets 2048 / 4096
@@ -205,13 +236,7 @@ __device__ __forceinline__ void sa_finish(const SaState& st, bf16_t* O, int ldo,
     const int q = qbase + qb * 16 + fr;
     if (q >= Nq) continue;
     if (lse && g == 0) lse[lse0 + q] = st.mrun[qb] * scale_log2 + __log2f(l);
-    bf16_t* orow = O + (size_t)(row0 + q) * ldo + h * 64;
-#pragma unroll
-    for (int db = 0; db < 4; ++db) {
-      const f32x4 v = st.o[db][qb] * inv;
-      u32x2 w{pack2bf(v[0], v[1]), pack2bf(v[2], v[3])};
-      *reinterpret_cast<u32x2*>(orow + db * 16 + g * 4) = w;
-    }
+    sa_store_row(st.o, qb, inv, O + (size_t)(row0 + q) * ldo + h * 64, lane);
   }
 }
 
@@ -219,9 +244,11 @@ __device__ __forceinline__ void sa_finish(const SaState& st, bf16_t* O, int ldo,
 // Frame-axis core.  NT = number of 16-frame tiles; s[a][c] is the S^T tile of keys 16a.. and queries 16c..
 // ---------------------------------------------------------------------------------
 
-// Keys >= n get -inf, then the softmax per query column: s becomes the unnormalised P, inv[c] = 1 / l
+// Keys >= n get -inf, then the softmax per query column: s becomes the unnormalised P, inv[c] = 1 / l, mb[c] = the
+// column's max in the exp2 domain (the backward recomputes the key-column P from it)
 template <int NT>
-__device__ __forceinline__ void ta_softmax(f32x4 (&s)[NT][NT], int n, float scale_log2, float (&inv)[NT], int lane) {
+__device__ __forceinline__ void ta_softmax(f32x4 (&s)[NT][NT], int n, float scale_log2, float (&inv)[NT],
+                                           float (&mb)[NT], int lane) {
   const int g = lane >> 4;
 #pragma unroll
   for (int a = 0; a < NT; ++a)
@@ -240,13 +267,13 @@ __device__ __forceinline__ void ta_softmax(f32x4 (&s)[NT][NT], int n, float scal
       for (int i = 0; i < 4; ++i) mx = fmaxf(mx, s[a][c][i]);
     mx = fmaxf(mx, __shfl_xor(mx, 16));
     mx = fmaxf(mx, __shfl_xor(mx, 32));
-    const float mb = mx * scale_log2;
+    mb[c] = mx * scale_log2;
     float ls = 0.f;
 #pragma unroll
     for (int a = 0; a < NT; ++a)
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const float pv = fast_exp2(s[a][c][i] * scale_log2 - mb);
+        const float pv = fast_exp2(s[a][c][i] * scale_log2 - mb[c]);
         s[a][c][i] = pv;
         ls += pv;
       }
@@ -254,6 +281,11 @@ __device__ __forceinline__ void ta_softmax(f32x4 (&s)[NT][NT], int n, float scal
     ls += __shfl_xor(ls, 32);
     inv[c] = 1.0f / ls;
   }
+}
+template <int NT>
+__device__ __forceinline__ void ta_softmax(f32x4 (&s)[NT][NT], int n, float scale_log2, float (&inv)[NT], int lane) {
+  float mb[NT];
+  ta_softmax<NT>(s, n, scale_log2, inv, mb, lane);
 }
 
 // P^T B operands of O^T = V^T P^T (one 32-key k-step; for NT = 1 the upper 16 keys are zero)
