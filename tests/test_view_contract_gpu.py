@@ -28,7 +28,8 @@ the projections).  Shapes moved from the first choice because an entry point's p
     8-phase conv cases use two 91x91 images (M = 16562 = 129 x 128 + 50) instead of 9x9;
   * the frame-axis attention takes head sizes 8 .. 160, so (nclip, F, HW, C) = (1, 16, 8, 80) runs as two heads of
     40, not eight of 10.
-Outputs a wrapper allocates itself (dx / dgamma / dbeta of the norm backward kernels) get checks 3 and 4 only.
+Outputs a wrapper allocates itself (dx / dgamma / dbeta of the norm backward kernels, the outputs of zero_insert and
+sumpool2x2) get checks 3 and 4 only.
 """
 import contextlib
 import math
@@ -705,6 +706,25 @@ def temporal_bwd_spec(nclip, Fr, HW, C):
     return Spec(ins, {"out": (rows, 3 * C, BF16, "view")}, run, ref, fused={"qkv": ["q", "k", "v"]}, default_tol=BWD)
 
 
+def sampler_dgrad_spec(op, n, h, w, C):
+    """zero_insert / sumpool2x2 (h, w: the small grid): x is addressed as one contiguous block, so it is a slice of a
+    NaN buffer with one image of NaN on each side; the wrappers allocate their outputs."""
+    g = gen(op, n, h, w, C)
+    if op == "zero_insert":
+        x = rnd(n, h, w, C, g=g)
+        run = lambda K, t: {"out": K.zero_insert(t["x"], n, h, w)}
+
+        def ref(i):
+            y = torch.zeros(n, 2 * h, 2 * w, C)
+            y[:, ::2, ::2] = x.float()
+            return {"out": y.reshape(-1, C)}
+    else:
+        x = rnd(n, 2 * h, 2 * w, C, g=g)
+        run = lambda K, t: {"out": K.sumpool2x2(t["x"], n, h, w)}
+        ref = lambda i: {"out": x.float().view(n, h, 2, w, 2, C).sum((2, 4)).reshape(-1, C)}
+    return Spec({"x": (x.reshape(-1, C), "contig")}, {}, run, ref, guard={"x": x[0].numel()})
+
+
 # ---------------------------------------------------------------- the matrix
 CASES = {}
 
@@ -788,6 +808,9 @@ case("spatial_attention_bwd-self", spatial_bwd_spec, 2, 2, 200, 200, 1)
 case("spatial_attention_bwd-cross", spatial_bwd_spec, 2, 2, 100, 77, 2)
 case("temporal_attention_bwd-3x5x7x64", temporal_bwd_spec, 3, 5, 7, 64)
 case("temporal_attention_bwd-1x16x8x80", temporal_bwd_spec, 1, 16, 8, 80)
+for _op in ("zero_insert", "sumpool2x2"):
+    case(f"{_op}-3x5x7x64", sampler_dgrad_spec, _op, 3, 5, 7, 64)
+    case(f"{_op}-2x8x8x320", sampler_dgrad_spec, _op, 2, 8, 8, 320)
 
 
 @pytest.mark.parametrize("cid", list(CASES))

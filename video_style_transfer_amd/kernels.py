@@ -1233,10 +1233,21 @@ def temporal_attention_bwd(q, k, v, dout, nclip, F, HW, heads, head_dim, scale=N
     return out[:, :C], out[:, C:2 * C], out[:, 2 * C:]
 
 
+def _sampler_in(fn, x, rows, what):
+    """The sampler dgrad kernels address x as one contiguous [rows, C] block of 16-byte chunks (no row stride in their
+    ABI): a shorter, strided or misaligned x would be read past its end."""
+    if not x.is_contiguous() or x.shape[0] != rows or rows <= 0:
+        raise _lib.VstError(f"{fn}: x must be contiguous [{what} = {rows}, C], got shape {tuple(x.shape)} stride "
+                            f"{x.stride()}")
+    if x.shape[1] % 8 or x.data_ptr() % 16:
+        raise _lib.VstError(f"{fn}: C = {x.shape[1]} must be a multiple of 8 and x 16-byte aligned")
+
+
 def zero_insert(x, nimg, h, w):
     """[nimg*h*w, C] -> [nimg*2h*2w, C] with x on the even (2i, 2j) pixels, zeros elsewhere."""
     _dev(x, BF16, "x")
     C = x.shape[1]
+    _sampler_in("zero_insert", x, nimg * h * w, "nimg*h*w")
     out = torch.zeros((nimg * 4 * h * w, C), dtype=BF16, device=x.device)
     _lib.call("vst_zero_insert", _p(x), nimg, h, w, C, _p(out), _stream())
     return out
@@ -1246,6 +1257,7 @@ def sumpool2x2(x, nimg, h, w):
     """[nimg*2h*2w, C] -> [nimg*h*w, C], 2x2 block sums (h, w: output size)."""
     _dev(x, BF16, "x")
     C = x.shape[1]
+    _sampler_in("sumpool2x2", x, nimg * 4 * h * w, "nimg*2h*2w")
     out = torch.empty((nimg * h * w, C), dtype=BF16, device=x.device)
     _lib.call("vst_sumpool2x2", _p(x), nimg, h, w, C, _p(out), _stream())
     return out
