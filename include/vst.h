@@ -30,6 +30,7 @@
 #ifndef VST_H
 #define VST_H
 #include <stddef.h>
+#include <stdint.h>
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -444,6 +445,35 @@ int vst_sampler_step(const void* noise, int ncopy, float guidance, float* lat, f
 size_t vst_cfg_rescale_factor_workspace_bytes(int B, int Cl, int F, int HW);
 int vst_cfg_rescale_factor(const void* noise, float guidance, float phi, int B, int Cl, int F, int HW, float* factor,
                            void* workspace, void* stream);
+
+/* ---- Stochastic samplers: counter-based noise on the device and the sampler step that adds it.  No
+ * reference counterpart (its loop is deterministic Euler); the samplers are k-diffusion's Euler ancestral and
+ * DPM-Solver++(2M) SDE and diffusers' LCMScheduler.step, as scheduler.sampler_coefficients restates them.
+ * The noise has no state.  For the element (clip b, channel c, local frame f, pixel p) of a tensor (B, Cl, F, HW) that
+ * holds frames [f0, f0 + F) of clips of F_total frames, with P = ((uint64)b * F_total + f0 + f) * HW + p and
+ * s = *step_idx, seed = *seed both read on the device:
+ *   x0..x3 = Philox4x32-10(counter (lo32 P, hi32 P, s, stream_id << 16 | c >> 2), key (lo32 seed, hi32 seed));
+ *   u_k = ((x_k >> 9) + 0.5) * 2^-23 (exact in fp32, inside (0, 1));
+ *   n0 = r0 cospi(2 u1), n1 = r0 sinpi(2 u1), r0 = sqrt(-2 log u0); n2, n3 likewise from (u2, u3);
+ *   channel c takes lane c & 3.  So a frame shard, or a replayed graph, draws what the whole eager clip draws.
+ *   stream_id 0 is the sampler step's; 1 .. 65535 are free for callers.
+ * vst_noise_bits: out[b][c][f][p] = x[c & 3] (the counter layout, exactly checkable against a host Philox).
+ * vst_noise_normal: out[b][c][f][p] = n[c & 3], the bits vst_sampler_step_noise adds.
+ * vst_sampler_step_noise: vst_sampler_step on coef4 rows (a, b, c, d), with lat' += d xi before the keep-mask blend,
+ *   xi the normal above at stream 0: lat' = a lat + b D + c hist + d xi; hist = D; a kept pixel stays
+ *   z0 + sigmas[s+1] eps.  Where d == 0 xi is neither generated nor added and lat' has vst_sampler_step's bits on
+ *   (a, b, c).  It is one more rule of the one step kernel (csrc/sampler.hip).
+ * Every entry returns 1 before any launch on a NULL pointer, a non-positive size, f0 < 0 or f0 + F > F_total, a
+ * stream_id outside [0, 65535] or Cl above 2^18 (the last counter word holds both); vst_sampler_step_noise also on
+ * what vst_sampler_step refuses. */
+int vst_noise_bits(uint32_t* out, const uint64_t* seed, const int* step_idx, int stream_id, int B, int Cl, int F,
+                   int F_total, int f0, int HW, void* stream);
+int vst_noise_normal(float* out, const uint64_t* seed, const int* step_idx, int stream_id, int B, int Cl, int F,
+                     int F_total, int f0, int HW, void* stream);
+int vst_sampler_step_noise(const void* noise, int ncopy, float guidance, float* lat, float* hist, int B, int Cl, int F,
+                           int F_total, int f0, int HW, const float* sigmas, const float* coef4, const int* step_idx,
+                           const uint64_t* seed, const float* factor, const float* z0, const float* eps,
+                           const float* mask, int mask_clips, void* stream);
 
 /* Ceiling probes (no reference counterpart; bench.py's measured peaks next to the vendor figures,
  * SURVEY §8(d)).  vst_probe_mfma: `grid` workgroups x 8 waves, each wave `iters` x 16 independent

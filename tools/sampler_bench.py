@@ -1,13 +1,17 @@
 """Few-step sampling: what the table-driven sampler step and guidance rescale cost.
 
 Kernel: at (1, 4, 16, 64, 64) fp32 latents with a CFG pair, alternating (device events around `iters` back-to-back
-calls): vst_sampler_step plain and masked, vst_cfg_rescale_factor (both launches), and vst_euler_cfg_step.  Median and
-min..max over the passes.
+calls): vst_sampler_step plain and masked, vst_cfg_rescale_factor (both launches), vst_euler_cfg_step, and the
+stochastic samplers' vst_noise_normal and vst_sampler_step_noise (on a d != 0 row of the
+DPM-Solver++ 2M SDE table, so the noise is generated).  Median and min..max over the passes.
 Step: AnimateDiffDenoiser at the bench workload (16 x 512^2, CFG pair, whole-step HIP graph), three denoisers over one
 UNet, all captured up front and replayed alternately, `--steps` replays per pass:
   euler          the default step (the bench.py path: vst_euler_cfg_step), 50-step table
   dpmpp_2m       sampler="dpmpp_2m" on 20 Karras sigmas (vst_sampler_step)
   dpmpp_2m_resc  the same with guidance_rescale 0.7 (vst_cfg_rescale_factor + vst_sampler_step)
+  dpmpp_2m_sde   sampler="dpmpp_2m_sde", eta 1, on the same sigmas (vst_sampler_step_noise)
+The two stochastic rows are left out when the loaded library does not export their entries (VST_LIB_AB of an older
+build, which the other rows are compared against).
 A step's time does not depend on the length of its table, so steps/s at 20 against 50 steps follows from it.
 Bits (--md5, nothing timed): one JSON line per case with an md5 of lat (and of hist) after one call of each of the
 three step entry points on seeded CPU inputs, over shapes x ncopy x step x mask x mask_clips x factor.  Two builds
@@ -26,10 +30,14 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from video_style_transfer_amd import kernels as K  # noqa: E402
+from video_style_transfer_amd import _lib, kernels as K  # noqa: E402
 
 BF = torch.bfloat16
 FRAMES, SIDE, STEPS, FEW = 16, 512, 50, 20
+
+
+def has_noise_entries():
+    return hasattr(_lib.load(), "vst_sampler_step_noise")
 
 
 def timed(fn, iters):
@@ -69,6 +77,13 @@ def kernel_ab(passes, iters, dev):
                                                            z0=z0, eps=eps, mask=mask),
              "cfg_rescale_factor": lambda: K.cfg_rescale_factor(noise, shape, guidance=7.5, phi=0.7, out=factor,
                                                                 workspace=ws)}
+    if has_noise_entries():
+        coef4 = sampler_coefficients(sch.sigmas, "dpmpp_2m_sde").float().to(dev)
+        seed = torch.full((1,), 42, dtype=torch.int64, device=dev)
+        xi = torch.empty(shape, device=dev)
+        sides["noise_normal"] = lambda: K.noise_normal(seed, step, shape, out=xi)
+        sides["sampler_step_noise"] = lambda: K.sampler_step_noise(noise, lat, hist, sig, coef4, step, seed,
+                                                                   guidance=7.5, ncopy=2)
     for fn in sides.values():
         fn(), fn()
     t = {s: [] for s in sides}
@@ -173,6 +188,8 @@ def main():
         unet = build_unet(seed=0, lora_rank=8, device=dev)
         dens = {"euler": make_denoiser(unet, dev), "dpmpp_2m": make_denoiser(unet, dev, sampler="dpmpp_2m"),
                 "dpmpp_2m_resc": make_denoiser(unet, dev, sampler="dpmpp_2m", guidance_rescale=0.7)}
+        if has_noise_entries():
+            dens["dpmpp_2m_sde"] = make_denoiser(unet, dev, sampler="dpmpp_2m_sde")
         for den in dens.values():
             den.init_latents(seed=42)
             den.run_steps(a.warmup)
@@ -187,6 +204,8 @@ def main():
         summary(rec, t, "step_ms", 1.0, 2)
         rec["dpmpp_2m_minus_euler_ms"] = round(rec["dpmpp_2m_step_ms"] - rec["euler_step_ms"], 2)
         rec["rescale_minus_dpmpp_2m_ms"] = round(rec["dpmpp_2m_resc_step_ms"] - rec["dpmpp_2m_step_ms"], 2)
+        if "dpmpp_2m_sde" in dens:
+            rec["sde_minus_dpmpp_2m_ms"] = round(rec["dpmpp_2m_sde_step_ms"] - rec["dpmpp_2m_step_ms"], 2)
         # derived from the step times, not a measured run: frames per second of a whole denoise
         rec["derived_frames_per_s"] = {f"euler_{STEPS}_steps": round(FRAMES / (STEPS * rec["euler_step_ms"] * 1e-3), 3),
                                        f"dpmpp_2m_{FEW}_steps": round(FRAMES / (FEW * rec["dpmpp_2m_step_ms"] * 1e-3), 3)}

@@ -103,6 +103,10 @@ SIGNATURES = {
     "vst_sampler_step": (_I, [_P, _I, _F, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     "vst_cfg_rescale_factor_workspace_bytes": (_S, [_I, _I, _I, _I]),
     "vst_cfg_rescale_factor": (_I, [_P, _F, _F, _I, _I, _I, _I, _P, _P, _P]),
+    "vst_noise_bits": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "vst_noise_normal": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "vst_sampler_step_noise": (_I, [_P, _I, _F, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I,
+                                    _P]),
     "vst_probe_mfma": (_I, [_I, _I, _P, _P]),
     "vst_probe_hbm_read": (_I, [_P, _S, _I, _P, _P]),
     "vst_probe_fetch": (_I, [_I, _P, _I, _I, _I, _P, _P]),

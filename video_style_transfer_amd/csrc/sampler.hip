@@ -1,21 +1,26 @@
 // The update of the denoise loop: one fused step kernel for the Euler step, the Euler step with a
 // per-pixel keep mask and the table-driven samplers (Euler and DPM-Solver++ 2M on the denoised estimate), and the
 // per-clip factor of guidance rescale.  Every per-step scalar is read through the device step counter, so one captured
-// step replays for the whole schedule.
+// step replays for the whole schedule.  The stochastic samplers are one more rule of that kernel: their
+// fresh noise is counter-based (philox.h), a function of the device seed and step, so the captured step still replays.
+#include "philox.h"
 #include "vst_common.h"
 
 namespace vst {
 
 // What differs between the steps.  A rule is a kernel argument: the host sets its pointers, load() fills the per-step
-// scalars on the device, update() gives lat' for one element (li indexes lat and every tensor of its shape) and
-// renoise() the value of a kept pixel.  Each rule's expressions decide its rounding (where the compiler may contract
+// scalars on the device for the thread's pixel (clip b, local frame f, pixel p of HW), update() gives lat' for the
+// element of channel k (li indexes lat and every tensor of its shape; the channels come in order) and renoise() the
+// value of a kept pixel.  Each rule's expressions decide its rounding (where the compiler may contract
 // a * b + c into one FMA), so they change only with the bits.
 
 // lat' = lat + (sigma[s+1] - sigma[s]) e  (EulerDiscreteScheduler.step, epsilon prediction)
 struct EulerRule {
   float ds;
-  __device__ __forceinline__ void load(const float* sigmas, int s, int) { ds = sigmas[s + 1] - sigmas[s]; }
-  __device__ __forceinline__ float update(float x, float e, size_t) const { return x + ds * e; }
+  __device__ __forceinline__ void load(const float* sigmas, int s, int, int, int, int) {
+    ds = sigmas[s + 1] - sigmas[s];
+  }
+  __device__ __forceinline__ float update(float x, float e, size_t, int) const { return x + ds * e; }
   static __device__ __forceinline__ float renoise(float z0, float s1, float eps) { return z0 + s1 * eps; }
 };
 
@@ -26,12 +31,13 @@ struct TableRule {
   const float* coef;
   const float* factor;  // per clip, or nullptr
   float sg, ca, cb, cc, fac;
-  __device__ __forceinline__ void load(const float* sigmas, int s, int b) {
+  __device__ __forceinline__ void load_row(const float* sigmas, int s, int b, int cols) {
     sg = sigmas[s];
-    ca = coef[3 * s], cb = coef[3 * s + 1], cc = coef[3 * s + 2];
+    ca = coef[cols * s], cb = coef[cols * s + 1], cc = coef[cols * s + 2];
     fac = factor ? factor[b] : 1.0f;
   }
-  __device__ __forceinline__ float update(float x, float e, size_t li) const {
+  __device__ __forceinline__ void load(const float* sigmas, int s, int b, int, int, int) { load_row(sigmas, s, b, 3); }
+  __device__ __forceinline__ float update(float x, float e, size_t li, int) const {
     const bool use_hist = cc != 0.0f;
     if (factor) e *= fac;
     const float D = x - sg * e;
@@ -47,6 +53,35 @@ struct TableRule {
 #pragma clang fp contract(off)
     const float t = s1 * eps;
     return z0 + t;
+  }
+};
+
+// coef rows are (a, b, c, d):  TableRule's step, then lat' += d xi, xi the standard normal of philox.h at
+// (*seed, s, stream 0, the element's place in the whole clip: this tensor holds frames [f0, f0 + F) of F_total).
+// Where d == 0 xi is neither generated nor added, so lat' has TableRule's bits.  One Philox call serves 4 channels.
+struct NoiseRule : TableRule {
+  const uint64_t* seed;
+  int F_total, f0;
+  float cd;
+  uint64_t key, pos;
+  uint32_t step;
+  float xi[4];
+  __device__ __forceinline__ void load(const float* sigmas, int s, int b, int f, int p, int HW) {
+    load_row(sigmas, s, b, 4);
+    cd = coef[4 * s + 3];
+    key = *seed;
+    pos = noise_position(b, F_total, f0 + f, HW, p);
+    step = (uint32_t)s;
+  }
+  __device__ __forceinline__ float update(float x, float e, size_t li, int k) {
+    float ln = TableRule::update(x, e, li, k);
+    if (cd != 0.0f) {
+      const int lane = k & 3;
+      if (lane == 0) noise_normal4(key, pos, step, 0u, (uint32_t)k >> 2, xi);
+      const float n = lane == 0 ? xi[0] : lane == 1 ? xi[1] : lane == 2 ? xi[2] : xi[3];  // no indexed register array
+      ln += cd * n;
+    }
+    return ln;
   }
 };
 
@@ -76,7 +111,7 @@ __global__ __launch_bounds__(256) void denoise_step_kernel(const bf16_t* __restr
   const int f = (int)(bf % F);
   const int b = (int)(bf / F);
   const int s = *step;
-  rule.load(sigmas, s, b);
+  rule.load(sigmas, s, b, f, p, HW);
   float s1 = 0.0f, m = 1.0f, keep = 0.0f;
   if (MASKED) {
     s1 = sigmas[s + 1];
@@ -88,8 +123,8 @@ __global__ __launch_bounds__(256) void denoise_step_kernel(const bf16_t* __restr
   const bf16_t* nu = noise + t * Cl;           // uncond (or the only) row
   const bf16_t* nc = noise + (npix + t) * Cl;  // cond row (ncopy == 2)
 
-  auto update = [&](float e) {
-    float ln = rule.update(lat[li], e, li);
+  auto update = [&](float e, int k) {
+    float ln = rule.update(lat[li], e, li, k);
     if (MASKED) ln = m * ln + keep * Rule::renoise(z0[li], s1, eps[li]);
     lat[li] = ln;
   };
@@ -105,13 +140,46 @@ __global__ __launch_bounds__(256) void denoise_step_kernel(const bf16_t* __restr
       for (int k = 0; k < 4; ++k) e[k] = cfg_mix(e[k], c[k], guidance);
     }
 #pragma unroll
-    for (int k = 0; k < 4; ++k, li += plane) update(e[k]);
+    for (int k = 0; k < 4; ++k, li += plane) update(e[k], k);
   } else {
     for (int k = 0; k < Cl; ++k, li += plane) {
       float e = bf2f(nu[k]);
       if (ncopy == 2) e = cfg_mix(e, bf2f(nc[k]), guidance);
-      update(e);
+      update(e, k);
     }
+  }
+}
+
+// The noise alone, one thread per pixel as the step walks it: out (B, Cl, F, HW) holds, per element, the Philox word
+// of its channel (NORMAL false: the counter layout, checked exactly) or the normal the step adds (NORMAL true).
+template <bool NORMAL>
+__global__ __launch_bounds__(256) void noise_fill_kernel(uint32_t* __restrict__ out, const uint64_t* __restrict__ seed,
+                                                         const int* __restrict__ step, uint32_t stream_id, int B,
+                                                         int Cl, int F, int F_total, int f0, int HW) {
+  const size_t npix = (size_t)B * F * HW;
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= npix) return;
+  const int p = (int)(t % HW);
+  const size_t bf = t / HW;
+  const int f = (int)(bf % F);
+  const int b = (int)(bf / F);
+  const uint64_t key = *seed;
+  const uint32_t s = (uint32_t)*step;
+  const uint64_t pos = noise_position(b, F_total, f0 + f, HW, p);
+  const size_t plane = (size_t)F * HW;
+  size_t li = ((size_t)b * Cl * F + f) * HW + p;
+  for (int k0 = 0; k0 < Cl; k0 += 4) {
+    uint32_t x[4];
+    noise_bits4(key, pos, s, stream_id, (uint32_t)k0 >> 2, x);
+    if (NORMAL) {
+      float n[4];
+      normals_of_bits4(x, n);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) x[j] = __float_as_uint(n[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j, li += plane)
+      if (k0 + j < Cl) out[li] = x[j];
   }
 }
 
@@ -299,6 +367,48 @@ extern "C" int vst_sampler_step(const void* noise, int ncopy, float guidance, fl
   if (factor && ncopy != 2) return VST_ERR_ARG;  // the rescale factor is defined on the CFG pair
   return launch_step({noise, ncopy, guidance, lat, B, Cl, F, HW, sigmas, step_idx, z0, eps, mask, mask_clips, stream},
                      TableRule{hist, coef, factor});
+}
+
+// What every noise entry refuses: the frames [f0, f0 + F) must lie in the clip, and the counter's last word holds the
+// stream in its upper and the channel group (Cl / 4 of them) in its lower 16 bits.
+static bool noise_args_ok(const void* seed, int stream_id, int Cl, int F, int F_total, int f0) {
+  return seed && stream_id >= 0 && stream_id < (1 << 16) && Cl <= (1 << 18) && F > 0 && F_total > 0 && f0 >= 0 &&
+         F <= F_total - f0;
+}
+
+extern "C" int vst_sampler_step_noise(const void* noise, int ncopy, float guidance, float* lat, float* hist, int B,
+                                      int Cl, int F, int F_total, int f0, int HW, const float* sigmas,
+                                      const float* coef4, const int* step_idx, const uint64_t* seed,
+                                      const float* factor, const float* z0, const float* eps, const float* mask,
+                                      int mask_clips, void* stream) {
+  if (!hist || !coef4 || lat == hist) return VST_ERR_ARG;
+  if (!mask && (z0 || eps)) return VST_ERR_ARG;
+  if (factor && ncopy != 2) return VST_ERR_ARG;
+  if (!noise_args_ok(seed, 0, Cl, F, F_total, f0)) return VST_ERR_ARG;
+  NoiseRule rule{{hist, coef4, factor}, seed, F_total, f0};
+  return launch_step({noise, ncopy, guidance, lat, B, Cl, F, HW, sigmas, step_idx, z0, eps, mask, mask_clips, stream},
+                     rule);
+}
+
+template <bool NORMAL>
+static int launch_noise_fill(void* out, const uint64_t* seed, const int* step_idx, int stream_id, int B, int Cl, int F,
+                             int F_total, int f0, int HW, void* stream) {
+  if (!out || !step_idx || B <= 0 || Cl <= 0 || HW <= 0) return VST_ERR_ARG;
+  if (!noise_args_ok(seed, stream_id, Cl, F, F_total, f0)) return VST_ERR_ARG;
+  const size_t npix = (size_t)B * F * HW;
+  hipLaunchKernelGGL(noise_fill_kernel<NORMAL>, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (uint32_t*)out, seed, step_idx, (uint32_t)stream_id, B, Cl, F, F_total, f0, HW);
+  return launch_status();
+}
+
+extern "C" int vst_noise_bits(uint32_t* out, const uint64_t* seed, const int* step_idx, int stream_id, int B, int Cl,
+                              int F, int F_total, int f0, int HW, void* stream) {
+  return launch_noise_fill<false>(out, seed, step_idx, stream_id, B, Cl, F, F_total, f0, HW, stream);
+}
+
+extern "C" int vst_noise_normal(float* out, const uint64_t* seed, const int* step_idx, int stream_id, int B, int Cl,
+                                int F, int F_total, int f0, int HW, void* stream) {
+  return launch_noise_fill<true>(out, seed, step_idx, stream_id, B, Cl, F, F_total, f0, HW, stream);
 }
 
 extern "C" size_t vst_cfg_rescale_factor_workspace_bytes(int B, int Cl, int F, int HW) {

@@ -1387,6 +1387,71 @@ def sampler_step(noise, lat, hist, sigmas, coef, step_idx, *, guidance=7.5, ncop
               _p(coef), _p(step_idx), _p(factor), _p(z0), _p(eps), _p(mask), mask_clips, _stream())
 
 
+# ---- stochastic samplers: counter-based noise and the step that adds it (pipeline._step) ----
+def _noise_operands(seed, step_idx, stream_id, shape, F_total, f0, fn):
+    """What every noise entry takes: the device seed (int64 [1], read as the uint64 of its bits) and step counter, a
+    stream below 2^16, and a (B, Cl, F, H, W) shape holding frames [f0, f0 + F) of F_total.  Returns F_total."""
+    _flat(seed, torch.int64, (1,), "seed", fn)
+    _flat(step_idx, torch.int32, (1,), "step_idx", fn)
+    if len(shape) != 5 or min(shape) <= 0:
+        raise _lib.VstError(f"{fn}: shape {tuple(shape)} must be (B, Cl, F, H, W), all positive")
+    F_total = shape[2] if F_total is None else int(F_total)
+    if not 0 <= int(stream_id) < 1 << 16 or shape[1] > 1 << 18:
+        raise _lib.VstError(f"{fn}: stream_id {stream_id} must be in [0, 65535] and Cl {shape[1]} at most 2^18")
+    if f0 < 0 or f0 + shape[2] > F_total:
+        raise _lib.VstError(f"{fn}: frames [{f0}, {f0 + shape[2]}) outside the clip's {F_total}")
+    return F_total
+
+
+def _noise_fill(entry, dtype, seed, step_idx, shape, stream_id, F_total, f0, out):
+    fn = entry[4:]
+    shape = tuple(int(v) for v in shape)
+    F_total = _noise_operands(seed, step_idx, stream_id, shape, F_total, f0, fn)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=seed.device)
+    _flat(out, dtype, shape, "out", fn)
+    B, Cl, F, H, W = shape
+    _lib.call(entry, _p(out), _p(seed), _p(step_idx), int(stream_id), B, Cl, F, F_total, int(f0), H * W, _stream())
+    return out
+
+
+def noise_bits(seed, step_idx, shape, *, stream_id=0, F_total=None, f0=0, out=None):
+    """The Philox4x32-10 word of every element of a (B, Cl, F, H, W) tensor holding frames [f0, f0 + F) of clips of
+    F_total frames (default F), as int32 bit patterns (view them as torch.uint32): scheduler.noise_reference's bits."""
+    return _noise_fill("vst_noise_bits", torch.int32, seed, step_idx, shape, stream_id, F_total, f0, out)
+
+
+def noise_normal(seed, step_idx, shape, *, stream_id=0, F_total=None, f0=0, out=None):
+    """fp32 standard normals of the same counters (Box-Muller on the words); stream_id 0 at step s is what
+    sampler_step_noise adds at step s."""
+    return _noise_fill("vst_noise_normal", F32, seed, step_idx, shape, stream_id, F_total, f0, out)
+
+
+def sampler_step_noise(noise, lat, hist, sigmas, coef, step_idx, seed, *, F_total=None, f0=0, guidance=7.5, ncopy=2,
+                       factor=None, z0=None, eps=None, mask=None):
+    """sampler_step on coef rows (a, b, c, d) (scheduler.sampler_coefficients of a stochastic sampler, fp32 [n, 4]):
+    lat = a * lat + b * D + c * hist + d * xi, xi = noise_normal(seed, step_idx, lat.shape, F_total=, f0=) generated in
+    the kernel; the keep-mask blend follows.  Where d == 0 no noise is generated and lat has sampler_step's bits."""
+    fn = "sampler_step_noise"
+    B, Cl, F, H, W = _step_operands(noise, lat, sigmas, step_idx, ncopy, fn)
+    _flat(hist, F32, lat.shape, "hist", fn)
+    if hist.data_ptr() == lat.data_ptr():
+        raise _lib.VstError(f"{fn}: hist must not be lat")
+    _flat(coef, F32, (sigmas.numel() - 1, 4), "coef", fn)
+    F_total = _noise_operands(seed, step_idx, 0, tuple(lat.shape), F_total, f0, fn)
+    if factor is not None:
+        _flat(factor, F32, (B,), "factor", fn)
+        if ncopy != 2:
+            raise _lib.VstError(f"{fn}: a rescale factor needs both CFG branches (ncopy 2)")
+    given = [t is not None for t in (z0, eps, mask)]
+    if any(given) and not all(given):
+        raise _lib.VstError(f"{fn}: z0, eps and mask go together")
+    mask_clips = _keep_mask(lat, z0, eps, mask, fn) if mask is not None else 0
+    _lib.call("vst_sampler_step_noise", _p(noise), ncopy, float(guidance), _p(lat), _p(hist), B, Cl, F, F_total,
+              int(f0), H * W, _p(sigmas), _p(coef), _p(step_idx), _p(seed), _p(factor), _p(z0), _p(eps), _p(mask),
+              mask_clips, _stream())
+
+
 def cfg_rescale_workspace(lat_shape, device):
     """The fp32 workspace cfg_rescale_factor needs for latents of this (B, Cl, F, H, W) shape."""
     B, Cl, F, H, W = lat_shape

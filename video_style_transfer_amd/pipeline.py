@@ -13,6 +13,9 @@ is captured once into a HIP graph and replayed for all 50 steps (no per-launch h
 Latents stay fp32 on the device (the reference keeps them in the UNet dtype between steps).
 With sampler="dpmpp_2m" or guidance_rescale > 0 the update is vst_sampler_step instead, after
 vst_cfg_rescale_factor when rescaling: its coefficients, its history and the rescale factor live on the device too.
+The stochastic samplers ("euler_a", "dpmpp_2m_sde", "lcm") step with vst_sampler_step_noise: the fresh
+noise of every step is counter-based, a function of a device seed and the device step counter, so the captured step
+still replays unchanged.
 """
 from __future__ import annotations
 
@@ -25,17 +28,23 @@ import torch
 from . import kernels as K
 from .attention_processor import refresh_text_kv
 from .lora_gate import LoraGate
-from .scheduler import SAMPLERS, EulerDiscreteScheduler, sampler_coefficients, start_index
+from .scheduler import (SAMPLERS, STOCHASTIC_SAMPLERS, EulerDiscreteScheduler, check_eta, sampler_coefficients,
+                        start_index)
 from .unet_motion import TemporalContext, UNetMotionModel, as_cross_frame, check_clip_length, check_cross_frame
 
 BF16 = torch.bfloat16
 
 
-def check_sampler(sampler, guidance_scale, guidance_rescale, shard=None) -> float:
+def check_sampler(sampler, guidance_scale, guidance_rescale, shard=None, eta=1.0, scheduler=None) -> float:
     """The sampler arguments of AnimateDiffDenoiser, refused here before anything is allocated.  Returns
-    guidance_rescale as a float."""
+    guidance_rescale as a float.  `eta` must be finite and >= 0; "lcm" steps on the LCM timesteps, so a `scheduler`
+    given with it must have timestep_spacing "lcm"."""
     if sampler not in SAMPLERS:
         raise ValueError(f"sampler {sampler!r}: one of {SAMPLERS}")
+    check_eta(eta)
+    if sampler == "lcm" and scheduler is not None and scheduler.timestep_spacing != "lcm":
+        raise ValueError(f"sampler 'lcm' needs EulerDiscreteScheduler(timestep_spacing='lcm'), got spacing "
+                         f"{scheduler.timestep_spacing!r}")
     try:
         phi = float(guidance_rescale)
     except (TypeError, ValueError):
@@ -58,7 +67,7 @@ class AnimateDiffDenoiser:
                  scheduler: Optional[EulerDiscreteScheduler] = None, use_graph: bool = True, shard=None,
                  num_clips: int = 1, context_length: Optional[int] = None, context_stride: int = 4,
                  context_weighting: str = "pyramid", cross_frame=None, sampler: str = "euler",
-                 guidance_rescale: float = 0.0):
+                 guidance_rescale: float = 0.0, eta: float = 1.0):
         """`num_clips` clips are denoised together (the reference loop is one clip, B=1).
         `shard` (frame_shard.FrameShard): this process denoises frames [f0, f0 + F/P) of every clip and
         exchanges with the other ranks inside every motion module.
@@ -73,9 +82,18 @@ class AnimateDiffDenoiser:
         `sampler` "euler" or "dpmpp_2m" (second-order multistep, DPM-Solver++ 2M; meant for 20-25 steps on
         EulerDiscreteScheduler(sigma_schedule="karras")) and `guidance_rescale` in [0, 1] (rescale_noise_cfg of the
         reference's pipeline; needs CFG and whole clips on this rank) are fixed at construction.
-        With "euler" and 0 the step is the one it always was."""
-        self.guidance_rescale = check_sampler(sampler, guidance_scale, guidance_rescale, shard)
+        With "euler" and 0 the step is the one it always was.
+        `sampler` "euler_a", "dpmpp_2m_sde" or "lcm"  adds fresh noise at every step, scaled by `eta`
+        (finite, >= 0; 0 is the deterministic sampler; "lcm" ignores it).  The noise is a function of the noise seed
+        (set_noise_seed, or the `seed` of a call), the step and the element's place in the whole clip, so a frame
+        shard draws what the whole clip draws.  "lcm" (4-8 steps, guidance_scale 1) needs a scheduler with
+        timestep_spacing "lcm" and builds one when none is given."""
+        self.guidance_rescale = check_sampler(sampler, guidance_scale, guidance_rescale, shard, eta, scheduler)
+        if unet is None:  # refused with the other arguments, before anything is allocated
+            raise ValueError("AnimateDiffDenoiser needs a UNetMotionModel, got None")
         self.sampler = sampler
+        self.eta = float(eta)
+        self.noise_step = sampler in STOCHASTIC_SAMPLERS
         self.context = None if context_length is None else TemporalContext(int(context_length), int(context_stride),
                                                                            context_weighting)
         if unet.config.motion_modules:
@@ -93,7 +111,8 @@ class AnimateDiffDenoiser:
         self.cfg = guidance_scale > 1.0
         self.ncopy = 2 if self.cfg else 1
         self.device = torch.device(device or "cuda")
-        self.scheduler = scheduler or EulerDiscreteScheduler()
+        self.scheduler = scheduler or EulerDiscreteScheduler(**({"timestep_spacing": "lcm"} if sampler == "lcm"
+                                                                else {}))
         self.scheduler.set_timesteps(num_inference_steps, device=self.device)
         self.num_steps = num_inference_steps
         self.use_graph = use_graph
@@ -117,12 +136,15 @@ class AnimateDiffDenoiser:
         # per-frame content / style strength (set_lora_gates): None = the plain step
         self.lora_gate = None
         # table-driven sampler step: the previous step's denoised estimate, the (a, b, c) rows, the
-        # per-clip rescale factor and its workspace; allocated here once, a captured step holds their pointers
+        # per-clip rescale factor and its workspace; allocated here once, a captured step holds their pointers.  A
+        # stochastic sampler (§16) has (a, b, c, d) rows and the seed of its noise, rewritten in place.
         self.table_step = sampler != "euler" or self.guidance_rescale > 0.0
-        self.hist = self.coef = self.factor = self.rescale_ws = None
+        self.hist = self.coef = self.factor = self.rescale_ws = self.noise_seed = None
         if self.table_step:
             self.hist = torch.zeros_like(self.lat)
-            self.coef = torch.empty(num_inference_steps, 3, dtype=torch.float32, device=dev)
+            self.coef = torch.empty(num_inference_steps, 4 if self.noise_step else 3, dtype=torch.float32, device=dev)
+            if self.noise_step:
+                self.noise_seed = torch.zeros(1, dtype=torch.int64, device=dev)
             self._write_coef(0)
             if self.guidance_rescale > 0.0:
                 self.factor = torch.ones(num_clips, dtype=torch.float32, device=dev)
@@ -162,8 +184,12 @@ class AnimateDiffDenoiser:
                 K.cfg_rescale_factor(noise, self.lat.shape, guidance=self.guidance, phi=self.guidance_rescale,
                                      out=self.factor, workspace=self.rescale_ws)
             src, eps, mask = (self.src, self.eps, self.mask) if self.masked else (None, None, None)
-            K.sampler_step(noise, self.lat, self.hist, self.sigmas, self.coef, self.step_idx, guidance=self.guidance,
-                           ncopy=self.ncopy, factor=self.factor, z0=src, eps=eps, mask=mask)
+            kw = dict(guidance=self.guidance, ncopy=self.ncopy, factor=self.factor, z0=src, eps=eps, mask=mask)
+            if self.noise_step:
+                K.sampler_step_noise(noise, self.lat, self.hist, self.sigmas, self.coef, self.step_idx,
+                                     self.noise_seed, F_total=self.F_total, f0=self.f0, **kw)
+            else:
+                K.sampler_step(noise, self.lat, self.hist, self.sigmas, self.coef, self.step_idx, **kw)
         elif self.masked:
             K.euler_cfg_step_masked(noise, self.lat, self.sigmas, self.step_idx, self.src, self.eps, self.mask,
                                     guidance=self.guidance, ncopy=self.ncopy)
@@ -202,7 +228,17 @@ class AnimateDiffDenoiser:
     def _write_coef(self, first_step: int):
         """Rewrite the coefficient table in place for a run entered at `first_step` (first order there: no history)."""
         if self.coef is not None:
-            self.coef.copy_(sampler_coefficients(self.scheduler.sigmas, self.sampler, first_step).to(torch.float32))
+            self.coef.copy_(sampler_coefficients(self.scheduler.sigmas, self.sampler, first_step, self.eta,
+                                                 self.scheduler.timesteps).to(torch.float32))
+
+    def set_noise_seed(self, seed: int):
+        """The seed of a stochastic sampler's step noise (any integer, taken modulo 2^64), written in place on the
+        device: a captured step replays with the new seed.  The noise has no other state, so the same seed from the
+        same latents is the same run."""
+        if self.noise_seed is None:
+            raise ValueError(f"sampler {self.sampler!r} adds no noise: one of {STOCHASTIC_SAMPLERS} takes a seed")
+        v = int(seed) & (2 ** 64 - 1)
+        self.noise_seed.fill_(v - 2 ** 64 if v >= 2 ** 63 else v)  # the same 64 bits as an int64
 
     def _set_masked(self, on: bool):
         if on != self.masked:  # another Euler kernel: the captured step no longer fits
@@ -341,7 +377,9 @@ class AnimateDiffDenoiser:
                  content_scale=None, style_scale=None):
         """Plain run from `latents` (or from noise drawn with `seed`), or, with `source` and `strength` (and an
         optional keep `mask`), a video-to-video run (set_source).  `content_scale` / `style_scale`: set_lora_gates
-        for this and later runs (the one not given is 1)."""
+        for this and later runs (the one not given is 1).  `seed` is also the noise seed of a stochastic sampler."""
+        if self.noise_seed is not None:
+            self.set_noise_seed(seed)
         if content_scale is not None or style_scale is not None:
             self.set_lora_gates(1.0 if content_scale is None else content_scale,
                                 1.0 if style_scale is None else style_scale)
