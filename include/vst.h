@@ -475,6 +475,24 @@ int vst_sampler_step_noise(const void* noise, int ncopy, float guidance, float* 
                            const uint64_t* seed, const float* factor, const float* z0, const float* eps,
                            const float* mask, int mask_clips, void* stream);
 
+/* ---- FreeU in the up path: diffusers' apply_freeu, which the reference's up blocks call before each
+ * skip concatenation of their first two stages (animatediff/unet_block.py:399-417,
+ * unziplora_unet/unet_block.py:853-867), as one launch over NHWC bf16 rows [nimg * H * W, C].
+ *   x_out[:, :Cx/2] = bf16(float(x) * b), x_out[:, Cx/2:] = x bit for bit;
+ *   skip_out = bf16(fourier_filter(float(skip), threshold 1, scale s)) per (image, channel) map, in closed form: with
+ *     th = 2 pi h / H, ph = 2 pi w / W and the seven sums m0 = S x, a = S x cos th, b = S x sin th, c = S x cos ph,
+ *     d = S x sin ph, e = S x cos(th + ph), f = S x sin(th + ph) over the map,
+ *     y = x + (s - 1) / (H W) (m0 + a cos th + b sin th + c cos ph + d sin ph + e cos(th + ph) + f sin(th + ph)),
+ *     sums and correction in fp32, one rounding at the store.  s == 1 stores the skip's bits.
+ *   (s, b) = table[2 * stage], table[2 * stage + 1]: fp32 [2][2] read on the device, so new values replay a captured
+ *   step.  A map's bits depend on that map and on (H, W) only, never on nimg or on the other maps of the batch.
+ * x_out may be x itself (same pointer and row stride: the scale runs in place); skip_out may overlap no operand.  Row
+ * strides >= channels; bases and strides 16-byte aligned; nothing outside the views is written.
+ * Returns 1 before any launch on a NULL pointer, H < 2 or W < 2 (the mask slice of the definition is empty or wraps),
+ * Cs % 8, Cx % 16, a stage outside {0, 1}, a stride or alignment as above, or an overlap; 3 for H + W > 4096. */
+int vst_freeu(const void* x, int ldx, int Cx, const void* skip, int lds, int Cs, void* x_out, int ldxo,
+              void* skip_out, int ldso, int nimg, int H, int W, const float* table, int stage, void* stream);
+
 /* Ceiling probes (no reference counterpart; bench.py's measured peaks next to the vendor figures,
  * SURVEY §8(d)).  vst_probe_mfma: `grid` workgroups x 8 waves, each wave `iters` x 16 independent
  * 16x16x32 bf16 MFMAs (flops = grid*8*iters*16*16384).  vst_probe_hbm_read: streams `bytes` of `src`

@@ -107,6 +107,7 @@ SIGNATURES = {
     "vst_noise_normal": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "vst_sampler_step_noise": (_I, [_P, _I, _F, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I,
                                     _P]),
+    "vst_freeu": (_I, [_P, _I, _I, _P, _I, _I, _P, _I, _P, _I, _I, _I, _I, _P, _I, _P]),
     "vst_probe_mfma": (_I, [_I, _I, _P, _P]),
     "vst_probe_hbm_read": (_I, [_P, _S, _I, _P, _P]),
     "vst_probe_fetch": (_I, [_I, _P, _I, _I, _I, _P, _P]),

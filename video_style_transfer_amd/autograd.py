@@ -489,6 +489,14 @@ def refuse_context(temporal_context, F: int):
                                   "context_length frames")
 
 
+def refuse_freeu(unet, freeu=None):
+    """FreeU (freeu.FreeU) is inference only: its filter has no backward pass.  A training forward
+    with one given, or with unet.enable_freeu in force, is refused before any launch."""
+    if freeu is not None or getattr(unet, "freeu", None) is not None:
+        raise NotImplementedError("training with freeu: FreeU is inference only (no backward pass); call "
+                                  "unet.disable_freeu() / pass freeu=None")
+
+
 def motion_module_train(mm, x2d, nclip: int, F: int, HW: int, temporal_context=None):
     """Forward of a motion module (unet_motion.MotionModule = diffusers AnimateDiffTransformer3D) built from the
     autograd Functions above, so loss.backward() runs the whole module backward on HIP kernels: GroupNorm over the
@@ -631,13 +639,14 @@ class SpatialAttentionFn(torch.autograd.Function):
 
 
 def unet_train_tokens(unet, x, B: int, F: int, h: int, w: int, emb_silu, enc2d, scale: float = 1.0,
-                      temporal_context=None):
+                      temporal_context=None, freeu=None):
     """UNetMotionModel.forward_tokens (unet_motion.py) on the autograd Functions: the training forward of
     train_animatediff.py:265-273 whose loss.backward() runs on HIP kernels end to end — frozen spatial path (convs,
     ResnetBlock2D, Transformer2DModel with UnZipLoRA) dX only, motion modules with their trainable parameters.
     x: [B*F*h*w, in] bf16 tokens of the noisy latents; emb_silu: SiLU(time + add embedding) [B, T] (constant);
     enc2d: [B*L, D] text states (constant)."""
     refuse_context(temporal_context, F)
+    refuse_freeu(unet, freeu)
     temb = unet.batched_temb(emb_silu)
     nimg = B * F
     H, W = h, w

@@ -1292,6 +1292,37 @@ def step_advance(step_idx, num_steps):
     _lib.call("vst_step_advance", _p(step_idx), int(num_steps), _stream())
 
 
+# ---- FreeU in the up path (freeu.FreeU) ----
+def freeu(x, skip, nimg, H, W, table, stage, *, x_out=None, skip_out=None):
+    """diffusers' apply_freeu on token rows (vst_freeu): x [nimg*H*W, Cx] and skip [nimg*H*W, Cs] bf16 ->
+    (x_out, skip_out) with x_out[:, :Cx/2] = bf16(x * b), the rest x's bits, and skip_out the skip with the four lowest
+    frequency bins of every (image, channel) map scaled by s; (s, b) = table[stage], fp32 [2, 2] on the device (read
+    there: new values replay a captured step).  x_out may be x (in place); skip_out must not overlap skip.  The
+    filtered skip is a new tensor to the GroupNorm that follows: no column statistics are registered for it, so
+    group_norm_stats computes them."""
+    _dev(x, BF16, "x")
+    _dev(skip, BF16, "skip")
+    rows = nimg * H * W
+    if x.shape[0] != rows or skip.shape[0] != rows:
+        raise _lib.VstError(f"freeu: x {tuple(x.shape)} / skip {tuple(skip.shape)} rows, expected nimg*H*W = {rows}")
+    if not isinstance(table, torch.Tensor) or not table.is_cuda or table.dtype != F32 or tuple(table.shape) != (2, 2) \
+            or not table.is_contiguous():
+        raise _lib.VstError("freeu: table must be a contiguous fp32 [2, 2] device tensor ((s, b) per stage)")
+    Cx, Cs = x.shape[1], skip.shape[1]
+    if x_out is None:
+        x_out = torch.empty((rows, Cx), dtype=BF16, device=x.device)
+    if skip_out is None:
+        skip_out = torch.empty((rows, Cs), dtype=BF16, device=x.device)
+    _out(x_out, (rows, Cx), BF16, "x_out", "freeu")
+    _out(skip_out, (rows, Cs), BF16, "skip_out", "freeu")
+    inplace = x_out.data_ptr() == x.data_ptr()
+    nbytes = 4.0 * rows * Cs + 2.0 * rows * (Cx if inplace else 2 * Cx)
+    with _Rec("freeu", 28.0 * rows * Cs, nbytes, lambda: "freeu_kernel", (rows, Cs, Cx)):
+        _lib.call("vst_freeu", _p(x), _ld(x), Cx, _p(skip), _ld(skip), Cs, _p(x_out), _ld(x_out), _p(skip_out),
+                  _ld(skip_out), nimg, H, W, _p(table), int(stage), _stream())
+    return x_out, skip_out
+
+
 # ---- video-to-video: start latents from a source clip, the masked Euler step (pipeline.set_source, DESIGN.md §13) ----
 def _flat(t, dtype, shape, name, fn):
     """Validate a tensor a kernel addresses as one contiguous block: on the device, `dtype`, contiguous, `shape`

@@ -27,6 +27,7 @@ import torch
 
 from . import kernels as K
 from .attention_processor import refresh_text_kv
+from .freeu import FreeU, as_freeu, check_freeu_arg
 from .lora_gate import LoraGate
 from .scheduler import (SAMPLERS, STOCHASTIC_SAMPLERS, EulerDiscreteScheduler, check_eta, sampler_coefficients,
                         start_index)
@@ -67,7 +68,7 @@ class AnimateDiffDenoiser:
                  scheduler: Optional[EulerDiscreteScheduler] = None, use_graph: bool = True, shard=None,
                  num_clips: int = 1, context_length: Optional[int] = None, context_stride: int = 4,
                  context_weighting: str = "pyramid", cross_frame=None, sampler: str = "euler",
-                 guidance_rescale: float = 0.0, eta: float = 1.0):
+                 guidance_rescale: float = 0.0, eta: float = 1.0, freeu=None):
         """`num_clips` clips are denoised together (the reference loop is one clip, B=1).
         `shard` (frame_shard.FrameShard): this process denoises frames [f0, f0 + F/P) of every clip and
         exchanges with the other ranks inside every motion module.
@@ -87,8 +88,13 @@ class AnimateDiffDenoiser:
         (finite, >= 0; 0 is the deterministic sampler; "lcm" ignores it).  The noise is a function of the noise seed
         (set_noise_seed, or the `seed` of a call), the step and the element's place in the whole clip, so a frame
         shard draws what the whole clip draws.  "lcm" (4-8 steps, guidance_scale 1) needs a scheduler with
-        timestep_spacing "lcm" and builds one when none is given."""
+        timestep_spacing "lcm" and builds one when none is given.
+        `freeu` (a freeu.FreeU or its (s1, s2, b1, b2), each finite and > 0): FreeU in the UNet's first
+        two up blocks, the reference's enable_freeu.  None takes what unet.enable_freeu set, if anything, as it stands
+        now.  It is per frame and per channel, so it composes with every other option, a frame shard included; the
+        values live in a device table, so set_freeu keeps a captured step."""
         self.guidance_rescale = check_sampler(sampler, guidance_scale, guidance_rescale, shard, eta, scheduler)
+        check_freeu_arg(freeu)
         if unet is None:  # refused with the other arguments, before anything is allocated
             raise ValueError("AnimateDiffDenoiser needs a UNetMotionModel, got None")
         self.sampler = sampler
@@ -111,6 +117,7 @@ class AnimateDiffDenoiser:
         self.cfg = guidance_scale > 1.0
         self.ncopy = 2 if self.cfg else 1
         self.device = torch.device(device or "cuda")
+        self.freeu = getattr(unet, "freeu", None) if freeu is None else as_freeu(freeu, self.device)
         self.scheduler = scheduler or EulerDiscreteScheduler(**({"timestep_spacing": "lcm"} if sampler == "lcm"
                                                                 else {}))
         self.scheduler.set_timesteps(num_inference_steps, device=self.device)
@@ -178,7 +185,7 @@ class AnimateDiffDenoiser:
         emb = self.unet.embed(self.timesteps, self.pooled, self.time_ids, B, step_idx=self.step_idx)
         noise = self.unet.forward_tokens(self.x, B, self.F, self.h, self.w, emb, self.enc, shard=self.shard,
                                          temporal_context=self.context, cross_frame=self.cross_frame,
-                                         lora_gate=self.lora_gate)
+                                         lora_gate=self.lora_gate, freeu=self.freeu)
         if self.table_step:
             if self.factor is not None:
                 K.cfg_rescale_factor(noise, self.lat.shape, guidance=self.guidance, phi=self.guidance_rescale,
@@ -285,6 +292,22 @@ class AnimateDiffDenoiser:
             self.graph = None
         self.lora_gate.set(c, s)
         refresh_text_kv(self.unet, self.lora_gate)
+
+    def set_freeu(self, s1: float, s2: float, b1: float, b2: float):
+        """FreeU values for the steps that follow.  When FreeU is already on, its device table is rewritten in place
+        and a captured step is kept (it replays with the new values); turning it on drops the captured step, which
+        has no FreeU launches."""
+        if self.freeu is None:
+            self.freeu = FreeU(s1, s2, b1, b2, device=self.device)
+            self.graph = None
+        else:
+            self.freeu.set(s1, s2, b1, b2)
+
+    def clear_freeu(self):
+        """Back to the plain step (drops a captured step with FreeU)."""
+        if self.freeu is not None:
+            self.freeu = None
+            self.graph = None
 
     def clear_lora_gates(self):
         """Back to the plain step (drops a captured gated step)."""

@@ -275,12 +275,13 @@ class TrainStep:
         """The micro-batch loss (train_animatediff.py:228-312): Euler add_noise, the HIP UNet forward, epsilon MSE in
         fp32 and the orthogonality loss."""
         from . import kernels as K
-        from .autograd import refuse_context, unet_train_tokens
+        from .autograd import refuse_context, refuse_freeu, unet_train_tokens
         from .temporal_lora import compute_orth_loss
 
         unet = self.unet
         B, Cl, F, h, w = latents.shape
         refuse_context(self.temporal_context, F)
+        refuse_freeu(unet)
         dev = latents.device
         # add_noise with the clip's timestep on every frame (:233-236); sigma broadcasts over (C, F, h, w)
         noisy = self.sched.add_noise(latents, noise, t).contiguous()

@@ -33,6 +33,7 @@ from torch import nn
 from . import kernels as K
 from .attention_processor import Attention, input_lora_ops
 from .config import UNetMotionConfig
+from .freeu import FreeU, as_freeu
 from .lora_linear import LoRACompatibleLinear, build_ops, lora_in_gemm, run_ops
 from .weights import sinusoid_table
 
@@ -215,6 +216,7 @@ class FwdCtx:
     temporal_context: Optional[TemporalContext] = None  # motion attention inside sliding windows when F > length
     cross_frame: Optional[CrossFrameAttention] = None   # spatial attn1 also attends to source frames when F > 1
     lora_gate: Optional[object] = None  # lora_gate.LoraGate ([B * F] rows): per-frame content / style strength
+    freeu: Optional[FreeU] = None       # backbone scale + skip filter before the skip concats of up stages 0 and 1
 
 
 # --------------------------------------------------------------------------------------- blocks
@@ -552,10 +554,15 @@ class UpBlock(nn.Module):
         self.motion_modules = nn.ModuleList([MotionModule(cout, motion_heads) for _ in range(n)]) if motion else None
         self.upsamplers = nn.ModuleList([Upsample2D(cout)]) if add_up else None
 
-    def run(self, x, nimg, H, W, ctx, skips):
+    def run(self, x, nimg, H, W, ctx, skips, stage=None):
+        """`stage`: this block's index in the up path; with ctx.freeu, stages 0 and 1 run apply_freeu before each
+        resnet (x scaled in place: it is this path's own tensor; the skip filtered into a new one)."""
+        freeu = ctx.freeu if stage in (0, 1) else None
         for j, res in enumerate(self.resnets):
             s, sh, sw = skips.pop()
             assert (sh, sw) == (H, W)
+            if freeu is not None:
+                x, s = K.freeu(x, s, nimg, H, W, freeu.table, stage, x_out=x)
             x = res.run(x, nimg, H, W, ctx, x2=s)  # channel concat [x, skip] read from two sources
             if self.attentions is not None:
                 x = self.attentions[j].run(x, nimg, H, W, ctx)
@@ -634,6 +641,7 @@ class UNetMotionModel(nn.Module):
                                           cfg.motion_num_attention_heads, cfg.motion_modules))
         self.conv_norm_out = GroupNorm(cfg.norm_num_groups, ch[0], eps=cfg.norm_eps)
         self.conv_out = Conv3x3(ch[0], cfg.out_channels)
+        self.freeu = None  # enable_freeu: the default of forward()
 
     # ---- diffusers surface ----------------------------------------------------------------
     @property
@@ -654,6 +662,18 @@ class UNetMotionModel(nn.Module):
         else:
             for m in mods.values():
                 m.set_processor(processor)
+
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
+        """FreeU for every later forward() that is given no `freeu=` (the reference's
+        unziplora_unet/unet_2d_condition.py method; the FreeU authors' SDXL values are s1=0.9, s2=0.2, b1=1.3,
+        b2=1.4).  Inference only.  A second call rewrites the same device table."""
+        if self.freeu is None:
+            self.freeu = FreeU(s1, s2, b1, b2, device=self.conv_in.weight.device)
+        else:
+            self.freeu.set(s1, s2, b1, b2)
+
+    def disable_freeu(self):
+        self.freeu = None
 
     # ---- embeddings -----------------------------------------------------------------------
     def embed(self, timestep, text_embeds, time_ids, B, step_idx=None, out=None):
@@ -689,7 +709,7 @@ class UNetMotionModel(nn.Module):
 
     # ---- core (NHWC tokens) -----------------------------------------------------------------
     def forward_tokens(self, x, B, F, h, w, emb_silu, enc, cross_kwargs=None, shard=None, fusion_world=None,
-                       temporal_context=None, cross_frame=None, lora_gate=None):
+                       temporal_context=None, cross_frame=None, lora_gate=None, freeu=None):
         """x: [B*F*h*w, in_channels] bf16 -> noise prediction [B*F*h*w, out_channels] bf16.
         With `shard` (frame_shard.FrameShard), F is this rank's frames of each clip.  `fusion_world` P (default: the
         shard's world size, else 1): take the shape-dependent fusion decisions a P-way frame-sharded rank takes
@@ -697,7 +717,10 @@ class UNetMotionModel(nn.Module):
         (CrossFrameAttention or its sources): attn1 of the spatial transformer blocks also attends to the source
         frames of the same clip.  `lora_gate` (lora_gate.LoraGate with B * F rows, one per (batch element, frame) in
         row order; under a shard this rank's frames): the content / style strength of the UnZipLoRA delta of the
-        spatial transformer blocks' projections, per row.  The motion modules are not gated."""
+        spatial transformer blocks' projections, per row.  The motion modules are not gated.  `freeu` (freeu.FreeU, or
+        its (s1, s2, b1, b2)): FreeU in the first two up blocks; None runs today's launches.  Here
+        None means off: the enable_freeu default is applied by forward()."""
+        freeu = as_freeu(freeu, x.device)
         cross_frame = as_cross_frame(cross_frame)
         check_cross_frame(self, F * (shard.world if shard is not None else 1), cross_frame, shard)
         if lora_gate is not None and lora_gate.rows != B * F:
@@ -711,7 +734,7 @@ class UNetMotionModel(nn.Module):
         K.colstat_reset()
         with K.row_invariant(), K.fusion_world(fusion_world):
             ctx = FwdCtx(B, F, emb_silu, enc, cross_kwargs or {}, shard, self.batched_temb(emb_silu),
-                         temporal_context, cross_frame, lora_gate)
+                         temporal_context, cross_frame, lora_gate, freeu)
             nimg = B * F
             H, W = h, w
             x = self.conv_in.run(x, nimg, H, W)
@@ -720,26 +743,27 @@ class UNetMotionModel(nn.Module):
                 x, H, W, outs = blk.run(x, nimg, H, W, ctx)
                 skips.extend(outs)
             x = self.mid_block.run(x, nimg, H, W, ctx)
-            for blk in self.up_blocks:
-                x, H, W = blk.run(x, nimg, H, W, ctx, skips)
+            for i, blk in enumerate(self.up_blocks):
+                x, H, W = blk.run(x, nimg, H, W, ctx, skips, stage=i)
             x = self.conv_norm_out.run(x, nimg, H * W, silu=True)
             return self.conv_out.run(x, nimg, H, W)
 
     def forward(self, sample, timestep, encoder_hidden_states, timestep_cond=None, attention_mask=None,
                 cross_attention_kwargs=None, added_cond_kwargs=None, return_dict=True, frame_shard=None,
-                fusion_world=None, temporal_context=None, cross_frame=None, lora_gate=None, **kwargs):
+                fusion_world=None, temporal_context=None, cross_frame=None, lora_gate=None, freeu=None, **kwargs):
         """diffusers UNetMotionModel.forward signature (inference_animatediff.py:110-121).  With
         `frame_shard` (frame_shard.FrameShard) `sample` holds this rank's frames of each clip; `fusion_world`: see
         forward_tokens; `temporal_context` (TemporalContext): the motion modules attend inside sliding windows when the
         clip is longer than its length; `cross_frame` (CrossFrameAttention or its sources, e.g. ("first",)): attn1 of the
         spatial transformer blocks also attends to the source frames of the same clip; `lora_gate`: see
-        forward_tokens."""
+        forward_tokens; `freeu` (FreeU or (s1, s2, b1, b2)): FreeU for this call, default what enable_freeu set."""
         if not sample.is_cuda:
             raise K._lib.VstError("UNetMotionModel: sample is on CPU; the HIP path has no CPU fallback")
         B, Cin, F, h, w = sample.shape
         cross_frame = as_cross_frame(cross_frame)
         check_cross_frame(self, F * (frame_shard.world if frame_shard is not None else 1), cross_frame,
                           frame_shard)
+        freeu = as_freeu(self.freeu if freeu is None else freeu, sample.device)  # bad values: before any launch
         if self.config.motion_modules:
             check_clip_length(F * (frame_shard.world if frame_shard is not None else 1),
                               self.config.motion_max_seq_length, temporal_context)
@@ -757,6 +781,7 @@ class UNetMotionModel(nn.Module):
         K.pack_latents(sample.float().contiguous(), x)
         y = self.forward_tokens(x, B, F, h, w, emb_silu, enc, cross_attention_kwargs, shard=frame_shard,
                                 fusion_world=fusion_world, temporal_context=temporal_context,
-                                cross_frame=cross_frame, lora_gate=lora_gate)
+                                cross_frame=cross_frame, lora_gate=lora_gate,
+                                freeu=freeu)
         out = y.view(B, F, h, w, -1).permute(0, 4, 1, 2, 3).contiguous().to(sample.dtype)
         return UNetMotionOutput(out) if return_dict else (out,)
