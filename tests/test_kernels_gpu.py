@@ -328,6 +328,62 @@ def test_conv3x3(cuda, K, n, Ci, Co, H, W, stride, up):
     check(out, to_nhwc(ref), name="conv")
 
 
+GATHER_CASES = [  # n, Ci, Co, H, W, mode, adds (bias + row bias + residual; else bias only)
+    (2, 3, 24, 7, 5, "s1", False),      # K 27 -> 32 (half k-tile), M = 70: one partial row tile, one partial column tile
+    (2, 4, 72, 13, 11, "s1", False),    # K 36 -> 40, M = 286: three row tiles with a tail, two column tiles
+    (2, 12, 24, 13, 11, "s1", False),   # K 108 -> 112: two k-tiles
+    (2, 12, 4, 7, 5, "s1", False),      # Cout 4: the scalar column tail
+    (2, 3, 72, 7, 5, "s2", False),      # stride 2, odd H and W
+    (2, 4, 24, 13, 11, "s2", False),
+    (2, 4, 24, 7, 5, "up", False),      # nearest-2x upsample, M = 280
+    (2, 12, 72, 7, 5, "up", True),
+    (2, 4, 24, 13, 11, "pad0", False),  # Downsample2D(padding=0)
+    (2, 4, 4, 7, 5, "pad0", False),
+    (2, 3, 24, 13, 11, "s1", True),
+    (2, 4, 4, 7, 5, "s1", True),        # the adds on the scalar column tail
+    (2, 12, 72, 13, 11, "s2", True),
+]
+
+
+def gather_case(n, Ci, Co, H, W, mode, adds):
+    """CPU tensors of one GATHER_CASES row and its fp32 reference [n, Co, OH, OW]."""
+    g = torch.Generator().manual_seed(Ci * 7 + Co + H)
+    x = rnd(n, Ci, H, W, gen=g)
+    w = rnd(Co, Ci, 3, 3, scale=(9 * Ci) ** -0.5, gen=g)
+    b = torch.randn(Co, generator=g) * 0.1
+    if mode == "pad0":
+        ref = F.conv2d(F.pad(x.float(), (0, 1, 0, 1)), w.float(), b, stride=2)
+    else:
+        ref = conv_ref(x.float(), w.float(), b, 2 if mode == "s2" else 1, mode == "up")
+    temb = r = None
+    if adds:  # the conv output rounded to bf16, then the adds (as test_conv3x3_8phase_bitwise_equals_ring builds it)
+        temb = torch.randn(n, Co, generator=g)
+        r = rnd(*ref.shape, gen=g)
+        ref = ref.to(torch.bfloat16).float() + temb[:, :, None, None] + r.float()
+    return x, w, b, temb, r, ref
+
+
+@pytest.mark.parametrize("n,Ci,Co,H,W,mode,adds", GATHER_CASES)
+def test_conv3x3_gather(cuda, K, n, Ci, Co, H, W, mode, adds):
+    """conv_gather_kernel (gemm.hip: 3x3 convs whose channel count does not allow 16-byte loads) against fp32 torch at
+    every branch: K padding and the skipped half k-tile, one and two k-tiles, row and column tile tails, the scalar
+    column tail, stride 2, upsample, no top / left padding, and the epilogue with and without row bias + residual."""
+    x, w, b, temb, r, ref = gather_case(n, Ci, Co, H, W, mode, adds)
+    OH, OW = ref.shape[2:]
+    M, wf = n * OH * OW, wflat(w)
+    assert K.gemm_kernel_name(M, Co, wf.shape[1], 3) == "gemm_kernel<conv_in>"
+    xd, wd, bd = to_nhwc(x).to(cuda), wf.to(cuda), b.to(cuda)
+    if mode == "pad0":  # the C entry point of K.conv3x3_down_pad0 (whose wrapper takes multiples of 64 channels only)
+        from video_style_transfer_amd import _lib
+        out = torch.empty((M, Co), dtype=torch.bfloat16, device=cuda)
+        _lib.call("vst_conv3x3_down_pad0", xd.data_ptr(), Ci, n, H, W, wd.data_ptr(), Co, bd.data_ptr(),
+                  out.data_ptr(), out.stride(0), K._workspace(xd.device).data_ptr(), K._WS_BYTES, K._stream())
+    else:
+        kw = dict(row_bias=temb.to(cuda), row_bias_div=OH * OW, residual=to_nhwc(r).to(cuda)) if adds else {}
+        out = K.conv3x3(xd, n, H, W, wd, bd, stride=2 if mode == "s2" else 1, upsample=mode == "up", **kw)
+    check(out, to_nhwc(ref), name="conv gather")
+
+
 @pytest.mark.parametrize("n,C1,C2,Co,H,W,stride,up", [
     (8, 320, 0, 320, 64, 64, 1, False),     # 64x64 level, Cout 320: 128x320 tiles
     (16, 640, 320, 640, 32, 32, 1, False),  # up path: skip concat, Cout 640

@@ -42,7 +42,8 @@ def bench_symbol(name: str) -> str:
     for k, v in (("gemm_skinny", "gemm_skinny"), ("spatial_attn_kernel", "spatial_attn_kernel"),
                  ("layernorm_g_kernel", "layernorm_kernel"),
                  ("temporal_attn_kernel", "temporal_attn_kernel"), ("layernorm_kernel", "layernorm_kernel"),
-                 ("gn_", "gn_stats/gn_finalize/gn_apply"), ("gemm_kernel<2", "gemm_kernel<conv_in>"),
+                 ("gn_", "gn_stats/gn_finalize/gn_apply"), ("conv_gather_kernel", "gemm_kernel<conv_in>"),
+                 ("gemm_kernel<2", "gemm_kernel<conv_in>"),  # its symbol in traces recorded before 2026-10-20
                  ("gemm_rows_kernel", "gemm_rows")):
         if k in name:
             return v

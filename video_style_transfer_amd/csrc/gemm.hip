@@ -1,29 +1,11 @@
-// bf16 MFMA GEMM for every dense contraction on the AnimateDiff-XL denoise path:
-//   C[M,N] = epilogue( A[M,K] . W[N,K]^T )
-// W is nn.Linear layout ([out, in], K contiguous) so both operands are K-contiguous
-// and every MFMA fragment is one 16-byte LDS read.
-//
-// A operand loaders (template AMODE):
-//   0  dense rows, optionally split along K into two sources (A1 for k < K1, A2
-//      after).  The split carries (a) channel concatenation without a copy and
-//      (b) the UnZipLoRA low-rank delta as extra K columns: [x | x.Acat^T] .
-//      [W | s.(B (.) m)]^T  = x W^T + s.Delta(x)  (unziplora_linear_layer.py:298-346).
-//   1  implicit-GEMM 3x3 conv over NHWC activations (per-frame SDXL conv, diffusers
-//      ResnetBlock2D / Downsample2D / Upsample2D): K = (ky,kx,ci), zero padding via
-//      out-of-range buffer loads, stride 1/2, fused nearest-2x upsample, two-source
-//      channel concat (up-block skip connections).
-//   2  same conv with a scalar gather (tiny Cin, e.g. conv_in with 4 channels).
-// Epilogues (template EPI): 0 = +bias[n] +row_bias[m/div][n] +residual[m,n] -> bf16;
-//   1 = GEGLU (per 64 columns: [0,32) hidden, [32,64) gate of the same 32 outputs;
-//   the host interleaves the weight rows accordingly); 2 = fp32 split-K partial slab
-//   (the epilogue then runs in gemm_splitk_reduce_kernel).
-//
-// Tile BM=128 x BN (128 or 64) x BK=64, 256 threads = 4 waves (2x2), each wave 64 x BN/2 via
-// v_mfma_f32_16x16x32_bf16.  Register-staged double-buffered LDS with the load-early /
-// write-late split; XOR-swizzled 128-byte LDS rows (conflict-free ds_read_b128 fragment
-// reads); XCD-aware tile order; fp32 LDS-staged epilogue with 16-byte coalesced stores.
-// Host-side heuristic (vst_gemm): BN=64 when the 128x128 grid would run in few waves on
-// 256 CUs (tail effect), split-K (blockIdx.z) when even that grid cannot fill the chip.
+// The GEMM front end: the small kernels beside the ring kernel (gemm_big.hip) and the 8-phase kernel (gemm_p8.hip),
+// the policy that turns one call into one plan (plan_gemm, gemm_plan.h), and the C entry points (include/vst.h).
+// Kernels here, each for a corner where a 256-wide MFMA tile has nothing to do:
+//   conv_gather_kernel         3x3 conv whose channel count does not allow 16-byte loads (conv_in of UNet and VAE)
+//   gemm_skinny_kernel         N <= 64 without an epilogue (the UnZipLoRA down-projection)
+//   gemm_rows_kernel           M <= 8 (time-embedding MLPs)
+//   gemm_splitk_reduce_kernel  sum of the ring kernel's split-K slabs + epilogue
+// Operand layouts: gemm_common.h; epilogues and rounding points: gemm_epilogue.h.
 #include <cstdio>
 #include <cstdlib>
 #include <mutex>
@@ -34,53 +16,35 @@
 
 namespace vst {
 
-constexpr int BM = 128, BK = 64;
-constexpr int A_TILE = BM * BK * 2;  // 16 KiB
+constexpr int BM = 128, BK = 64;  // (BK is also the alignment the host asks of an A source split)
+constexpr int GBN = 64;           // the gather conv's tile: 128 x 64 x 64
+constexpr int A_TILE = BM * BK * 2, B_TILE = GBN * BK * 2, STAGE = A_TILE + B_TILE;
+constexpr int GATHER_LDS = 2 * STAGE;  // 48 KiB: two stages; the fp32 epilogue tile (32 KiB) reuses them
+static_assert(GATHER_LDS >= BM * GBN * 4, "epilogue tile fits the stages");
 
-template <int BN>
-constexpr int gemm_lds_bytes() {
-  return (2 * (A_TILE + BN * BK * 2)) > (BM * BN * 4) ? 2 * (A_TILE + BN * BK * 2) : BM * BN * 4;
-}
-
-template <int AMODE, int EPI, int BN>
-__global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs p) {
-  constexpr int B_TILE = BN * BK * 2;
-  constexpr int STAGE = A_TILE + B_TILE;
-  constexpr int NT = BN / 32;      // 16-wide n tiles per wave
-  constexpr int BCH = BN / 32;     // B staging chunks per thread
+// 3x3 conv (gemm_common.h conv A, one source) for channel counts that are no multiple of 8: each of a thread's
+// 16-byte A chunks is gathered as 8 scalar loads, k = (tap, ci) padded to a multiple of 8 (the weight rows too).
+// 256 threads = 4 waves (2 x 2), each wave 64 x 32 via v_mfma_f32_16x16x32_bf16; register-staged double-buffered LDS
+// (load early, write late) in XOR-swizzled 128-byte rows; XCD-aware tile order; the fp32 tile goes through LDS to
+// 16-byte stores with the ring kernel's rounding points (gemm_epilogue.h).
+__global__ __launch_bounds__(256, 2) void conv_gather_kernel(GemmArgs p) {
+  constexpr int NT = GBN / 32;   // 16-wide n tiles per wave
+  constexpr int BCH = GBN / 32;  // B staging chunks per thread
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wr = wid >> 1, wc = wid & 1;
-  const int nbn = (p.N + BN - 1) / BN, nbm = (p.M + BM - 1) / BM;
+  const int nbn = (p.N + GBN - 1) / GBN, nbm = (p.M + BM - 1) / BM;
   const int wg = xcd_remap(blockIdx.x, nbn * nbm);
   const int bm = wg / nbn, bn = wg - bm * nbn;
-  const int m0 = bm * BM, n0 = bn * BN;
+  const int m0 = bm * BM, n0 = bn * GBN;
 
-  const auto ra1 = make_rsrc(p.A1, p.a1_bytes);
-  const auto ra2 = make_rsrc(p.A2 ? p.A2 : p.A1, p.A2 ? p.a2_bytes : 0u);
+  const auto ra = make_rsrc(p.A1, p.a1_bytes);
   const auto rw = make_rsrc(p.Wt, p.w_bytes);
 
   const int sc = tid & 7, sr = tid >> 3;  // staging chunk / base row
-  // per-staged-row A geometry (fixed over the K loop)
-  int rowA[4], oyv[4], oxv[4];
+  int img[4], oyv[4], oxv[4];             // per-staged-row A geometry (fixed over the K loop)
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int m = m0 + sr + 32 * i;
-    if (AMODE == 0) {
-      rowA[i] = m < p.M ? m : -1;
-      oyv[i] = oxv[i] = 0;
-    } else {
-      if (m < p.M) {
-        const int hw = p.OH * p.OW;
-        const int img = m / hw, rem = m - img * hw;
-        rowA[i] = img;
-        oyv[i] = rem / p.OW;
-        oxv[i] = rem - oyv[i] * p.OW;
-      } else {
-        rowA[i] = -1; oyv[i] = oxv[i] = 0;
-      }
-    }
-  }
+  for (int i = 0; i < 4; ++i) conv_row(p, m0 + sr + 32 * i, img[i], oyv[i], oxv[i]);
   int rowB[BCH];
 #pragma unroll
   for (int i = 0; i < BCH; ++i) {
@@ -89,88 +53,29 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs p) {
   }
 
   u32x4 va[4], vb[BCH];
-  const int nk_all = (p.K + BK - 1) / BK;
-  int kt_beg = 0, kt_end = nk_all;
-  if (EPI == 2) {
-    const int z = blockIdx.z;
-    kt_beg = (int)((long long)nk_all * z / p.splits);
-    kt_end = (int)((long long)nk_all * (z + 1) / p.splits);
-  }
-  const int Ctot = p.C1 + p.C2;
+  const int nk = (p.K + BK - 1) / BK;
 
   auto load_tile = [&](int kt) {
-    const int k0 = kt * BK;
-    const int k = k0 + sc * 8;
-    // ---- B (weights) ----
+    const int k = kt * BK + sc * 8;
 #pragma unroll
     for (int i = 0; i < BCH; ++i) {
       const int off = (rowB[i] >= 0 && k < p.K) ? (rowB[i] * p.ldw + k) * 2 : kOOB;
       vb[i] = buf_load16(rw, off);
     }
-    // ---- A ----
-    if (AMODE == 0) {
-      if (k0 < p.K1) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int off = (rowA[i] >= 0 && k < p.K1) ? (rowA[i] * p.lda1 + k) * 2 : kOOB;
-          va[i] = buf_load16(ra1, off);
-        }
-      } else {
-        const int kk = k - p.K1;
+    for (int i = 0; i < 4; ++i) {
+      uint16_t e[8];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int off = (rowA[i] >= 0 && k < p.K) ? (rowA[i] * p.lda2 + kk) * 2 : kOOB;
-          va[i] = buf_load16(ra2, off);
-        }
+      for (int j = 0; j < 8; ++j) {
+        const int kj = k + j;
+        const int tap = kj / p.C1, ci = kj - tap * p.C1;
+        const int ky = tap / 3, kx = tap - ky * 3;
+        int px;  // (kj >= K1 = 9 C1: the K padding)
+        const bool ok = conv_tap_pixel(p, img[i], oyv[i], oxv[i], ky, kx, px, kj < p.K1);
+        e[j] = buf_load2(ra, ok ? (px * p.C1 + ci) * 2 : kOOB);
       }
-    } else if (AMODE == 1) {
-      const int tap = k0 / Ctot;
-      const int ci0 = k0 - tap * Ctot;
-      const int ky = tap / 3, kx = tap - ky * 3;
-      const bool first = ci0 < p.C1;
-      const int cs = first ? p.C1 : p.C2;
-      const int ci = (first ? ci0 : ci0 - p.C1) + sc * 8;
-      const auto rs = first ? ra1 : ra2;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        int iy, ix;
-        bool ok = rowA[i] >= 0 && tap < 9;
-        if (p.up) {
-          const int uy = oyv[i] + ky - 1, ux = oxv[i] + kx - 1;
-          ok = ok && uy >= 0 && uy < 2 * p.H && ux >= 0 && ux < 2 * p.W;
-          iy = uy >> 1; ix = ux >> 1;
-        } else {
-          iy = oyv[i] * p.stride + ky - 1 + p.pad0; ix = oxv[i] * p.stride + kx - 1 + p.pad0;
-          ok = ok && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
-        }
-        const int off = ok ? (((rowA[i] * p.H + iy) * p.W + ix) * cs + ci) * 2 : kOOB;
-        va[i] = buf_load16(rs, off);
-      }
-    } else {  // scalar gather conv (single source)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        uint16_t e[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const int kj = k + j;
-          const int tap = kj / p.C1, ci = kj - tap * p.C1;
-          const int ky = tap / 3, kx = tap - ky * 3;
-          int iy, ix;
-          bool ok = rowA[i] >= 0 && kj < p.K1;
-          if (p.up) {
-            const int uy = oyv[i] + ky - 1, ux = oxv[i] + kx - 1;
-            ok = ok && uy >= 0 && uy < 2 * p.H && ux >= 0 && ux < 2 * p.W;
-            iy = uy >> 1; ix = ux >> 1;
-          } else {
-            iy = oyv[i] * p.stride + ky - 1 + p.pad0; ix = oxv[i] * p.stride + kx - 1 + p.pad0;
-            ok = ok && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
-          }
-          const int off = ok ? (((rowA[i] * p.H + iy) * p.W + ix) * p.C1 + ci) * 2 : kOOB;
-          e[j] = buf_load2(ra1, off);
-        }
-        va[i] = u32x4{(uint32_t)e[0] | ((uint32_t)e[1] << 16), (uint32_t)e[2] | ((uint32_t)e[3] << 16),
-                      (uint32_t)e[4] | ((uint32_t)e[5] << 16), (uint32_t)e[6] | ((uint32_t)e[7] << 16)};
-      }
+      va[i] = u32x4{(uint32_t)e[0] | ((uint32_t)e[1] << 16), (uint32_t)e[2] | ((uint32_t)e[3] << 16),
+                    (uint32_t)e[4] | ((uint32_t)e[5] << 16), (uint32_t)e[6] | ((uint32_t)e[7] << 16)};
     }
   };
 
@@ -190,18 +95,18 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs p) {
     for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   const int fr = lane & 15, fq = lane >> 4;
-  if (kt_beg < kt_end) {
-    load_tile(kt_beg);
+  if (nk > 0) {
+    load_tile(0);
     store_tile(0);
   }
   __syncthreads();
 
-  for (int kt = kt_beg; kt < kt_end; ++kt) {
-    const int cur = (kt - kt_beg) & 1;
-    if (kt + 1 < kt_end) load_tile(kt + 1);
+  for (int kt = 0; kt < nk; ++kt) {
+    const int cur = kt & 1;
+    if (kt + 1 < nk) load_tile(kt + 1);
     const char* As = smem + cur * STAGE;
     const char* Bs = As + A_TILE;
-    // skip the second 32-deep half when it lies wholly beyond K (LoRA tail tile)
+    // skip the second 32-deep half when it lies wholly beyond K (Cin = 3 / 4: K = 32 / 40)
     const int nkk = (kt * BK + 32 < p.K) ? 2 : 1;
     for (int kk = 0; kk < nkk; ++kk) {
       bf16x8 af[4], bfr[NT];
@@ -210,14 +115,14 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs p) {
       for (int i = 0; i < 4; ++i) af[i] = *reinterpret_cast<const bf16x8*>(As + swz(wr * 64 + i * 16 + fr, chunk));
 #pragma unroll
       for (int j = 0; j < NT; ++j)
-        bfr[j] = *reinterpret_cast<const bf16x8*>(Bs + swz(wc * (BN / 2) + j * 16 + fr, chunk));
+        bfr[j] = *reinterpret_cast<const bf16x8*>(Bs + swz(wc * (GBN / 2) + j * 16 + fr, chunk));
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < NT; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
     }
-    if (kt + 1 < kt_end) store_tile(cur ^ 1);
+    if (kt + 1 < nk) store_tile(cur ^ 1);
     __syncthreads();
   }
 
@@ -230,97 +135,63 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs p) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int row = wr * 64 + i * 16 + fq * 4 + r;
-        const int col = wc * (BN / 2) + j * 16 + fr;
-        Cs[row * BN + col] = acc[i][j][r];
+        const int col = wc * (GBN / 2) + j * 16 + fr;
+        Cs[row * GBN + col] = acc[i][j][r];
       }
   __syncthreads();
 
-  constexpr int CPR = BN / 8;  // 8-column chunks per tile row
-  if (EPI == 2) {
-    float* slab = p.ws + (size_t)blockIdx.z * p.M * p.N;
-#pragma unroll 2
-    for (int it = 0; it < BM * CPR / 256; ++it) {
-      const int idx = tid + 256 * it;
-      const int row = idx / CPR, cc = idx - row * CPR;
-      const int m = m0 + row, n = n0 + cc * 8;
-      if (m >= p.M || n >= p.N) continue;
-      const f32x4 c0 = *reinterpret_cast<const f32x4*>(Cs + row * BN + cc * 8);
-      const f32x4 c1 = *reinterpret_cast<const f32x4*>(Cs + row * BN + cc * 8 + 4);
-      float* dst = slab + (size_t)m * p.N + n;
-      if (n + 8 <= p.N) {
-        *reinterpret_cast<f32x4*>(dst) = c0;
-        *reinterpret_cast<f32x4*>(dst + 4) = c1;
-      } else {
-        for (int e = 0; e < p.N - n; ++e) dst[e] = e < 4 ? c0[e] : c1[e - 4];
-      }
-    }
-    return;
-  }
+  constexpr int CPR = GBN / 8;  // 8-column chunks per tile row
   const auto rr = make_rsrc(p.R ? p.R : p.Wt, p.R ? p.r_bytes : 0u);
-  if (EPI == 0) {
 #pragma unroll 2
-    for (int it = 0; it < BM * CPR / 256; ++it) {
-      const int idx = tid + 256 * it;
-      const int row = idx / CPR, cc = idx - row * CPR;
-      const int m = m0 + row, n = n0 + cc * 8;
-      if (m >= p.M || n >= p.N) continue;
-      float v[8];
-      const f32x4 c0 = *reinterpret_cast<const f32x4*>(Cs + row * BN + cc * 8);
-      const f32x4 c1 = *reinterpret_cast<const f32x4*>(Cs + row * BN + cc * 8 + 4);
+  for (int it = 0; it < BM * CPR / 256; ++it) {
+    const int idx = tid + 256 * it;
+    const int row = idx / CPR, cc = idx - row * CPR;
+    const int m = m0 + row, n = n0 + cc * 8;
+    if (m >= p.M || n >= p.N) continue;
+    float v[8];
+    const f32x4 c0 = *reinterpret_cast<const f32x4*>(Cs + row * GBN + cc * 8);
+    const f32x4 c1 = *reinterpret_cast<const f32x4*>(Cs + row * GBN + cc * 8 + 4);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) { v[e] = c0[e]; v[e + 4] = c1[e]; }
-      const int nv = min(8, p.N - n);
-      if (p.bias) {
+    for (int e = 0; e < 4; ++e) { v[e] = c0[e]; v[e + 4] = c1[e]; }
+    const int nv = min(8, p.N - n);
+    if (p.bias) {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) if (e < nv) v[e] += p.bias[n + e];
-      }
-      if (p.rbias || p.R) {  // same rounding points as the ring kernel: bf16 linear output, then the adds
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = round_bf(v[e]);
-      }
-      if (p.rbias) {
-        const float* rb = p.rbias + (size_t)(m / p.rbias_div) * p.ldrb + n;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) if (e < nv) v[e] += rb[e];
-      }
-      if (nv == 8) {
-        if (p.R) {
-          float r8[8];
-          unpack8(buf_load16(rr, (m * p.ldr + n) * 2), r8);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] += r8[e];
-        }
-        *reinterpret_cast<u32x4*>(p.C + (size_t)m * p.ldc + n) = pack8(v);
-      } else {
-        for (int e = 0; e < nv; ++e) {
-          float x = v[e];
-          if (p.R) x += bf2f(p.R[(size_t)m * p.ldr + n + e]);
-          p.C[(size_t)m * p.ldc + n + e] = f2bf(x);
-        }
-      }
+      for (int e = 0; e < 8; ++e) if (e < nv) v[e] += p.bias[n + e];
     }
-  } else {  // GEGLU (BN == 128): out[m, n0/2 + c] = (h + bh) * gelu(g + bg)
-#pragma unroll 2
-    for (int it = 0; it < 4; ++it) {
-      const int idx = tid + 256 * it;
-      const int row = idx >> 3, cc = idx & 7;
-      const int m = m0 + row;
-      if (m >= p.M || n0 >= p.N) continue;
-      float v[8];
+    if (p.rbias || p.R) {  // same rounding points as the ring kernel: bf16 conv output, then the adds
 #pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        float h = Cs[row * BN + cc * 8 + e];
-        float g = Cs[row * BN + 64 + cc * 8 + e];
-        if (p.bias) { h += p.bias[n0 + cc * 8 + e]; g += p.bias[n0 + 64 + cc * 8 + e]; }
-        v[e] = round_bf(h) * gelu_erf(round_bf(g));  // bf16 projection output, as the ring kernel stages it
+      for (int e = 0; e < 8; ++e) v[e] = round_bf(v[e]);
+    }
+    if (p.rbias) {
+      const float* rb = p.rbias + (size_t)(m / p.rbias_div) * p.ldrb + n;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) if (e < nv) v[e] += rb[e];
+    }
+    if (nv == 8) {
+      if (p.R) {
+        float r8[8];
+        unpack8(buf_load16(rr, (m * p.ldr + n) * 2), r8);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] += r8[e];
       }
-      *reinterpret_cast<u32x4*>(p.C + (size_t)m * p.ldc + (n0 >> 1) + cc * 8) = pack8(v);
+      *reinterpret_cast<u32x4*>(p.C + (size_t)m * p.ldc + n) = pack8(v);
+    } else {  // Cout < 8 (conv_out-like widths), or the last chunk of a Cout that is no multiple of 8
+      for (int e = 0; e < nv; ++e) {
+        float x = v[e];
+        if (p.R) x += bf2f(p.R[(size_t)m * p.ldr + n + e]);
+        p.C[(size_t)m * p.ldc + n + e] = f2bf(x);
+      }
     }
   }
 }
 
-// sum the split-K slabs and apply the epilogue.  geglu: slab columns are the interleaved
-// [h(32) | g(32)] blocks; each thread produces 8 output columns.
+static int launch_gather(const GemmArgs& a, hipStream_t s) {
+  const int nwg = ((a.M + BM - 1) / BM) * ((a.N + GBN - 1) / GBN);
+  hipLaunchKernelGGL(conv_gather_kernel, dim3(nwg), dim3(256), GATHER_LDS, s, a);
+  return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
+}
+
+
 // Skinny GEMM for the UnZipLoRA down-projection u = x . Acat^T (N = padded 2r per projection <= 64,
 // no epilogue): HBM/MALL-bound on reading x once.  A workgroup = 8 waves owns 32 rows (two 16-row
 // MFMA fragments) and all N columns; wave w takes the k32-steps w, w+8, ..., issuing a whole group
@@ -328,12 +199,11 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs p) {
 // the 16x16x32 operand layout: no LDS staging).  Each W fragment feeds two row fragments, so the W
 // bytes read per x byte are N/32 (the L2 traffic that bounded the 16-row version).  The 8 partial
 // accumulators are summed through LDS (64 KiB at N = 64).  ceil(M/32) workgroups (256 at M = 8192), 2 per CU.
+constexpr int kSkinnyMI = 2;  // 16-row fragments per workgroup
+
 template <int NJ>
-#ifndef VST_SKINNY_MI
-#define VST_SKINNY_MI 2
-#endif
 __global__ __launch_bounds__(512, 2) void gemm_skinny_kernel(GemmArgs p) {
-  constexpr int MI = VST_SKINNY_MI, NW = 8;
+  constexpr int MI = kSkinnyMI, NW = 8;
   constexpr int SK = NJ <= 2 ? 6 : 3;  // k32-steps per wave per load group (all in flight at once)
   __shared__ f32x4 red[NW][MI][NJ][64];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -414,7 +284,7 @@ __global__ __launch_bounds__(512, 2) void gemm_skinny_kernel(GemmArgs p) {
 }
 
 static int launch_skinny(const GemmArgs& a, hipStream_t s) {
-  const dim3 grid((a.M + 16 * VST_SKINNY_MI - 1) / (16 * VST_SKINNY_MI));
+  const dim3 grid((a.M + 16 * kSkinnyMI - 1) / (16 * kSkinnyMI));
   switch ((a.N + 15) / 16) {
     case 1: hipLaunchKernelGGL(gemm_skinny_kernel<1>, grid, dim3(512), 0, s, a); break;
     case 2: hipLaunchKernelGGL(gemm_skinny_kernel<2>, grid, dim3(512), 0, s, a); break;
@@ -505,6 +375,8 @@ static int launch_rows(const GemmArgs& a, hipStream_t s) {
   return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
 }
 
+// Sum the ring kernel's split-K slabs and apply the epilogue.  geglu: slab columns are the interleaved
+// [h(32) | g(32)] blocks; each thread produces 8 output columns.
 __global__ __launch_bounds__(256) void gemm_splitk_reduce_kernel(GemmArgs p, int geglu) {
   const int Nout = geglu ? p.N / 2 : p.N;
   const int CPR = (Nout + 7) / 8;
@@ -560,13 +432,6 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce_kernel(GemmArgs p, int
       for (int e = 0; e < nv; ++e) dst[e] = f2bf(v[e]);
     }
   }
-}
-
-template <int AMODE, int EPI, int BN>
-static int launch_one(const GemmArgs& a, hipStream_t s, int splits) {
-  const int nwg = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
-  hipLaunchKernelGGL((gemm_kernel<AMODE, EPI, BN>), dim3(nwg, 1, splits), dim3(256), gemm_lds_bytes<BN>(), s, a);
-  return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
 }
 
 // ---------------- dispatch: one query -> one plan (gemm_plan.h) ----------------
@@ -713,7 +578,7 @@ static int p8_bn(int M, int N, bool geglu) {
 // per launch (tools/vae_conv_ab.py, profiles/r6_vae_conv_ab.txt).  No UNet conv qualifies (Cout 320 / 640 / 1280 / 4).
 static bool conv_ring128(int M, int N) { return N % 128 == 0 && N % 320 != 0 && p8_bn(M, N, false) == 192; }
 
-// the 8-phase kernel: AMODE 0, no split-K, a 64-aligned A source split
+// the 8-phase kernel: dense A, no split-K, a 64-aligned A source split
 static bool p8_applies(int K1, bool two_src) {
   return !two_src || (K1 & 63) == 0;
 }
@@ -810,7 +675,7 @@ static int launch_plan(GemmArgs& a, const GemmPlan& p, hipStream_t s) {
   switch (p.family) {
     case kRows: return launch_rows(a, s);
     case kSkinny: return launch_skinny(a, s);
-    case kGather: return launch_one<2, 0, 64>(a, s, 1);
+    case kGather: return launch_gather(a, s);
     case kP8: return launch_gemm_p8(a, p, s);
     case kP8Conv: return launch_gemm_p8_conv(a, p, s);
     case kRing: break;
@@ -859,6 +724,33 @@ extern "C" size_t vst_gemm_workspace_bytes(int M, int N, int K) {
   q.M = M, q.N = N, q.K = q.K1 = K, q.epi = 2, q.slab_bytes = (size_t)-1;
   const int splits = plan_gemm(q).splits;
   return splits > 1 ? (size_t)splits * M * N * sizeof(float) : 0;
+}
+
+// ---------------- entry points ----------------
+constexpr size_t kMaxExtent = 0x7fffffffULL;  // the largest byte extent a buffer descriptor's 32-bit offsets reach
+constexpr float kLog2e = 1.4426950408889634f;
+
+// GemmArgs of a dense call: A [M][K1] (row stride lda; vst_gemm_ex adds the second source), W [N][K], bias, C, the
+// operands' extents through fit, one split, stride 1.  Everything else is zero.
+static GemmArgs dense_args(Fit31& fit, const void* A, int lda, int K1, const void* W, int ldw, int M, int N, int K,
+                           const float* bias, void* C, int ldc) {
+  GemmArgs a{};
+  a.A1 = (const bf16_t*)A; a.lda1 = lda; a.K1 = K1;
+  a.Wt = (const bf16_t*)W; a.ldw = ldw; a.M = M; a.N = N; a.K = K;
+  a.bias = bias; a.C = (bf16_t*)C; a.ldc = ldc;
+  a.a1_bytes = fit(((size_t)(M - 1) * lda + K1) * 2);
+  a.w_bytes = fit(((size_t)(N - 1) * ldw + K) * 2);
+  a.stride = 1; a.splits = 1;
+  return a;
+}
+
+// The in-GEMM LoRA block (GemmArgs::la ...) and the row gate on u, on top of dense_args
+static void lora_args(GemmArgs& a, Fit31& fit, const void* Acat, int ld_acat, int P, int group_n, int group_r,
+                      bool gated, const float* gate, int ld_gate, int gate_div) {
+  a.wtail_bytes = fit(((size_t)(a.N - 1) * a.ldw + a.K + P) * 2);
+  a.la = (const bf16_t*)Acat; a.lda_la = ld_acat; a.la_p = P; a.la_gn = group_n; a.la_gr = group_r;
+  a.la_bytes = fit((size_t)P * ld_acat * 2);
+  if (gated) { a.gate = gate; a.ld_gate = ld_gate; a.gate_div = gate_div; }
 }
 
 // ---- fused base + LoRA projection with the down-projection inside the 8-phase GEMM (gemm_p8.hip LORA) ----
@@ -920,19 +812,11 @@ static int gemm_lora_impl(const void* x, int ldx, const void* Acat, int ld_acat,
   if (R && ((ldr & 7) || ldr < N)) return VST_ERR_ARG;
   const int bn = lora_ingemm_bn(M, N, K, P, group_n, group_r);
   if (!bn) return VST_ERR_UNSUPPORTED;
-  GemmArgs a{};
-  a.A1 = (const bf16_t*)x; a.A2 = nullptr; a.lda1 = ldx; a.lda2 = 0; a.K1 = K;
-  a.Wt = (const bf16_t*)W; a.ldw = ldw; a.M = M; a.N = N; a.K = K;
-  a.bias = bias; a.R = (const bf16_t*)R; a.ldr = ldr; a.C = (bf16_t*)C; a.ldc = ldc;
-  a.a1_bytes = fit(((size_t)(M - 1) * ldx + K) * 2);
-  a.w_bytes = fit(((size_t)(N - 1) * ldw + K) * 2);
-  a.wtail_bytes = fit(((size_t)(N - 1) * ldw + K + P) * 2);
+  GemmArgs a = dense_args(fit, x, ldx, K, W, ldw, M, N, K, bias, C, ldc);
+  a.R = (const bf16_t*)R; a.ldr = ldr;
   a.r_bytes = R ? fit(((size_t)(M - 1) * ldr + N) * 2) : 0;
-  a.la = (const bf16_t*)Acat; a.lda_la = ld_acat; a.la_p = P; a.la_gn = group_n; a.la_gr = group_r;
-  a.la_bytes = fit((size_t)P * ld_acat * 2);
-  if (gated) { a.gate = gate; a.ld_gate = ld_gate; a.gate_div = gate_div; }
+  lora_args(a, fit, Acat, ld_acat, P, group_n, group_r, gated, gate, ld_gate, gate_div);
   if (fit.over) return VST_ERR_ARG;  // past the 32-bit buffer offsets (not chunked here): refuse
-  a.stride = 1; a.splits = 1;
   a.ablate = gemm_knobs().ablate;  // (reaches the kernel in the diagnostics build only, -DVST_P8_TRACE)
   a.group_m = gemm_knobs().group_m;
   const bool persist = bn == 320 && p8_lora_persist_on() && p8_persist_applies(M, N, K, 0, bn, false, (size_t)M * ldc * 2);
@@ -982,23 +866,12 @@ static int gemm_cross_attention_impl(const void* x, int ldx, const void* Acat, i
   if (!Acat && ldw < K) return VST_ERR_ARG;
   if (!xattn_ok(M, N, K, Acat, P, group_n, group_r, Nq, Nk)) return VST_ERR_UNSUPPORTED;
   if ((M / Nq - 1) / kv_div >= nkv_rows / Nk) return VST_ERR_ARG;  // every frame's text batch inside K/V
-  GemmArgs a{};
-  a.A1 = (const bf16_t*)x; a.lda1 = ldx; a.K1 = K;
-  a.Wt = (const bf16_t*)W; a.ldw = ldw; a.M = M; a.N = N; a.K = K;
-  a.bias = bias; a.C = (bf16_t*)O; a.ldc = ldo;
-  a.a1_bytes = fit(((size_t)(M - 1) * ldx + K) * 2);
-  a.w_bytes = fit(((size_t)(N - 1) * ldw + K) * 2);
-  if (Acat) {
-    a.wtail_bytes = fit(((size_t)(N - 1) * ldw + K + P) * 2);
-    a.la = (const bf16_t*)Acat; a.lda_la = ld_acat; a.la_p = P; a.la_gn = group_n; a.la_gr = group_r;
-    a.la_bytes = fit((size_t)P * ld_acat * 2);
-    if (gated) { a.gate = gate; a.ld_gate = ld_gate; a.gate_div = gate_div; }
-  }
+  GemmArgs a = dense_args(fit, x, ldx, K, W, ldw, M, N, K, bias, O, ldo);
+  if (Acat) lora_args(a, fit, Acat, ld_acat, P, group_n, group_r, gated, gate, ld_gate, gate_div);
   a.xa_k = (const bf16_t*)Kt; a.xa_v = (const bf16_t*)Vt; a.xa_ldkv = ldkv; a.xa_nk = Nk; a.xa_nq = Nq;
-  a.xa_kvdiv = kv_div; a.xa_scale_log2 = scale * 1.4426950408889634f;
+  a.xa_kvdiv = kv_div; a.xa_scale_log2 = scale * kLog2e;
   a.xa_kv_bytes = fit(((size_t)(nkv_rows - 1) * ldkv + N) * 2);
   if (fit.over) return VST_ERR_ARG;  // past the 32-bit buffer offsets (not chunked here): refuse
-  a.stride = 1; a.splits = 1;
   a.ablate = gemm_knobs().ablate;  // (diagnostics build only)
   return launch_gemm_p8_xattn(a, (hipStream_t)stream);
 }
@@ -1044,15 +917,9 @@ extern "C" int vst_gemm_temporal_attention(const void* x, int ldx, const void* W
   if ((ldx & 7) || (ldw & 7) || (ldo & 7) || ldx < K || ldw < K || ldo < heads * head_dim) return VST_ERR_ARG;
   if (!tattn_ok(M, K, nclip, F, HW, heads, head_dim)) return VST_ERR_UNSUPPORTED;
   const int N = heads / tattn_hpt(head_dim) * 256;
-  GemmArgs a{};
-  a.A1 = (const bf16_t*)x; a.lda1 = ldx; a.K1 = K;
-  a.Wt = (const bf16_t*)Wt; a.ldw = ldw; a.M = M; a.N = N; a.K = K;
-  a.bias = bias; a.C = (bf16_t*)O; a.ldc = ldo;
-  a.a1_bytes = fit(((size_t)(M - 1) * ldx + K) * 2);
-  a.w_bytes = fit(((size_t)(N - 1) * ldw + K) * 2);
+  GemmArgs a = dense_args(fit, x, ldx, K, Wt, ldw, M, N, K, bias, O, ldo);
   if (fit.over) return VST_ERR_ARG;  // past the 32-bit buffer offsets (not chunked here): refuse
-  a.ta_hw = HW; a.ta_heads = heads; a.ta_d = head_dim; a.ta_scale_log2 = scale * 1.4426950408889634f;
-  a.stride = 1; a.splits = 1;
+  a.ta_hw = HW; a.ta_heads = heads; a.ta_d = head_dim; a.ta_scale_log2 = scale * kLog2e;
   return launch_gemm_p8_tattn(a, (hipStream_t)stream);
 }
 
@@ -1074,8 +941,7 @@ extern "C" const char* vst_gemm_kernel_name(int M, int N, int K, int kind, int t
 // kernels (no split-K), so every row gets the bits of one launch (test_kernels_gpu.py::test_gemm_rows_past_2gb).
 static size_t row_extent(size_t rows, int ld, int cols) { return ((rows - 1) * (size_t)ld + (size_t)cols) * 2; }
 static int row_chunk(int M, size_t row_bytes, int align) {  // balanced rows per chunk (a multiple of align), 0: none
-  const size_t lim = 0x7fffffffULL;
-  const size_t fit = (lim / row_bytes) / (size_t)align * (size_t)align;
+  const size_t fit = (kMaxExtent / row_bytes) / (size_t)align * (size_t)align;
   if (fit == 0) return 0;
   const size_t n = ((size_t)M + fit - 1) / fit;
   const size_t rows = (((size_t)M + n - 1) / n + align - 1) / align * align;
@@ -1102,7 +968,7 @@ extern "C" int vst_gemm_ex(const void* A, int lda, const void* A2, int lda2, int
   if (row_bias && row_bias_div <= 0) return VST_ERR_ARG;
   {
     const int nout = epilogue == 1 ? N / 2 : N;
-    const size_t lim = 0x7fffffffULL;
+    const size_t lim = kMaxExtent;
     if (row_extent(M, lda, K1) > lim || (A2 && row_extent(M, lda2, K - K1) > lim) ||
         (R && row_extent(M, ldr, nout) > lim) || row_extent(M, ldc, nout) > lim) {
       const int wide = max(max(lda, A2 ? lda2 : 0), max(R ? ldr : 0, ldc));
@@ -1128,18 +994,14 @@ extern "C" int vst_gemm_ex(const void* A, int lda, const void* A2, int lda2, int
   q.tile = tile, q.splits = splits, q.slab_bytes = workspace ? ws_bytes : 0, q.c_bytes = (size_t)M * ldc * 2;
   const GemmPlan plan = plan_gemm(q);
   if (plan.family == kNone) return VST_ERR_ARG;
-  GemmArgs a{};
-  a.A1 = (const bf16_t*)A; a.A2 = (const bf16_t*)A2; a.lda1 = lda; a.lda2 = lda2; a.K1 = K1;
-  a.Wt = (const bf16_t*)W; a.ldw = ldw; a.M = M; a.N = N; a.K = K;
-  a.bias = bias; a.rbias = row_bias; a.rbias_div = row_bias_div; a.ldrb = ld_row_bias;
-  a.R = (const bf16_t*)R; a.ldr = ldr; a.C = (bf16_t*)C; a.ldc = ldc;
-  a.ws = (float*)workspace;
-  a.a1_bytes = fit(((size_t)(M - 1) * lda + K1) * 2);
+  GemmArgs a = dense_args(fit, A, lda, K1, W, ldw, M, N, K, bias, C, ldc);
+  a.A2 = (const bf16_t*)A2; a.lda2 = lda2;
   a.a2_bytes = A2 ? fit(((size_t)(M - 1) * lda2 + (K - K1)) * 2) : 0;
-  a.w_bytes = fit(((size_t)(N - 1) * ldw + K) * 2);
+  a.rbias = row_bias; a.rbias_div = row_bias_div; a.ldrb = ld_row_bias;
+  a.R = (const bf16_t*)R; a.ldr = ldr;
   a.r_bytes = R ? fit(((size_t)(M - 1) * ldr + N) * 2) : 0;
+  a.ws = (float*)workspace;
   if (fit.over) return VST_ERR_ARG;  // (A / R / C are chunked above; a weight past 2^31 - 1 bytes is refused)
-  a.C1 = 0; a.C2 = 0; a.stride = 1; a.up = 0;
   a.act = epilogue == 2 ? 1 : 0;
   return launch_plan(a, plan, (hipStream_t)stream);
 }
@@ -1172,7 +1034,7 @@ static int conv3x3_impl(const void* x1, int C1, const void* x2, int C2, int nimg
   a.OW = upsample ? 2 * W : pad0 ? (W - 2) / 2 + 1 : (stride == 2 ? (W + 1) / 2 : W);
   {  // byte extents past the 32-bit buffer offsets (vst_gemm_ex): chunks of whole images (a 3x3 tap never leaves its
      // image), equal in size
-    const size_t lim = 0x7fffffffULL, hw = (size_t)H * W, ohw = (size_t)a.OH * a.OW;
+    const size_t lim = kMaxExtent, hw = (size_t)H * W, ohw = (size_t)a.OH * a.OW;
     const size_t img_bytes = max(max(hw * C1, x2 ? hw * C2 : 0), max(R ? ohw * ldr : 0, ohw * ldc)) * 2;
     if ((size_t)nimg * img_bytes > lim) {
       if (colstat || (row_bias && row_bias_div != (int)ohw)) return VST_ERR_UNSUPPORTED;
@@ -1258,12 +1120,8 @@ extern "C" int vst_gemm_f32out(const void* A, int lda, const void* W, int ldw, i
   Fit31 fit;
   if (!A || !W || !C || M <= 0 || N <= 0 || K <= 0) return VST_ERR_ARG;
   if ((K & 7) || (lda & 7) || (ldw & 7) || (N & 3)) return VST_ERR_ARG;
-  GemmArgs a{};
-  a.A1 = (const bf16_t*)A; a.lda1 = lda; a.lda2 = lda; a.K1 = K;
-  a.Wt = (const bf16_t*)W; a.ldw = ldw; a.M = M; a.N = N; a.K = K;
-  a.C = nullptr; a.ldc = N; a.ws = C; a.splits = 1; a.stride = 1;
-  a.a1_bytes = fit(((size_t)(M - 1) * lda + K) * 2);
-  a.w_bytes = fit(((size_t)(N - 1) * ldw + K) * 2);
+  GemmArgs a = dense_args(fit, A, lda, K, W, ldw, M, N, K, nullptr, nullptr, N);
+  a.ws = C;  // (no bf16 output: the fp32 slab is the result)
   if (fit.over) return VST_ERR_ARG;  // past the 32-bit buffer offsets (not chunked here): refuse
   GemmQuery q{};
   q.M = M, q.N = N, q.K = q.K1 = K, q.epi = 2, q.splits = 1;  // the slab epilogue: a ring tile, one split

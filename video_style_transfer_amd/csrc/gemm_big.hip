@@ -1,7 +1,8 @@
 // LDS-DMA ring GEMM: the main bf16 MFMA GEMM of the denoise path (projections, GEGLU FF,
-// implicit-GEMM conv3x3, split-K partials).  Same contract as gemm.hip (GemmArgs, AMODE 0/1,
-// EPI 0/1/2).  Tiles (template): 256x256 and 256x128 (8 waves, 1 WG/CU), 128x128 and 128x64
-// (4 waves, 2-3 WG/CU).
+// implicit-GEMM conv3x3, split-K partials).  Operands: gemm_common.h (GemmArgs; template AMODE
+// 0 dense A, 1 conv A); epilogues: gemm_epilogue.h (EPI 0 / 1) and the fp32 split-K slab (EPI 2).
+// Tiles (template): 256x256 and 256x128 (8 waves, 1 WG/CU), 128x128 and 128x64 (4 waves,
+// 2-3 WG/CU).
 //
 // Staging: `buffer_load_dwordx4 ... lds` (__builtin_amdgcn_raw_ptr_buffer_load_lds) writes each
 // wave's 1 KiB piece (16 rows x 64 B) straight into LDS; the buffer range check supplies the
@@ -130,14 +131,8 @@ __device__ __forceinline__ void ring_tile(const GemmArgs& p, char* smem, const i
     if (AMODE == 0) {
       rowA[q] = m < p.M ? m : -1;
       oyv[q] = oxv[q] = 0;
-    } else if (m < p.M) {
-      const int hw = p.OH * p.OW;
-      const int img = m / hw, rem = m - img * hw;
-      rowA[q] = img;
-      oyv[q] = rem / p.OW;
-      oxv[q] = rem - oyv[q] * p.OW;
     } else {
-      rowA[q] = -1; oyv[q] = oxv[q] = 0;
+      conv_row(p, m, rowA[q], oyv[q], oxv[q]);  // rowA: the image
     }
   }
   int rowB[Cfg::B_PIECES + 1];
@@ -184,17 +179,9 @@ __device__ __forceinline__ void ring_tile(const GemmArgs& p, char* smem, const i
     run_ci0 = second ? p.C1 : 0;
 #pragma unroll
     for (int q = 0; q < AQ; ++q) {
-      int iy, ix;
-      bool ok = rowA[q] >= 0;
-      if (p.up) {
-        const int uy = oyv[q] + ky - 1, ux = oxv[q] + kx - 1;
-        ok = ok && uy >= 0 && uy < 2 * p.H && ux >= 0 && ux < 2 * p.W;
-        iy = uy >> 1; ix = ux >> 1;
-      } else {
-        iy = oyv[q] * p.stride + ky - 1 + p.pad0; ix = oxv[q] * p.stride + kx - 1 + p.pad0;
-        ok = ok && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
-      }
-      bA[q] = ok ? (uint32_t)(((rowA[q] * p.H + iy) * p.W + ix) * cs + lchunk * 8) * 2u : (uint32_t)kOOB;
+      int px;
+      const bool ok = conv_tap_pixel(p, rowA[q], oyv[q], oxv[q], ky, kx, px);
+      bA[q] = ok ? (uint32_t)(px * cs + lchunk * 8) * 2u : (uint32_t)kOOB;
     }
   };
   int offs[Cfg::DPT];

@@ -1,4 +1,15 @@
-// Shared GEMM argument block and LDS swizzle (gemm.hip, gemm_big.hip).
+// Shared by every GEMM / 3x3-conv kernel (gemm.hip, gemm_big.hip, gemm_p8.hip through gemm_plan.h and
+// gemm_epilogue.h): the argument block, the 128-byte-row LDS swizzle and the implicit-GEMM conv geometry.
+//
+// Operands.  C[M, N] = epilogue(A[M, K] . W[N, K]^T), bf16 in, fp32 accumulate.  W is nn.Linear layout ([out, in], K
+// contiguous), so both operands are K-contiguous and an MFMA fragment is one 16-byte LDS read.
+//   dense A: rows of A1 for k < K1 and of A2 after (K1 a multiple of 64).  The split carries channel concatenation
+//     without a copy, and the UnZipLoRA low-rank delta as extra K columns: [x | x.Acat^T] . [W | s.(B (.) m)]^T =
+//     x W^T + s.Delta(x) (unziplora_linear_layer.py:298-346).
+//   conv A: implicit-GEMM 3x3 conv over NHWC activations (per-frame SDXL conv, diffusers ResnetBlock2D /
+//     Downsample2D / Upsample2D): K = (ky, kx, ci), zero padding through out-of-range buffer loads, stride 1 / 2,
+//     fused nearest-2x upsample, two-source channel concat (up-block skip connections); conv_row / conv_tap_pixel.
+// The epilogues and their rounding points: gemm_epilogue.h.
 #pragma once
 #include "vst_common.h"
 
@@ -7,7 +18,7 @@ namespace vst {
 struct GemmArgs {
   const bf16_t* A1; const bf16_t* A2;
   int lda1, lda2, K1;
-  // conv geometry (AMODE 1/2): input NHWC [nimg, H, W, C1 (+C2)] -> output [nimg, OH, OW, N]
+  // conv geometry: input NHWC [nimg, H, W, C1 (+C2)] -> output [nimg, OH, OW, N]
   int H, W, C1, C2, OH, OW, stride, up;
   int pad0;  // 1: no top/left padding (F.pad (0,1,0,1) + stride-2 conv of diffusers Downsample2D(padding=0))
   const bf16_t* Wt; int ldw;
@@ -21,9 +32,10 @@ struct GemmArgs {
   int act;     // EPI 0 only: 1 = GELU(erf) after the bias (TemporalTransformerBlock ffn, no residual / row bias)
   int persist;  // > 0: persistent launch over `persist` CUs (VST_GEMM_PERSIST; 0 = one workgroup per tile)
   int group_m;  // grouped tile order: row panels per group (0 = default 8; VST_GEMM_GROUP_M for tuning)
-  int p8_bn;   // unused (the tile width travels in the host's GemmPlan); kept for the layout
   int ablate;  // diagnostics only (VST_GEMM_ABLATE): bit0 skip loop DMA, bit1 skip MFMA
-  uint32_t a1_bytes, a2_bytes, w_bytes, r_bytes;
+  // byte extents of A1 / A2 / W / R for the buffer descriptors; 16-byte aligned so that one scalar load fetches the four
+  alignas(16) uint32_t a1_bytes;
+  uint32_t a2_bytes, w_bytes, r_bytes;
   // in-GEMM LoRA down-projection (gemm_p8.hip LORA, vst_gemm_lora): Acat [la_p][K] bf16 (row stride lda_la); the
   // output columns of group g = n / la_gn use u columns [g la_gr, (g + 1) la_gr), whose up-projection sits in W's
   // columns K + that range (ldw >= K + la_p); wtail_bytes covers those columns
@@ -54,6 +66,38 @@ struct GemmArgs {
 
 __device__ __forceinline__ int swz(int row, int chunk) {
   return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4);
+}
+
+// 3x3 conv geometry, one copy for every implicit-GEMM A loader.  Output row m -> (img, oy, ox); img = -1 past M.
+__device__ __forceinline__ void conv_row(const GemmArgs& p, const int m, int& img, int& oy, int& ox) {
+  if (m < p.M) {
+    const int hw = p.OH * p.OW;
+    img = m / hw;
+    const int rem = m - img * hw;
+    oy = rem / p.OW;
+    ox = rem - oy * p.OW;
+  } else {
+    img = -1; oy = ox = 0;
+  }
+}
+
+// px = the input pixel (img * H + iy) * W + ix that tap (ky, kx) of output pixel (img, oy, ox) reads; false where
+// the tap falls into the padding or img < 0 (px is then not to be used: the caller loads out of range, i.e. zeros).
+// up: nearest-2x upsample first; pad0: no top / left padding.
+__device__ __forceinline__ bool conv_tap_pixel(const GemmArgs& p, const int img, const int oy, const int ox,
+                                               const int ky, const int kx, int& px, const bool live = true) {
+  int iy, ix;
+  bool ok = live && img >= 0;
+  if (p.up) {
+    const int uy = oy + ky - 1, ux = ox + kx - 1;
+    ok = ok && uy >= 0 && uy < 2 * p.H && ux >= 0 && ux < 2 * p.W;
+    iy = uy >> 1; ix = ux >> 1;
+  } else {
+    iy = oy * p.stride + ky - 1 + p.pad0; ix = ox * p.stride + kx - 1 + p.pad0;
+    ok = ok && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
+  }
+  px = (img * p.H + iy) * p.W + ix;
+  return ok;
 }
 
 }  // namespace vst

@@ -2,6 +2,11 @@
 // staged once in LDS, then per-frame row bias / residual add (after that rounding, as the reference's separate add
 // does) or GEGLU, written as full 16-B chunks.  acc[i][j][r] = C[m0 + wr*WM + i*16 + (lane&15)][n0 + wc*WN + j*16 +
 // 4*(lane>>4) + r] (the W fragment is the MFMA's A operand).
+// Epilogue codes (GemmPlan::epi): 0 = +bias[n], round to bf16, +row_bias[m / div][n] +residual[m, n] -> bf16 (the small
+// kernels of gemm.hip round at the same points); 1 = GEGLU: of every 64 columns, [0, 32) are the hidden and [32, 64) the
+// gate values of the same 32 outputs (the host interleaves the weight rows accordingly), out = bf16(h + bh) *
+// gelu(bf16(g + bg)); 2 = the fp32 split-K slab (gemm_big.hip; the epilogue then runs in gemm_splitk_reduce_kernel);
+// 3 = bias + GELU.
 #pragma once
 #include "gemm_common.h"
 

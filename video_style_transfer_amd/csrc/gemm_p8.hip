@@ -1,5 +1,5 @@
 // 8-phase 256x256x64 GEMM (projections / GEGLU FF of the denoise path; same GemmArgs contract and epilogues as the
-// ring kernel in gemm_big.hip, AMODE 0 only: A = [A1 | A2] split at K1, W row-major [N][K]).
+// ring kernel in gemm_big.hip, dense A only: A = [A1 | A2] split at K1, W row-major [N][K]).
 //
 // Why: the ring kernel runs 32-deep k-steps with two barriers per 32 MFMAs per wave; its MFMA + barrier skeleton
 // alone reaches ~60 % of peak.  This kernel takes 64-deep k-tiles, two LDS buffers, and splits each
@@ -107,8 +107,6 @@ __device__ __forceinline__ void p8_dma16(__amdgpu_buffer_rsrc_t r, char* lds_pie
   __builtin_amdgcn_raw_ptr_buffer_load_lds(
       r, (p8_lds_void*)((__attribute__((address_space(3))) char*)(uintptr_t)lds_piece), 16, off, 0, 0, 0);
 }
-
-__device__ __forceinline__ int p8_off(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
 
 __device__ __forceinline__ void p8_barrier() {
   __builtin_amdgcn_sched_barrier(0);
@@ -685,7 +683,7 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_kernel(GemmArgs p) {
         if (s < 2) {
           const int m = m0 + (r / HALF) * Cfg::WM + s * HALF + (r % HALF);
           if constexpr (CONV) {
-            if (pc < NPA) {
+            if (pc < NPA) {  // conv_row (gemm_common.h), but oy / ox left unmasked past M: the measured code
               const int hw = p.OH * p.OW;
               const int img = m / hw, rem = m - img * hw;
               cv_img[s][pc] = m < p.M ? img : -1;
@@ -718,17 +716,9 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_kernel(GemmArgs p) {
     cv_ci0[s] = cv_second[s] ? p.C1 : 0;
 #pragma unroll
     for (int pc = 0; pc < NPA; ++pc) {
-      int iy, ix;
-      bool ok = cv_img[s][pc] >= 0;
-      if (p.up) {
-        const int uy = cv_oy[s][pc] + ky - 1, ux = cv_ox[s][pc] + kx - 1;
-        ok = ok && uy >= 0 && uy < 2 * p.H && ux >= 0 && ux < 2 * p.W;
-        iy = uy >> 1; ix = ux >> 1;
-      } else {
-        iy = cv_oy[s][pc] * p.stride + ky - 1 + p.pad0; ix = cv_ox[s][pc] * p.stride + kx - 1 + p.pad0;
-        ok = ok && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
-      }
-      base1[s][pc] = ok ? (uint32_t)(((cv_img[s][pc] * p.H + iy) * p.W + ix) * cs + c8[s][pc]) * 2u : (uint32_t)kOOB;
+      int px;
+      const bool ok = conv_tap_pixel(p, cv_img[s][pc], cv_oy[s][pc], cv_ox[s][pc], ky, kx, px);
+      base1[s][pc] = ok ? (uint32_t)(px * cs + c8[s][pc]) * 2u : (uint32_t)kOOB;
     }
     cv_rebase[s] = false;
   };
@@ -842,7 +832,7 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_kernel(GemmArgs p) {
     for (int i = 0; i < MQR; ++i) {
       const int ib = LORA ? ((i + wc) & (MQR - 1)) : i;  // (MQR < 4: waves wc >= MQR repeat a block, their u unused)
 #pragma unroll
-      for (int h = 0; h < 2; ++h) fa[i][h] = *reinterpret_cast<const bf16x8*>(S + p8_off(wr * HALF + ib * 16 + fr, h * 4 + fq));
+      for (int h = 0; h < 2; ++h) fa[i][h] = *reinterpret_cast<const bf16x8*>(S + swz(wr * HALF + ib * 16 + fr, h * 4 + fq));
     }
   };
   auto read_b = [&](int buf, int nq, auto& fb) {
@@ -852,14 +842,14 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_kernel(GemmArgs p) {
 #pragma unroll
     for (int j = 0; j < (nq == 0 ? 2 : NJ1); ++j)
 #pragma unroll
-      for (int h = 0; h < 2; ++h) fb[j][h] = *reinterpret_cast<const bf16x8*>(S + p8_off(wc * rb + j * 16 + fr, h * 4 + fq));
+      for (int h = 0; h < 2; ++h) fb[j][h] = *reinterpret_cast<const bf16x8*>(S + swz(wc * rb + j * 16 + fr, h * 4 + fq));
   };
   auto read_l = [&](int buf) {
     if (abl & 16) return;
     if constexpr (LORA) {
       const char* S = smem + Cfg::LORA_OFF + buf * 2048;
 #pragma unroll
-      for (int h = 0; h < 2; ++h) fl[h] = *reinterpret_cast<const bf16x8*>(S + p8_off(fr, h * 4 + fq));
+      for (int h = 0; h < 2; ++h) fl[h] = *reinterpret_cast<const bf16x8*>(S + swz(fr, h * 4 + fq));
     }
   };
   // LORA: u rows of row block wc of the current row quadrant

@@ -10,7 +10,7 @@ enum GemmFamily {
   kNone = 0,  // the request is not legal (VST_ERR_ARG; VST_ERR_UNSUPPORTED for a column-statistics conv)
   kRows,      // gemm_rows_kernel, M <= 8
   kSkinny,    // gemm_skinny_kernel, N <= 64, no epilogue
-  kGather,    // gemm_kernel<2, 0, 64>: scalar-gather conv (channels not a multiple of 64)
+  kGather,    // conv_gather_kernel: scalar-gather conv (channels not a multiple of 64)
   kRing,      // gemm_ring_kernel (gemm_big.hip); conv: its implicit-GEMM A loader
   kP8,        // gemm_p8_kernel (gemm_p8.hip)
   kP8Conv,    // gemm_p8_kernel, implicit-GEMM 3x3 conv
