@@ -21,7 +21,7 @@
  *     and so are fp32 vectors read as float4 (bias, row_bias, gamma, beta, pe, lse).  Bases at smaller offsets
  *     are outside the contract; only vst_gemm_tn checks its output pointer (8 bytes) and refuses;
  *   - operands WITHOUT a row stride in their signature are contiguous: conv inputs x1 / x2 ([nimg*H*W][C]) and
- *     conv weights ([Cout][9*(C1+C2)], rows padded to 8), bias / gamma / beta / pe / table, lse, colstat and
+ *     conv weights ([Cout][9*(C1+C2)], rows padded to 8), bias / gamma / beta / pe / table, lse and
  *     GroupNorm partials, every workspace, vst_permute_rows / vst_silu / vst_add / vst_quick_gelu operands,
  *     vst_gemm_f32out's C, vst_colsum's y, the dgamma / dbeta vectors, the fp32 NCHW / latent tensors;
  *   - an output is written exactly on [rows) x [cols) of its view and nowhere else: no guard row or column is
@@ -163,13 +163,6 @@ int vst_conv3x3_ex(const void* x1, int C1, const void* x2, int C2, int nimg, int
                    const void* Wt, int Cout, const float* bias, const float* row_bias, int row_bias_div,
                    int ld_row_bias, const void* R, int ldr, void* out, int ldc, int tile, int splits, void* workspace,
                    size_t ws_bytes, void* stream);
-/* + the GroupNorm column statistics of the stored output, colstat [ceil(M/128)][Cout][2] fp32 (sum, sum of squares
- * per 128-row tile and channel) for vst_groupnorm_colstat; returns 3 (unsupported, nothing launched) unless the
- * conv runs on the 8-phase kernel's 128x320 tiles (Cout % 320 == 0). */
-int vst_conv3x3_colstat(const void* x1, int C1, const void* x2, int C2, int nimg, int H, int W, int stride,
-                        int upsample, const void* Wt, int Cout, const float* bias, const float* row_bias,
-                        int row_bias_div, int ld_row_bias, const void* R, int ldr, void* out, int ldc,
-                        float* colstat, void* stream);
 
 /* Spatial SDPA, head_dim 64: replaces F.scaled_dot_product_attention in
  * AnimateDiffAttnProcessor2_0.__call__ (animatediff/attention_processor.py:78-80).  K/V row
@@ -214,34 +207,11 @@ int vst_temporal_attention_windowed(const void* q, const void* k, const void* v,
                                     int F, int HW, int heads, int head_dim, int L, int S, int weighting, float scale,
                                     void* stream);
 
-/* One attention half of a motion-module BasicTransformerBlock in ONE launch (the fused temporal block of SURVEY
- * §8(d)):  y = x + to_out(softmax_over_frames(q k^T * scale) v),  [q | k | v] = (LayerNorm(x) + pe[frame]) . wqkv^T
- * (+ bqkv), to_out = . wo^T + bo; token (clip b, frame f, pixel p) at row (b*F + f)*HW + p; pe: [F][C] fp32 or NULL.
- * Replaces norm1/norm2 (+ the sinusoidal PE, animatediff/temporal_transformer.py:11-27), attn1/attn2 with the default
- * processor and the residual add of the motion module's BasicTransformerBlock (unziplora_unet/unzip_attention.py:
- * 150-151, 196-197; core: temporal_transformer.py:66-68).  C = 320 (the 64x64 level), 8 heads, F = 16, HW % 8 == 0;
- * returns 3 (VST_ERR_UNSUPPORTED) otherwise, which _supported answers without a launch.  Out of place (y != x).
- * The UNet uses it only with VST_MOTION_FUSE=1: it measured slower than the four launches. */
-int vst_motion_attention_block(const void* x, int ldx, int nclip, int F, int HW, int C, int heads, const float* gamma,
-                               const float* beta, float eps, const float* pe, const void* wqkv, int ldw,
-                               const float* bqkv, const void* wo, int ldwo, const float* bo, float scale, void* y,
-                               int ldy, void* stream);
-int vst_motion_attention_block_supported(int C, int F, int HW, int heads);
-
 /* GroupNorm (+SiLU) over NHWC samples of rows_per_sample rows; optional 2-source channel concat. */
 size_t vst_groupnorm_workspace_bytes(int nsamples, int rows_per_sample, int groups, int C);
 int vst_groupnorm(const void* x1, int ld1, int C1, const void* x2, int ld2, int C2, int nsamples,
                   int rows_per_sample, int groups, float eps, const float* gamma, const float* beta, int silu_act,
                   void* y, int ldy, void* workspace, void* stream);
-/* Column statistics of x [M, C] (C % 8 == 0) in the arithmetic of vst_conv3x3_colstat's epilogue, cs
- * [ceil(M/128)][C][2] fp32: for a GroupNorm input whose producer did not write them (same bits if it had). */
-int vst_colstat(const void* x, int ldx, int M, int C, float* cs, void* stream);
-/* vst_groupnorm with its statistics from the column statistics the producing conv wrote (vst_conv3x3_colstat;
- * cs2 for x2's channels), so the GroupNorm does not read x for them: rows_per_sample % 128 == 0. */
-int vst_groupnorm_colstat(const void* x1, int ld1, int C1, const float* cs1, const void* x2, int ld2, int C2,
-                          const float* cs2, int nsamples, int rows_per_sample, int groups, float eps,
-                          const float* gamma, const float* beta, int silu_act, void* y, int ldy, void* workspace,
-                          void* stream);
 
 /* GroupNorm (+SiLU) over NHWC samples of rows_per_sample rows; a frame's statistics depend only on its own rows
  * (the chunking is a function of rows_per_sample, not of how many samples share the launch). */

@@ -1,6 +1,6 @@
 """CPU tests of the host-side fusion policy (no launch, no GPU): which SDXL projections take the in-GEMM UnZipLoRA
-down-projection (vst_gemm_lora), which attn2 calls run as one launch (vst_gemm_cross_attention), which motion-module
-shapes the fused attention block accepts, and the operand grouping build_ops hands them."""
+down-projection (vst_gemm_lora), which attn2 calls run as one launch (vst_gemm_cross_attention), and the operand
+grouping build_ops hands them."""
 import pytest
 import torch
 
@@ -63,19 +63,3 @@ def test_cross_attention_fusion_policy():
         assert not AP._cross_fusable(ops, 32 * 320, 320, 77)
     plain = AP.Attention(1280, 2048, 20, 64)
     assert AP._cross_fusable(build_ops([plain.to_q], 1.0), 8192, 256, 77)
-
-
-def test_motion_block_policy_is_opt_in(monkeypatch):
-    """The fused motion attention block accepts the 64x64 level only and is used only with VST_MOTION_FUSE=1."""
-    from video_style_transfer_amd import kernels as K
-    from video_style_transfer_amd.unet_motion import BasicTransformerBlock, _fused_motion_ops_impl
-    assert K.motion_block_fusable(320, 16, 4096, 8) and not K.motion_block_fusable(640, 16, 1024, 8)
-    blk = BasicTransformerBlock(320, 8, 40, None, temporal=True)
-    for p in blk.parameters():
-        p.requires_grad_(False)
-    monkeypatch.delenv("VST_MOTION_FUSE", raising=False)
-    assert _fused_motion_ops_impl(blk, 320, 16, 4096) is None
-    monkeypatch.setenv("VST_MOTION_FUSE", "1")
-    ops = _fused_motion_ops_impl(blk, 320, 16, 4096)
-    assert ops is not None and [o.w.shape for pair in ops for o in pair] == [(960, 320), (320, 320)] * 2
-    assert _fused_motion_ops_impl(blk, 320, 32, 4096) is None  # 32 frames (configs[3])

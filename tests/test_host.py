@@ -53,54 +53,6 @@ def test_gemm_tn_refuses_misaligned_output_without_gpu():
     assert lib.vst_gemm_tn(A, 8, B, 8, 64, 8, 8, None, 8, None, 0, None) == 1    # no output
 
 
-def test_wrote_drops_colstat_of_overlapping_views():
-    """kernels._wrote (called for every out= a wrapper hands to a kernel) drops the GroupNorm column statistics of
-    every registered tensor that shares storage bytes with the written view: a launch into out=t[4:] overwrites rows
-    of t, whose entry is keyed by t.data_ptr(), not by the view's.  Writes to other storage, or to bytes of the same
-    storage that t does not cover, leave the entry alone."""
-    import weakref
-    from video_style_transfer_amd import kernels as K
-    K.colstat_reset()
-    cs = torch.zeros(1, 64, 2)
-
-    def register(t):
-        K._COLSTAT[t.data_ptr()] = (weakref.ref(t), t._version, cs)
-
-    t = torch.zeros(8, 64, dtype=torch.bfloat16)
-    register(t)
-    K._wrote(t[4:])
-    assert K.colstat_of(t) is None
-    register(t)
-    K._wrote(t[2:3, 8:16])                                   # a block inside t
-    assert K.colstat_of(t) is None
-    register(t)
-    K._wrote(torch.zeros(8, 64, dtype=torch.bfloat16))       # a disjoint tensor
-    assert K.colstat_of(t) is cs
-    K._wrote(None)
-    assert K.colstat_of(t) is cs
-    # the registered tensor is itself a view: writes to its neighbours in the same storage do not touch it ...
-    big = torch.zeros(24, 64, dtype=torch.bfloat16)
-    mid = big[8:16]
-    K.colstat_reset()
-    register(mid)
-    K._wrote(big[:8])
-    K._wrote(big[16:])
-    assert K.colstat_of(mid) is cs
-    K._wrote(big[15:17])                                     # ... one that reaches into its last row does
-    assert K.colstat_of(mid) is None
-    register(mid)
-    K._wrote(big.view(torch.int16)[0:9])                     # (another dtype over the same bytes)
-    assert K.colstat_of(mid) is None
-    # an entry whose tensor died is dropped on the way
-    dead = torch.zeros(8, 64, dtype=torch.bfloat16)
-    register(dead)
-    key = dead.data_ptr()
-    del dead
-    K._wrote(t)
-    assert key not in K._COLSTAT
-    K.colstat_reset()
-
-
 def test_out_validation_is_host_side():
     """Every wrapper validates out= before it touches the library: a wrong dtype, width, rank or column stride raises
     VstError naming the argument (here on CPU tensors, so the device check fires first for those; the shape / dtype
@@ -321,33 +273,3 @@ def test_text_encoder_surface_cpu():
         assert ours == set(model.state_dict())
         with pytest.raises(_lib.VstError):
             model(torch.zeros(1, 77, dtype=torch.long))
-
-
-def test_colstat_registry_host_logic():
-    """kernels.colstat_of (the GroupNorm column-statistics hand-off, opt-in VST_GN_COLSTAT): an entry is valid only
-    for the very tensor its conv wrote -- same storage, shape and strides, not modified since, still alive -- and
-    colstat_reset() drops every entry (each UNet forward starts with it)."""
-    import weakref
-    from video_style_transfer_amd import kernels as K
-    K.colstat_reset()
-    out = torch.zeros(256, 320, dtype=torch.bfloat16)
-    cs = torch.zeros(2, 320, 2)
-    K._COLSTAT[out.data_ptr()] = (weakref.ref(out), out._version, cs)
-    assert K.colstat_of(out) is cs
-    assert K.colstat_of(out.view(128, 640)) is None          # another shape over the same storage
-    assert K.colstat_of(out[:, :160]) is None                # a column slice (other strides)
-    assert K.colstat_of(None) is None
-    out.add_(1)                                              # modified after the conv wrote it
-    assert K.colstat_of(out) is None
-    K._COLSTAT[out.data_ptr()] = (weakref.ref(out), out._version, cs)
-    assert K.colstat_of(out) is cs
-    K.colstat_reset()
-    assert K.colstat_of(out) is None
-    # a raw-pointer write into the tensor (a K.* wrapper given out=, which does not bump _version) drops the entry
-    K._COLSTAT[out.data_ptr()] = (weakref.ref(out), out._version, cs)
-    K._wrote(out)
-    assert K.colstat_of(out) is None
-    K._COLSTAT[out.data_ptr()] = (weakref.ref(out), out._version, cs)
-    with pytest.raises(K._lib.VstError):                     # _dev(out, ...) drops it too (then refuses the CPU tensor)
-        K._dev(out, torch.bfloat16, "out")
-    assert K.colstat_of(out) is None

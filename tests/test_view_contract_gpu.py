@@ -468,34 +468,6 @@ def temporal_spec(nclip, Fr, HW, C):
     return Spec(ins, {"out": (rows, C, BF16, "view")}, run, ref, fused={"qkv": ["q", "k", "v"]})
 
 
-def motion_block_spec(nclip, HW):
-    C, heads, Fr = 320, 8, 16
-    g = gen("motion", nclip, HW)
-    T = nclip * Fr * HW
-    ins = {"x": (rnd(T, C, scale=0.7, g=g), "view"),
-           "gamma": (1.0 + 0.1 * torch.randn(C, generator=g), "contig"),
-           "beta": (0.1 * torch.randn(C, generator=g), "contig"),
-           "pe": (0.5 * torch.randn(32, C, generator=g), "contig"),
-           "wqkv": (rnd(3 * C, C, scale=C ** -0.5, g=g), "view"),
-           "bqkv": (0.1 * torch.randn(3 * C, generator=g), "contig"),
-           "wo": (rnd(C, C, scale=0.25 * C ** -0.5, g=g), "view"),
-           "bo": (0.05 * torch.randn(C, generator=g), "contig")}
-
-    def run(K, t):
-        assert K.motion_block_fusable(C, Fr, HW, heads)
-        K.motion_attention_block(t["x"], nclip, Fr, HW, heads, t["gamma"], t["beta"], 1e-5, t["pe"], t["wqkv"],
-                                 t["bqkv"], t["wo"], t["bo"], out=t["out"])
-
-    def ref(i):
-        xf = i["x"].float()
-        n = F.layer_norm(xf, (C,), i["gamma"], i["beta"], 1e-5) + i["pe"][:Fr].repeat_interleave(HW, 0).repeat(nclip, 1)
-        qkv = n @ i["wqkv"].float().t() + i["bqkv"]
-        o = seq_attn_ref(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], nclip, Fr, HW, heads, C // heads)
-        return {"out": xf + o @ i["wo"].float().t() + i["bo"]}
-
-    return Spec(ins, {"out": (T, C, BF16, "view")}, run, ref)
-
-
 def gn_ref(x, ns, rps, gam, bet, eps, silu):
     C = x.shape[1]
     y = F.group_norm(x.float().view(ns, rps, C).permute(0, 2, 1), 32, gam, bet, eps).permute(0, 2, 1).reshape(-1, C)
@@ -787,7 +759,6 @@ for _on in (True, False):
     case(f"spatial_attention-cross-sa{int(_on)}", spatial_spec, 2, 2, 100, 77, 2, _on)
 case("temporal_attention-3x5x7x64", temporal_spec, 3, 5, 7, 64)
 case("temporal_attention-1x16x8x80", temporal_spec, 1, 16, 8, 80)
-case("motion_attention_block", motion_block_spec, 1, 64)
 
 for _rows in (70, 300):
     for _C in (64, 320):
@@ -825,7 +796,7 @@ OUT_ARGS = [
     ("linear-ring-t1-bias", "out"), ("linear_lora-w192", "out"), ("linear_cross_attention-lora0", "out"),
     ("linear_temporal_attention-h2d40", "out"), ("conv3x3-64to320-s1-t0s0", "out"), ("conv3x3_down_pad0", "out"),
     ("spatial_attention-cross-sa1", "out"), ("spatial_attention-cross-sa1", "lse"),
-    ("temporal_attention-3x5x7x64", "out"), ("motion_attention_block", "out"), ("group_norm-70x64-silu0", "out"),
+    ("temporal_attention-3x5x7x64", "out"), ("group_norm-70x64-silu0", "out"),
     ("group_norm_apply_partials-70x64", "out"), ("layer_norm-70x64", "out"), ("layer_norm_lora-70x64", "out"),
     ("layer_norm_lora-70x64", "u"), ("add_row_table-70x64", "out"), ("permute_rows-70x64", "out"),
     ("transpose-70x64", "out"), ("copy2d-70x64", "out"), ("softmax_rows-70x64", "out"), ("gemm_f32out-70x64", "out"),
@@ -873,27 +844,3 @@ def test_elementwise_out_is_validated(cuda, K):
     torch.cuda.synchronize()
     verify_out("bf16 arena", full, GUARD_TOP, GUARD_COL, 16, 64, untouched=True)
     verify_out("fp32 buffer", full32, GUARD_TOP, 0, 16, 64, untouched=True)
-
-
-# ---------------------------------------------------------------- column statistics follow the written bytes
-def test_colstat_dropped_by_write_into_offset_view(cuda, K, monkeypatch):
-    """A conv registers GroupNorm column statistics for its output t; a later launch into out=t[128:] overwrites
-    rows of t through a raw pointer at another data_ptr(): the entry must go, and group_norm_stats(t) must be the
-    statistics of the bytes now in t."""
-    monkeypatch.setenv("VST_GN_COLSTAT", "1")
-    g = gen("colstat")
-    n, H, W, Ci, Co = 11, 32, 32, 64, 640  # 11264 rows x 640: the 8-phase 128x320 conv tiles write the statistics
-    x = rnd(n * H * W, Ci, g=g).to(cuda)
-    w = wflat(rnd(Co, Ci, 3, 3, scale=(9 * Ci) ** -0.5, g=g)).to(cuda)
-    K.colstat_reset()
-    t = K.conv3x3(x, n, H, W, w, None, colstat=True)
-    cs = K.colstat_of(t)
-    assert cs is not None and torch.equal(cs, K.colstat(t))
-    a, b = rnd(n * H * W - 128, Co, g=g).to(cuda), rnd(n * H * W - 128, Co, g=g).to(cuda)
-    K.add(a, b, out=t[128:])
-    assert K.colstat_of(t) is None
-    fresh = K.colstat(t)
-    assert torch.equal(K.group_norm_stats(t)[0], fresh)
-    assert torch.equal(fresh[0], cs[0]) and not torch.equal(fresh[1:], cs[1:])  # rows [0, 128) kept, the rest new
-    check(t[128:], a.float() + b.float(), FWD, "add into the offset view")
-    K.colstat_reset()

@@ -7,8 +7,7 @@ mkdir -p gpurun_out
 for tag in "$@"; do
   base=$(echo $tag | sed 's/[0-9]*$//')  # trailing digits: repeats of the same build
   unset VST_GEMM_P8
-  unset VST_LN_GENERIC VST_P8_BN VST_CFG_STREAMS VST_LORA_INGEMM VST_XATTN_FUSE VST_MOTION_FUSE
-  if [ "$base" = motionfuse ]; then export VST_MOTION_FUSE=1; base=new; fi  # fused motion attention blocks (opt-in)
+  unset VST_LN_GENERIC VST_P8_BN VST_CFG_STREAMS VST_LORA_INGEMM VST_XATTN_FUSE
   if [ "$base" = noxattn ]; then export VST_XATTN_FUSE=0; base=new; fi  # attn2 as q GEMM + attention kernel
   if [ "$base" = nolora ]; then export VST_LORA_INGEMM=0; base=new; fi  # LoRA down-projection as its own pass
   if [ "$base" = cfgstreams ]; then export VST_CFG_STREAMS=1; base=new; fi  # CFG branches on two streams (B=1 each)

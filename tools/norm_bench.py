@@ -28,7 +28,6 @@ GN = [(32, 4096, 320, 0, 1), (32, 4096, 320, 320, 1), (32, 4096, 640, 320, 1), (
       (2, 9, 64, 0, 0), (5, 77, 640, 320, 1), (3, 700, 4096, 0, 0)]
 # (P, nclip, F, HW, C): motion-module GroupNorm as frame partials + apply (P ranks' partials, rank 0's rows applied)
 GN_PARTS = [(1, 2, 16, 4096, 320), (1, 2, 16, 1024, 640), (1, 2, 16, 256, 1280), (2, 3, 4, 100, 64), (8, 1, 32, 576, 640)]
-GN_COLSTAT = [(32, 1024, 640, 320)]           # (ns, rps, C1, C2), statistics from K.colstat
 GN_BWD = [(3, 77, 64, 1), (4, 256, 640, 1)]   # (ns, rps, C, silu)
 # (rows, C, pe): the step's LayerNorms, then the edge shapes (C = 64 / 768 / 2048: generic kernel, 1 / 2 / 4 chunks)
 LN = [(131072, 320, 0), (32768, 640, 0), (8192, 1280, 0),
@@ -130,17 +129,6 @@ def cases(generic):
             c.report(fn, (P + 2) * 2.0 * nclip * Fl * HW * C)
         return f"gn_parts_P{P}_{nclip}x{Fr}x{HW}x{C}", run
 
-    def gn_colstat(ns, rps, C1, C2):
-        def run(c):
-            x1, x2 = c.bf(ns * rps, C1, shift=0.5), c.bf(ns * rps, C2)
-            gam, bet = c.affine(C1 + C2)
-            cs = (K.colstat(x1), K.colstat(x2))
-            out = torch.empty(ns * rps, C1 + C2, dtype=BF16, device=DEV)
-            c.report(lambda: {"cs1": cs[0], "cs2": cs[1],
-                              "y": K.group_norm(x1, ns, rps, 32, 1e-5, gam, bet, silu=True, x2=x2, out=out,
-                                                colstat=cs)}, 2 * 2.0 * ns * rps * (C1 + C2))
-        return f"gn_colstat_{ns}x{rps}x{C1}+{C2}", run
-
     def gn_bwd(ns, rps, C, act):
         def run(c):
             x, g = c.bf(ns * rps, C, shift=0.5), c.bf(ns * rps, C)
@@ -168,8 +156,8 @@ def cases(generic):
                      3 * 2.0 * rows * C)
         return f"ln_bwd_{rows}x{C}" + ("_affine" if affine else ""), run
 
-    return ([gn(*a) for a in GN] + [gn_parts(*a) for a in GN_PARTS] + [gn_colstat(*a) for a in GN_COLSTAT] +
-            [gn_bwd(*a) for a in GN_BWD] + [ln(*a) for a in LN] + [ln_lora(*a) for a in LN_LORA] +
+    return ([gn(*a) for a in GN] + [gn_parts(*a) for a in GN_PARTS] + [gn_bwd(*a) for a in GN_BWD] +
+            [ln(*a) for a in LN] + [ln_lora(*a) for a in LN_LORA] +
             [ln_bwd(r, C, aff) for r, C in LN_BWD for aff in (True, False)])
 
 

@@ -42,9 +42,6 @@ SIGNATURES = {
     "vst_temporal_attention": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
     "vst_temporal_attention_windowed": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F,
                                              _P]),
-    "vst_motion_attention_block": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _F, _P, _P, _I, _P, _P, _I, _P, _F, _P, _I,
-                                        _P]),
-    "vst_motion_attention_block_supported": (_I, [_I, _I, _I, _I]),
     "vst_groupnorm_workspace_bytes": (_S, [_I, _I, _I, _I]),
     "vst_groupnorm_frame_chunks": (_I, [_I]),
     "vst_p8_force_bn": (_I, [_I]),
@@ -55,10 +52,6 @@ SIGNATURES = {
     "vst_groupnorm_apply_partials": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _I, _F, _P, _P, _I, _P, _I, _P, _P]),
     "vst_permute_rows": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "vst_groupnorm": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _F, _P, _P, _I, _P, _I, _P, _P]),
-    "vst_colstat": (_I, [_P, _I, _I, _I, _P, _P]),
-    "vst_groupnorm_colstat": (_I, [_P, _I, _I, _P, _P, _I, _I, _P, _I, _I, _I, _F, _P, _P, _I, _P, _I, _P, _P]),
-    "vst_conv3x3_colstat": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _I, _I, _P, _I, _P, _I, _P,
-                                 _P]),
     "vst_layernorm_lora": (_I, [_P, _I, _I, _I, _P, _P, _F, _P, _I, _P, _I, _P, _I, _P]),
     "vst_layernorm": (_I, [_P, _I, _I, _I, _P, _P, _F, _P, _I, _I, _P, _I, _P]),
     "vst_add_row_table": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _I, _P]),

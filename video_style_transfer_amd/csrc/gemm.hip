@@ -446,7 +446,7 @@ struct GemmQuery {
   int tile, splits;   // the caller's: public tile code 0-10 (0 auto), splits 0 auto / >= 1 forced
   size_t slab_bytes;  // usable split-K workspace
   size_t c_bytes;     // byte extent of C (M * ldc * 2)
-  bool conv, vec, colstat;  // 3x3 conv; its channels allow 16-byte loads; column statistics requested
+  bool conv, vec;     // 3x3 conv; its channels allow 16-byte loads
   int C1, C2;
 };
 
@@ -628,13 +628,11 @@ static GemmPlan plan_gemm(const GemmQuery& q) {
       // tiles where Cout is a multiple of 320, else the projection policy's width); VST_P8_CONV=0 restores the ring
       const bool p8 = p8_ok && gemm_knobs().p8_conv && !(q.C1 & 63) && !(q.C2 & 63) && !(N & 63) &&
                       K == 9 * (q.C1 + q.C2);
-      const bool ring128 = p8 && !q.colstat && conv_ring128(M, N);
+      const bool ring128 = p8 && conv_ring128(M, N);
       if (ring128) p.bm = 256, p.bn = 128;
       if (p8 && !ring128) p8_tile(kP8Conv, N % 320 == 0 ? 320 : p8_bn(M, N, false));
       else p.family = kRing, choose(q, ring128 ? 1 : q.splits, p);
     }
-    // column statistics come from the 128x320 tiles' epilogue only
-    if (q.colstat && !(p.family == kP8Conv && p.bn == 320)) return {};
     return p;
   }
   if (p.family == kP8 && (!p8_applies(q.K1, q.two_src) || (geglu && p.bn != 256) || (p.bn == 320 && N % 320))) return {};
@@ -1020,7 +1018,7 @@ extern "C" int vst_gemm(const void* A, int lda, const void* A2, int lda2, int K1
 static int conv3x3_impl(const void* x1, int C1, const void* x2, int C2, int nimg, int H, int W, int stride,
                         int upsample, int pad0, const void* Wt, int Cout, const float* bias, const float* row_bias,
                         int row_bias_div, int ld_row_bias, const void* R, int ldr, void* out, int ldc, int tile,
-                        int splits, void* workspace, size_t ws_bytes, void* stream, float* colstat = nullptr) {
+                        int splits, void* workspace, size_t ws_bytes, void* stream) {
   Fit31 fit;
   if (!x1 || !Wt || !out || nimg <= 0 || H <= 0 || W <= 0 || Cout <= 0) return VST_ERR_ARG;
   if (pad0 && (stride != 2 || H < 2 || W < 2)) return VST_ERR_ARG;
@@ -1037,7 +1035,7 @@ static int conv3x3_impl(const void* x1, int C1, const void* x2, int C2, int nimg
     const size_t lim = kMaxExtent, hw = (size_t)H * W, ohw = (size_t)a.OH * a.OW;
     const size_t img_bytes = max(max(hw * C1, x2 ? hw * C2 : 0), max(R ? ohw * ldr : 0, ohw * ldc)) * 2;
     if ((size_t)nimg * img_bytes > lim) {
-      if (colstat || (row_bias && row_bias_div != (int)ohw)) return VST_ERR_UNSUPPORTED;
+      if (row_bias && row_bias_div != (int)ohw) return VST_ERR_UNSUPPORTED;
       const int per = (int)(lim / img_bytes);
       if (per <= 0) return VST_ERR_ARG;
       const int nch = (nimg + per - 1) / per, ipc = (nimg + nch - 1) / nch;
@@ -1075,10 +1073,9 @@ static int conv3x3_impl(const void* x1, int C1, const void* x2, int C2, int nimg
   GemmQuery q{};
   q.M = a.M, q.N = a.N, q.K = a.K, q.K1 = a.K1, q.two_src = x2 != nullptr, q.tile = tile, q.splits = splits;
   q.slab_bytes = workspace ? ws_bytes : 0, q.c_bytes = (size_t)a.M * ldc * 2;
-  q.conv = true, q.vec = vec, q.colstat = colstat != nullptr, q.C1 = a.C1, q.C2 = a.C2;
+  q.conv = true, q.vec = vec, q.C1 = a.C1, q.C2 = a.C2;
   const GemmPlan plan = plan_gemm(q);
-  if (plan.family == kNone) return colstat ? VST_ERR_UNSUPPORTED : VST_ERR_ARG;
-  a.colstat = colstat;
+  if (plan.family == kNone) return VST_ERR_ARG;
   return launch_plan(a, plan, (hipStream_t)stream);
 }
 
@@ -1088,19 +1085,6 @@ extern "C" int vst_conv3x3_ex(const void* x1, int C1, const void* x2, int C2, in
                               int splits, void* workspace, size_t ws_bytes, void* stream) {
   return conv3x3_impl(x1, C1, x2, C2, nimg, H, W, stride, upsample, 0, Wt, Cout, bias, row_bias, row_bias_div,
                       ld_row_bias, R, ldr, out, ldc, tile, splits, workspace, ws_bytes, stream);
-}
-
-// vst_conv3x3_ex + the GroupNorm column statistics of the output for a following vst_groupnorm_colstat:
-// colstat [ceil(M / 128)][Cout][2] fp32 = (sum, sum of squares) over each 128-row output tile of the stored bf16
-// values.  VST_ERR_UNSUPPORTED (nothing launched) unless the conv runs on the 8-phase kernel's 128x320 tiles
-// (Cout % 320 == 0, both sources multiples of 64 channels, default policy).
-extern "C" int vst_conv3x3_colstat(const void* x1, int C1, const void* x2, int C2, int nimg, int H, int W, int stride,
-                                   int upsample, const void* Wt, int Cout, const float* bias, const float* row_bias,
-                                   int row_bias_div, int ld_row_bias, const void* R, int ldr, void* out, int ldc,
-                                   float* colstat, void* stream) {
-  if (!colstat) return VST_ERR_ARG;
-  return conv3x3_impl(x1, C1, x2, C2, nimg, H, W, stride, upsample, 0, Wt, Cout, bias, row_bias, row_bias_div,
-                      ld_row_bias, R, ldr, out, ldc, 0, 1, nullptr, 0, stream, colstat);
 }
 
 // 3x3 stride-2 conv with padding (0,1,0,1): diffusers Downsample2D(padding=0) = F.pad(x, (0, 1, 0, 1)) + conv(k3, s2,

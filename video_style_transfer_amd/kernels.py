@@ -7,9 +7,6 @@ No CPU fallback exists: a CPU tensor or a missing library raises.
 """
 from __future__ import annotations
 
-import os
-import weakref
-
 import torch
 
 from . import _lib
@@ -87,15 +84,13 @@ _FUSION_WORLD = [1]
 
 
 class fusion_world:
-    """Inside: shape-dependent fusion decisions are taken as a P-way frame-sharded rank takes them, so a forward here
-    computes exactly the bits of a P-way sharded forward.  Two decisions depend on the pixels a rank holds (with the
-    all-to-all exchange H*W/P of them): the motion attention fused into its q/k/v GEMM (vst_gemm_temporal_attention,
-    default), which needs a multiple of 16 pixels, so an unsharded forward (or an all-gather rank, which holds all
-    H*W) under fusion_world(P) fuses a layer only when (H*W) % (16 P) == 0; and the opt-in whole-block motion kernel
-    (VST_MOTION_FUSE=1, unet_motion._fused_motion_ops_impl), which also asks vst_motion_attention_block_supported
-    for H*W/P.  UNetMotionModel.forward_tokens enters it
-    with the shard's world size (or its `fusion_world` argument); the all-to-all branch of MotionModule, whose
-    pixels are already split, re-enters it with 1."""
+    """Inside: the one shape-dependent fusion decision is taken as a P-way frame-sharded rank takes it, so a forward
+    here computes exactly the bits of a P-way sharded forward.  The motion attention fused into its q/k/v GEMM
+    (vst_gemm_temporal_attention) needs a multiple of 16 pixels, and a rank of the all-to-all exchange holds H*W/P of
+    them, so an unsharded forward (or an all-gather rank, which holds all H*W) under fusion_world(P) fuses a layer only
+    when (H*W) % (16 P) == 0.  UNetMotionModel.forward_tokens enters it with the shard's world size (or its
+    `fusion_world` argument); the all-to-all branch of MotionModule, whose pixels are already split, re-enters it
+    with 1."""
 
     def __init__(self, world: int):
         if world < 1:
@@ -141,38 +136,9 @@ def _workspace(device):
     return ws
 
 
-def _wrote(t):
-    """A launch is about to write t through a raw pointer (which does not bump t._version): drop any GroupNorm column
-    statistics registered for its storage (colstat_of), so they are never read for overwritten data."""
-    if not _COLSTAT or t is None:
-        return
-    # every entry whose registered tensor shares bytes with the written view goes, not only the one registered at the
-    # view's own data_ptr(): a write into out=t[rows:] overwrites part of t, whose entry sits at t.data_ptr()
-    sp = _span(t)
-    for key, e in list(_COLSTAT.items()):
-        base = e[0]()
-        if base is None:
-            del _COLSTAT[key]
-            continue
-        sb = _span(base)
-        if sb[0] == sp[0] and sb[1] < sp[2] and sp[1] < sb[2]:
-            del _COLSTAT[key]
-
-
-def _span(t):
-    """(storage pointer, first byte, one past the last byte) of the storage bytes the view t can touch."""
-    st = t.untyped_storage().data_ptr()
-    lo = t.storage_offset() * t.element_size()
-    if t.numel() == 0:
-        return st, lo, lo
-    last = sum((n - 1) * s for n, s in zip(t.shape, t.stride()))
-    return st, lo, lo + (last + 1) * t.element_size()
-
-
 def _out(t, shape, dtype, name, fn):
     """Validate an output view before a launch writes it through its raw pointer: on the device, the expected dtype,
     2-D with unit column stride, exactly `shape`.  A kernel given anything else writes outside the view."""
-    _wrote(t)
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         raise _lib.VstError(f"{fn}: {name} must be a device tensor; the HIP path has no CPU fallback")
     if t.dtype != dtype:
@@ -187,7 +153,6 @@ def _out(t, shape, dtype, name, fn):
 
 def _out_flat(t, shape, dtype, name, fn):
     """Validate an output the kernel addresses as one contiguous block (no row stride in its ABI)."""
-    _wrote(t)
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         raise _lib.VstError(f"{fn}: {name} must be a device tensor; the HIP path has no CPU fallback")
     if t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
@@ -197,8 +162,6 @@ def _out_flat(t, shape, dtype, name, fn):
 
 
 def _dev(t: torch.Tensor, dtype, name):
-    if name == "out":
-        _wrote(t)
     if not t.is_cuda:
         raise _lib.VstError(f"{name}: tensor is on {t.device}; the HIP path has no CPU fallback")
     if t.dtype != dtype:
@@ -580,68 +543,12 @@ def linear_temporal_attention(x: torch.Tensor, w_t: torch.Tensor, b_t: torch.Ten
     return out
 
 
-# GroupNorm column statistics of conv outputs (vst_conv3x3_colstat -> vst_groupnorm_colstat): output data_ptr ->
-# (weakref to the output, its version counter at the conv, colstat [ceil(M/128), Cout, 2] fp32).  Filled by
-# conv3x3(colstat=True) and read by colstat_of(); an entry is valid only for the very tensor the conv wrote, not
-# modified since (version), still alive (weakref).  colstat_reset() at the start of each UNet forward.
-_COLSTAT: dict = {}
-
-
-def colstat_enabled() -> bool:
-    """VST_GN_COLSTAT=1: the UNet's GroupNorms take their statistics from column statistics (opt-in).  Measured in
-    the denoise step (profiles/r5_ab_gn_colstat.txt): GroupNorm 2.22 -> 2.00 ms, the convs that write the statistics
-    10.80 -> 10.92 ms (the epilogue's two extra barriers and row-group sums), net -0.08 ms per step, within the
-    run-to-run spread; and every GroupNorm's statistics change bits (another summation order), which moved one
-    configs[2] block's max-element error past its gate (1.76e-2 against 1.6e-2, rel_l2 unchanged)."""
-    return os.environ.get("VST_GN_COLSTAT", "0") == "1"
-
-
-def colstat_reset() -> None:
-    _COLSTAT.clear()
-
-
-def colstat_of(t: torch.Tensor | None):
-    """The column statistics a conv3x3(colstat=True) registered for exactly this tensor, else None."""
-    if t is None:
-        return None
-    e = _COLSTAT.get(t.data_ptr())
-    if e is None:
-        return None
-    base = e[0]()
-    if base is None or base.shape != t.shape or base.stride() != t.stride() or t._version != e[1]:
-        return None
-    return e[2]
-
-
-def colstat(x: torch.Tensor) -> torch.Tensor:
-    """Column statistics of x [M, C] in the conv epilogue's arithmetic (vst_colstat): [ceil(M/128), C, 2] fp32."""
-    _dev(x, BF16, "x")
-    M, C = x.shape
-    cs = torch.empty(((M + 127) // 128, C, 2), dtype=F32, device=x.device)
-    with _Rec("groupnorm", 0.0, 2.0 * M * C):
-        _lib.call("vst_colstat", _p(x), _ld(x), M, C, _p(cs), _stream())
-    return cs
-
-
-def group_norm_stats(x1, x2=None):
-    """(cs1, cs2) for group_norm(colstat=...): each source's column statistics from its producing conv when it wrote
-    them (colstat_of), else from vst_colstat -- the same bits either way."""
-    c1 = colstat_of(x1)
-    c1 = colstat(x1) if c1 is None else c1
-    if x2 is None:
-        return c1, None
-    c2 = colstat_of(x2)
-    return c1, colstat(x2) if c2 is None else c2
-
-
 def conv3x3(x1: torch.Tensor, nimg: int, H: int, W: int, w: torch.Tensor, bias: torch.Tensor | None, *,
             x2: torch.Tensor | None = None, stride: int = 1, upsample: bool = False,
             row_bias: torch.Tensor | None = None, row_bias_div: int = 1, residual: torch.Tensor | None = None,
-            out: torch.Tensor | None = None, colstat: bool = False) -> torch.Tensor:
+            out: torch.Tensor | None = None) -> torch.Tensor:
     """NHWC 3x3 conv (pad 1).  x1: [nimg*H*W, C1] (+ x2: [nimg*H*W, C2] concatenated on channels).
-    w: [Cout, 9*(C1+C2)] laid out (ky, kx, ci).  Returns [nimg*OH*OW, Cout].
-    colstat: also write the GroupNorm column statistics of the output where the 128x320 8-phase tiles run it
-    (vst_conv3x3_colstat), registered for colstat_of(out)."""
+    w: [Cout, 9*(C1+C2)] laid out (ky, kx, ci).  Returns [nimg*OH*OW, Cout]."""
     _dev(x1, BF16, "x1")
     C1 = x1.shape[1]
     C2 = 0
@@ -678,18 +585,6 @@ def conv3x3(x1: torch.Tensor, nimg: int, H: int, W: int, w: torch.Tensor, bias: 
     kind = "conv3x3" if (C1 + C2) % 64 == 0 else "conv3x3_small_cin"
     with _Rec(kind, 2.0 * M * Cout * kreal, 2.0 * (nimg * H * W * (C1 + C2) + Cout * kreal + M * Cout),
               lambda: gemm_kernel_name(M, Cout, w.shape[1], 2 if kind == "conv3x3" else 3), (M, Cout, w.shape[1])):
-        if colstat and colstat_enabled() and Cout % 320 == 0 and out.is_contiguous() and GEMM_POLICY["tile"] == 0 \
-                and _splits() <= 1:
-            cs = torch.empty(((M + 127) // 128, Cout, 2), dtype=F32, device=x1.device)
-            rc = _lib.load().vst_conv3x3_colstat(
-                _p(x1), C1, _p(x2), C2, nimg, H, W, stride, 1 if upsample else 0, _p(w), Cout, _p(bias),
-                _p(row_bias), row_bias_div, 0 if row_bias is None else _ld(row_bias), _p(residual),
-                0 if residual is None else _ld(residual), _p(out), _ld(out), _p(cs), _stream())
-            if rc == 0:
-                _COLSTAT[out.data_ptr()] = (weakref.ref(out), out._version, cs)
-                return out
-            if rc != 3:
-                raise _lib.VstError(f"vst_conv3x3_colstat failed with status {rc}")
         ws = _workspace(x1.device)
         _lib.call("vst_conv3x3_ex", _p(x1), C1, _p(x2), C2, nimg, H, W, stride, 1 if upsample else 0, _p(w), Cout,
                   _p(bias), _p(row_bias), row_bias_div, 0 if row_bias is None else _ld(row_bias), _p(residual), 0 if residual is None else _ld(residual),
@@ -710,8 +605,6 @@ def spatial_attention(q, k, v, nbatch, heads, Nq, Nk, kv_div=1, out=None, scale=
     if out is None:
         out = torch.empty((nbatch * Nq, heads * 64), dtype=BF16, device=q.device)
     _out(out, (nbatch * Nq, heads * 64), BF16, "out", "spatial_attention")
-    if lse is not None:
-        _wrote(lse)
     if lse is not None and (lse.dtype != F32 or not lse.is_cuda or lse.numel() != nbatch * heads * Nq
                             or not lse.is_contiguous()):
         raise _lib.VstError("spatial_attention: lse must be contiguous fp32 [nbatch*heads*Nq] on device")
@@ -870,47 +763,7 @@ def temporal_attention_windowed(q, k, v, pos, nclip, F, HW, heads, head_dim, con
     return out
 
 
-def motion_block_fusable(C, F, HW, heads):
-    """vst_motion_attention_block takes this motion-module shape (host policy only)."""
-    return bool(_lib.load().vst_motion_attention_block_supported(C, F, HW, heads))
-
-
-def motion_attention_block(x, nclip, F, HW, heads, gamma, beta, eps, pe, wqkv, bqkv, wo, bo, *, scale=None, out=None):
-    """y = x + (attention over the F frames of (LayerNorm(x) * gamma + beta + pe[frame]) . wqkv^T (+ bqkv)) . wo^T + bo
-    in one launch; x: [nclip * F * HW, C] token rows (b * F + f) * HW + p."""
-    _dev(x, BF16, "x")
-    _dev(wqkv, BF16, "wqkv")
-    _dev(wo, BF16, "wo")
-    T, C = x.shape
-    if T != nclip * F * HW or wqkv.shape != (3 * C, C) or wo.shape != (C, C):
-        raise _lib.VstError(f"motion_attention_block: x {tuple(x.shape)} wqkv {tuple(wqkv.shape)} wo {tuple(wo.shape)}")
-    for n, t, k in (("gamma", gamma, C), ("beta", beta, C), ("bqkv", bqkv, 3 * C), ("bo", bo, C)):
-        if t is not None and (t.dtype != F32 or not t.is_cuda or t.numel() != k or not t.is_contiguous()):
-            raise _lib.VstError(f"motion_attention_block: {n} must be fp32 [{k}] on device")
-    if pe is not None and (pe.dtype != F32 or not pe.is_cuda or pe.shape[0] < F or pe.shape[-1] != C
-                           or not pe.is_contiguous()):
-        raise _lib.VstError("motion_attention_block: pe must be fp32 [>= F, C] on device")
-    if any(t is not None and t.data_ptr() % 16 for t in (gamma, beta, pe)):
-        raise _lib.VstError("motion_attention_block: gamma / beta / pe must be 16-byte aligned (vector loads)")
-    if gamma is None or beta is None:
-        raise _lib.VstError("motion_attention_block: gamma and beta are required")
-    if out is None:
-        out = torch.empty((T, C), dtype=BF16, device=x.device)
-    _out(out, (T, C), BF16, "out", "motion_attention_block")
-    D = C // heads
-    scale = D ** -0.5 if scale is None else scale
-    flops = 2.0 * T * C * 4 * C + 4.0 * T * F * C
-    with _Rec("motion_block", flops, 2.0 * (2 * T * C + 4 * C * C), lambda: "motion_attn_block_kernel", (T, 4 * C, C)):
-        _lib.call("vst_motion_attention_block", _p(x), _ld(x), nclip, F, HW, C, heads, _p(gamma), _p(beta), float(eps),
-                  _p(pe), _p(wqkv), _ld(wqkv), _p(bqkv), _p(wo), _ld(wo), _p(bo), float(scale), _p(out), _ld(out),
-                  _stream())
-    return out
-
-
-def group_norm(x1, nsamples, rows_per_sample, groups, eps, gamma, beta, *, silu=False, x2=None, out=None,
-               colstat=None):
-    """colstat: (cs1, cs2 or None) column statistics of x1 / x2 from their producing convs (colstat_of):
-    the statistics pass over x is skipped (vst_groupnorm_colstat)."""
+def group_norm(x1, nsamples, rows_per_sample, groups, eps, gamma, beta, *, silu=False, x2=None, out=None):
     _dev(x1, BF16, "x1")
     C = x1.shape[1] + (0 if x2 is None else x2.shape[1])
     if x2 is not None:
@@ -922,23 +775,6 @@ def group_norm(x1, nsamples, rows_per_sample, groups, eps, gamma, beta, *, silu=
     _out(out, (x1.shape[0], C), BF16, "out", "group_norm")
     ws_bytes = _lib.load().vst_groupnorm_workspace_bytes(nsamples, rows_per_sample, groups, C)
     ws = torch.empty((ws_bytes + 3) // 4, dtype=F32, device=x1.device)
-    if colstat is not None:
-        cs1, cs2 = colstat
-        for nm, cs, src in (("cs1", cs1, x1), ("cs2", cs2, x2)):
-            if (cs is None) != (src is None):
-                raise _lib.VstError(f"group_norm: {nm} must be given exactly when its source is")
-            if cs is None:
-                continue
-            want = ((src.shape[0] + 127) // 128, src.shape[1], 2)
-            if tuple(cs.shape) != want or cs.dtype != F32 or cs.device != src.device or not cs.is_contiguous():
-                raise _lib.VstError(f"group_norm: {nm} must be contiguous fp32 {want} on {src.device}, got "
-                                    f"{tuple(cs.shape)} {cs.dtype} on {cs.device}")
-        with _Rec("groupnorm", 0.0, 2.0 * 2 * x1.shape[0] * C):  # one read + one write
-            _lib.call("vst_groupnorm_colstat", _p(x1), _ld(x1), x1.shape[1], _p(cs1), _p(x2),
-                      0 if x2 is None else _ld(x2), 0 if x2 is None else x2.shape[1], _p(cs2), nsamples,
-                      rows_per_sample, groups, float(eps), _p(gamma), _p(beta), 1 if silu else 0, _p(out), _ld(out),
-                      _p(ws), _stream())
-        return out
     with _Rec("groupnorm", 0.0, 2.0 * 3 * x1.shape[0] * C):  # two reads + one write
         _lib.call("vst_groupnorm", _p(x1), _ld(x1), x1.shape[1], _p(x2), 0 if x2 is None else _ld(x2),
                   0 if x2 is None else x2.shape[1], nsamples, rows_per_sample, groups, float(eps), _p(gamma),
@@ -1072,7 +908,6 @@ def timestep_embedding(t, n, dim, out, *, col0=0, per_row=1, step_idx=None, flip
 
 def _elementwise(fn, out, *ins):
     """silu / add address every operand as one flat bf16 block of the first input's size."""
-    _wrote(out)
     for name, t in (("out", out),) + tuple((f"input {i}", t) for i, t in enumerate(ins)):
         if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != BF16 or not t.is_contiguous() \
                 or t.numel() != ins[0].numel():
@@ -1150,7 +985,6 @@ def colsum(x, out=None):
     M, N = x.shape
     if out is None:
         out = torch.empty(N, dtype=F32, device=x.device)
-    _wrote(out)
     if not out.is_cuda or out.dtype != F32 or out.dim() != 1 or out.numel() != N or not out.is_contiguous():
         raise _lib.VstError(f"colsum: out must be contiguous fp32 [{N}] on device")
     if N % 8 or _ld(x) % 8 or x.data_ptr() % 16:

@@ -21,8 +21,6 @@ Block semantics (diffusers ~0.30, restated in oracle/unet.py with citations):
 """
 from __future__ import annotations
 
-import os
-
 import dataclasses
 from dataclasses import dataclass
 from typing import Optional
@@ -60,12 +58,8 @@ f32 = _F32Cache.get
 
 class GroupNorm(nn.GroupNorm):
     def run(self, x1, nsamples, rows_per_sample, *, silu=False, x2=None, out=None):
-        # statistics from column statistics (128-row chunks): the producing conv's epilogue wrote them
-        # (K.conv3x3(colstat=True)) or vst_colstat makes them, the same bits either way, so a frame shard (whose convs
-        # may run on other tiles) normalises exactly as the whole clip does
-        cs = K.group_norm_stats(x1, x2) if rows_per_sample % 128 == 0 and K.colstat_enabled() else None
         return K.group_norm(x1, nsamples, rows_per_sample, self.num_groups, self.eps, f32(self.weight), f32(self.bias),
-                            silu=silu, x2=x2, out=out, colstat=cs)
+                            silu=silu, x2=x2, out=out)
 
 
 class LayerNorm(nn.LayerNorm):
@@ -101,11 +95,9 @@ class Conv3x3(nn.Conv2d):
             self.__dict__["_vst_w"] = c
         return c[1]
 
-    def run(self, x1, nimg, H, W, *, x2=None, upsample=False, row_bias=None, row_bias_div=1, residual=None,
-            colstat=False):
+    def run(self, x1, nimg, H, W, *, x2=None, upsample=False, row_bias=None, row_bias_div=1, residual=None):
         return K.conv3x3(x1, nimg, H, W, self.kernel_weight(), f32(self.bias), x2=x2, stride=self.stride[0],
-                         upsample=upsample, row_bias=row_bias, row_bias_div=row_bias_div, residual=residual,
-                         colstat=colstat)
+                         upsample=upsample, row_bias=row_bias, row_bias_div=row_bias_div, residual=residual)
 
 
 class Conv1x1(nn.Conv2d):
@@ -276,9 +268,6 @@ class BasicTransformerBlock(nn.Module):
         if temporal:
             self.pos_embed = _SinusoidalPE(dim, max_seq_length)
 
-    def _fused_motion_ops(self, C, F, HW):
-        return _fused_motion_ops_impl(self, C, F, HW)
-
     def run(self, x, nimg, N, ctx: FwdCtx):
         """x: [nimg*N, C] -> same."""
         C = x.shape[1]
@@ -288,20 +277,12 @@ class BasicTransformerBlock(nn.Module):
             check_clip_length(ctx.F, pe.shape[0], tc)
             if tc is not None and tc.active(ctx.F):
                 # LayerNorm WITHOUT the positional term: the windowed kernel adds pe[position in window] . Wqkv^T per
-                # window behind one projection per frame; the fused q/k/v GEMM and the whole-block kernel step aside
+                # window behind one projection per frame; the fused q/k/v GEMM steps aside
                 kw = dict(num_frames=ctx.F, _vst_context=(tc, pe))
                 n = self.norm1.run(x)
                 x = self.attn1(n.view(nimg, N, C), _vst_residual=x, **kw).view(-1, C)
                 n = self.norm2.run(x)
                 x = self.attn2(n.view(nimg, N, C), _vst_residual=x, **kw).view(-1, C)
-                n = self.norm3.run(x)
-                return self.ff.run(n, residual=x)
-            fused = self._fused_motion_ops(C, ctx.F, N)
-            if fused is not None:
-                # each attention half (norm + PE, q/k/v, frame attention, to_out, residual) as one launch
-                for norm, (qkv, o) in zip((self.norm1, self.norm2), fused):
-                    x = K.motion_attention_block(x, nimg // ctx.F, ctx.F, N, self.attn1.heads, f32(norm.weight),
-                                                 f32(norm.bias), norm.eps, pe, qkv.w, qkv.bias, o.w, o.bias)
                 n = self.norm3.run(x)
                 return self.ff.run(n, residual=x)
             kw = dict(pe=pe, pe_div=N, pe_mod=ctx.F)
@@ -322,30 +303,6 @@ class BasicTransformerBlock(nn.Module):
                            **ctx.cross_kwargs).view(-1, C)
         n = self.norm3.run(x)
         return self.ff.run(n, residual=x)
-
-
-def _fused_motion_ops_impl(block, C, F, HW):
-    """[(qkv ops, out ops)] for attn1 / attn2 when vst_motion_attention_block can run them: the default processor,
-    no LoRA on any projection (temporal LoRA trains through the autograd path), the kernel's shape."""
-    from .attention_processor import AttnProcessor2_0
-    # opt-in (VST_MOTION_FUSE=1): the fused block is correct but measured slower than the four launches (DESIGN §9)
-    if os.environ.get("VST_MOTION_FUSE") != "1" or not K.motion_block_fusable(C, F, HW, block.attn1.heads):
-        return None
-    # shape-dependent like the fused frame attention (kernels.fusion_world): decide as a P-way all-to-all rank, which
-    # holds HW / P pixels, decides, so an unsharded forward under fusion_world(P) equals the shards bit for bit
-    P = K.fusion_pixel_div()
-    if P > 1 and (HW % P or not K.motion_block_fusable(C, F, HW // P, block.attn1.heads)):
-        return None
-    out = []
-    for attn in (block.attn1, block.attn2):
-        if type(attn.processor) is not AttnProcessor2_0 or attn.heads != block.attn1.heads:
-            return None
-        qkv = build_ops([attn.to_q, attn.to_k, attn.to_v], 1.0)
-        o = build_ops([attn.to_out[0]], 1.0)
-        if qkv.a is not None or o.a is not None or qkv.w.shape != (3 * C, C) or o.w.shape != (C, C):
-            return None
-        out.append((qkv, o))
-    return out
 
 
 class _SinusoidalPE(nn.Module):
@@ -489,10 +446,10 @@ class ResnetBlock2D(nn.Module):
             temb = ctx.temb[self]  # view of the one batched projection (UNetMotionModel.batched_temb)
         else:
             temb = self.time_emb_proj.run(ctx.emb_silu).float()  # [B, cout]; bf16-rounded like the reference
-        h = self.conv1.run(h, nimg, H, W, row_bias=temb, row_bias_div=ctx.F * HW, colstat=True)
+        h = self.conv1.run(h, nimg, H, W, row_bias=temb, row_bias_div=ctx.F * HW)
         h = self.norm2.run(h, nimg, HW, silu=True)
         sc = self.conv_shortcut.run(x1, x2) if self.conv_shortcut is not None else x1
-        return self.conv2.run(h, nimg, H, W, residual=sc, colstat=True)
+        return self.conv2.run(h, nimg, H, W, residual=sc)
 
 
 class Downsample2D(nn.Module):
@@ -501,7 +458,7 @@ class Downsample2D(nn.Module):
         self.conv = Conv3x3(C, C, stride=2)
 
     def run(self, x, nimg, H, W):
-        return self.conv.run(x, nimg, H, W, colstat=True), (H + 1) // 2, (W + 1) // 2
+        return self.conv.run(x, nimg, H, W), (H + 1) // 2, (W + 1) // 2
 
 
 class Upsample2D(nn.Module):
@@ -510,7 +467,7 @@ class Upsample2D(nn.Module):
         self.conv = Conv3x3(C, C)
 
     def run(self, x, nimg, H, W):
-        return self.conv.run(x, nimg, H, W, upsample=True, colstat=True), 2 * H, 2 * W
+        return self.conv.run(x, nimg, H, W, upsample=True), 2 * H, 2 * W
 
 
 class DownBlock(nn.Module):
@@ -731,7 +688,6 @@ class UNetMotionModel(nn.Module):
         if fusion_world is None:
             fusion_world = shard.world if shard is not None else 1
         # no split-K: a row's bits do not depend on the launch's row count (frame shards)
-        K.colstat_reset()
         with K.row_invariant(), K.fusion_world(fusion_world):
             ctx = FwdCtx(B, F, emb_silu, enc, cross_kwargs or {}, shard, self.batched_temb(emb_silu),
                          temporal_context, cross_frame, lora_gate, freeu)
