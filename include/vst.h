@@ -26,11 +26,22 @@
  *     vst_gemm_f32out's C, vst_colsum's y, the dgamma / dbeta vectors, the fp32 NCHW / latent tensors;
  *   - an output is written exactly on [rows) x [cols) of its view and nowhere else: no guard row or column is
  *     touched, and every element of the view is written by every call.
+ *
+ * This header is the one declaration of the ABI: every csrc/ file sees it through vst_common.h (a definition that
+ * disagrees with its prototype does not compile), and _lib.py derives its ctypes signatures from the prototypes
+ * below, so keep them plain C: one prototype per statement, scalar types int / unsigned / float / size_t.
+ * vst_p8_trace_read exists only in -DVST_P8_TRACE builds; it stays outside this header and tools/p8_trace.py types it.
  */
 #ifndef VST_H
 #define VST_H
 #include <stddef.h>
 #include <stdint.h>
+
+#define VST_OK 0
+#define VST_ERR_ARG 1
+#define VST_ERR_LAUNCH 2
+#define VST_ERR_UNSUPPORTED 3
+
 #ifdef __cplusplus
 extern "C" {
 #endif

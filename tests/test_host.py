@@ -9,6 +9,16 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+class FakeCuda(torch.Tensor):  # a CPU tensor that claims to be on the device: the validators never launch anything
+    @property
+    def is_cuda(self):
+        return True
+
+
+def fake_device_tensor(*shape, dtype=torch.bfloat16):
+    return torch.zeros(*shape, dtype=dtype).as_subclass(FakeCuda)
+
+
 def test_library_exports_header_symbols():
     from video_style_transfer_amd import _lib
     lib = _lib.load()
@@ -19,6 +29,18 @@ def test_library_exports_header_symbols():
     for name in declared:
         assert hasattr(lib, name), name
     assert lib.vst_version().startswith(b"vst-hip")
+    # the signatures are derived from the header's prototypes: three of them against lists written out here (a reader
+    # bug cannot pass by agreeing with itself), and a type the reader does not know must raise, never go untyped
+    import ctypes
+    P, I, F, S = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
+    assert _lib.SIGNATURES["vst_gemm_ex"] == (I, [P, I, P, I, I, P, I, I, I, I, P, P, I, I, P, I, P, I, I, I, I, P, S,
+                                                  P])
+    assert _lib.SIGNATURES["vst_sampler_step_noise"] == (I, [P, I, F, P, P, I, I, I, I, I, I, P, P, P, P, P, P, P, P,
+                                                             I, P])
+    assert _lib.SIGNATURES["vst_version"] == (ctypes.c_char_p, [])
+    assert _lib.parse_header("/* c */ int vst_a(const float* x, size_t n);  // d\n") == {"vst_a": (I, [P, S])}
+    with pytest.raises(_lib.VstError, match="double"):
+        _lib.parse_header("int vst_a(const float* x, double alpha);")
 
 
 def test_calls_fail_loudly_on_cpu_tensors():
@@ -56,27 +78,20 @@ def test_gemm_tn_refuses_misaligned_output_without_gpu():
 def test_out_validation_is_host_side():
     """Every wrapper validates out= before it touches the library: a wrong dtype, width, rank or column stride raises
     VstError naming the argument (here on CPU tensors, so the device check fires first for those; the shape / dtype
-    checks of kernels._out are exercised directly)."""
+    checks of kernels._view / kernels._block are exercised directly)."""
     from video_style_transfer_amd import kernels as K
 
-    class FakeCuda(torch.Tensor):  # a CPU tensor that claims to be on the device: _out never launches anything
-        @property
-        def is_cuda(self):
-            return True
-
-    def fake(*shape, dtype=torch.bfloat16):
-        return torch.zeros(*shape, dtype=dtype).as_subclass(FakeCuda)
-
-    K._out(fake(6, 16), (6, 16), torch.bfloat16, "out", "op")
-    K._out(fake(6, 32)[:, 8:24], (6, 16), torch.bfloat16, "out", "op")   # a column view is fine
+    fake = fake_device_tensor
+    K._view(fake(6, 16), torch.bfloat16, "out", "op", shape=(6, 16))
+    K._view(fake(6, 32)[:, 8:24], torch.bfloat16, "out", "op", shape=(6, 16))   # a column view is fine
     for bad, what in ((fake(6, 16, dtype=torch.float32), "expected"), (fake(6, 8), "shape"), (fake(5, 16), "shape"),
                       (fake(6 * 16), "2-D"), (fake(16, 6).t(), "2-D"), (fake(6, 32)[:, ::2], "2-D"),
                       (torch.zeros(6, 16, dtype=torch.bfloat16), "device")):
         with pytest.raises(K._lib.VstError, match=f"op: out .*{what}"):
-            K._out(bad, (6, 16), torch.bfloat16, "out", "op")
+            K._view(bad, torch.bfloat16, "out", "op", shape=(6, 16))
     with pytest.raises(K._lib.VstError, match="op: out must be contiguous"):
-        K._out_flat(fake(6, 32)[:, :16], (6, 16), torch.bfloat16, "out", "op")
-    K._out_flat(fake(6, 16), (6, 16), torch.bfloat16, "out", "op")
+        K._block(fake(6, 32)[:, :16], torch.bfloat16, "out", "op", (6, 16))
+    K._block(fake(6, 16), torch.bfloat16, "out", "op", (6, 16))
 
 
 def test_gemm_lora_policy_without_gpu():

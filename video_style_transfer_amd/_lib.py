@@ -8,111 +8,59 @@ from __future__ import annotations
 
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvst_hip.so")
-
-# name -> (restype, argtypes)
-_P = ctypes.c_void_p
-_I = ctypes.c_int
-_F = ctypes.c_float
-_S = ctypes.c_size_t
-SIGNATURES = {
-    "vst_gemm": (_I, [_P, _I, _P, _I, _I, _P, _I, _I, _I, _I, _P, _P, _I, _I, _P, _I, _P, _I, _I, _P]),
-    "vst_gemm_ex": (_I, [_P, _I, _P, _I, _I, _P, _I, _I, _I, _I, _P, _P, _I, _I, _P, _I, _P, _I, _I, _I, _I, _P, _S,
-                         _P]),
-    "vst_gemm_workspace_bytes": (_S, [_I, _I, _I]),
-    "vst_gemm_lora": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _I, _P, _I, _P]),
-    "vst_gemm_lora_supported": (_I, [_I, _I, _I, _I, _I, _I]),
-    "vst_gemm_lora_gated": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _I, _P, _I, _P, _I, _I, _P]),
-    "vst_lora_gate": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _I, _P]),
-    "vst_gemm_cross_attention": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I,
-                                      _F, _P, _I, _P]),
-    "vst_gemm_cross_attention_supported": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I]),
-    "vst_gemm_cross_attention_gated": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _P, _P, _I, _I, _I, _I,
-                                            _I, _F, _P, _I, _P, _I, _I, _P]),
-    "vst_gemm_temporal_attention": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _F, _P, _I, _P]),
-    "vst_gemm_temporal_attention_supported": (_I, [_I, _I, _I, _I, _I, _I, _I]),
-    "vst_gemm_kernel_name": (ctypes.c_char_p, [_I, _I, _I, _I, _I, _I, _S]),
-    "vst_conv3x3": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _I, _P, _I, _P, _I, _P]),
-    "vst_conv3x3_ex": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _I, _I, _P, _I, _P, _I, _I, _I, _P,
-                            _S, _P]),
-    "vst_spatial_attention": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P]),
-    "vst_spatial_attention_frames": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P]),
-    "vst_temporal_attention": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
-    "vst_temporal_attention_windowed": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F,
-                                             _P]),
-    "vst_groupnorm_workspace_bytes": (_S, [_I, _I, _I, _I]),
-    "vst_groupnorm_frame_chunks": (_I, [_I]),
-    "vst_p8_force_bn": (_I, [_I]),
-    "vst_p8_conv": (_I, [_I]),
-    "vst_p8_persist": (_I, [_I]),
-    "vst_sa_self": (_I, [_I]),
-    "vst_groupnorm_frame_partials": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
-    "vst_groupnorm_apply_partials": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _I, _F, _P, _P, _I, _P, _I, _P, _P]),
-    "vst_permute_rows": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "vst_groupnorm": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _F, _P, _P, _I, _P, _I, _P, _P]),
-    "vst_layernorm_lora": (_I, [_P, _I, _I, _I, _P, _P, _F, _P, _I, _P, _I, _P, _I, _P]),
-    "vst_layernorm": (_I, [_P, _I, _I, _I, _P, _P, _F, _P, _I, _I, _P, _I, _P]),
-    "vst_add_row_table": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _I, _P]),
-    "vst_unpack_tokens": (_I, [_P, _I, _I, _I, _I, _P, _P]),
-    "vst_timestep_embedding": (_I, [_P, _P, _I, _I, _I, _F, _P, _I, _I, _I, _P]),
-    "vst_pack_latents": (_I, [_P, _I, _I, _I, _I, _P, _P, _F, _I, _P, _P]),
-    "vst_euler_cfg_step": (_I, [_P, _I, _F, _P, _I, _I, _I, _I, _P, _P, _P]),
-    "vst_step_advance": (_I, [_P, _I, _P]),
-    "vst_silu": (_I, [_P, _P, _S, _P]),
-    "vst_add": (_I, [_P, _P, _P, _S, _P]),
-    "vst_quick_gelu": (_I, [_P, _P, _S, _P]),
-    "vst_embed_tokens": (_I, [_P, _I, _I, _P, _P, _I, _P, _I, _P]),
-    "vst_causal_attention": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _F, _P]),
-    "vst_residual_layernorm": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _F, _P, _I, _P, _I, _P]),
-    "vst_copy2d": (_I, [_P, _I, _P, _I, _I, _I, _P]),
-    "vst_transpose": (_I, [_P, _I, _I, _I, _P, _I, _P]),
-    "vst_layernorm_bwd_workspace_bytes": (_S, [_I, _I]),
-    "vst_layernorm_bwd": (_I, [_P, _I, _P, _I, _I, _I, _P, _F, _P, _I, _P, _P, _P, _P]),
-    "vst_geglu_bwd": (_I, [_P, _I, _P, _I, _I, _I, _P, _I, _P]),
-    "vst_colsum_workspace_bytes": (_S, [_I, _I]),
-    "vst_colsum": (_I, [_P, _I, _I, _I, _P, _P, _P]),
-    "vst_groupnorm_bwd_workspace_bytes": (_S, [_I, _I, _I, _I]),
-    "vst_groupnorm_bwd": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _F, _P, _P, _I, _P, _I, _P, _P, _P, _P]),
-    "vst_spatial_attention_bwd_workspace_bytes": (_S, [_I, _I, _I, _I]),
-    "vst_spatial_attention_bwd": (_I, [_P, _I, _P, _P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I,
-                                       _I, _F, _P, _P]),
-    "vst_zero_insert": (_I, [_P, _I, _I, _I, _I, _P, _P]),
-    "vst_sumpool2x2": (_I, [_P, _I, _I, _I, _I, _P, _P]),
-    "vst_temporal_attention_bwd": (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
-    "vst_conv3x3_down_pad0": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _P, _S, _P]),
-    "vst_gemm_f32out": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P]),
-    "vst_gemm_tn": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _I, _P, _S, _P]),
-    "vst_gemm_tn_workspace_bytes": (_S, [_I, _I, _I]),
-    "vst_softmax_rows": (_I, [_P, _I, _I, _I, _F, _P, _I, _P]),
-    "vst_nchw_to_nhwc": (_I, [_P, _I, _I, _I, _F, _P, _I, _P]),
-    "vst_nhwc_to_nchw": (_I, [_P, _I, _I, _I, _I, _P, _P]),
-    "vst_frames_to_u8": (_I, [_P, _I, _I, _I, _I, _P, _P]),
-    "vst_vae_sample": (_I, [_P, _I, _I, _I, _P, _F, _P, _P]),
-    "vst_noise_latents": (_I, [_P, _P, _P, _P, _P, _S, _P]),
-    "vst_euler_cfg_step_masked": (_I, [_P, _I, _F, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P]),
-    "vst_u8_to_frames": (_I, [_P, _I, _I, _I, _P, _I, _P]),
-    "vst_sampler_step": (_I, [_P, _I, _F, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
-    "vst_cfg_rescale_factor_workspace_bytes": (_S, [_I, _I, _I, _I]),
-    "vst_cfg_rescale_factor": (_I, [_P, _F, _F, _I, _I, _I, _I, _P, _P, _P]),
-    "vst_noise_bits": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "vst_noise_normal": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "vst_sampler_step_noise": (_I, [_P, _I, _F, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I,
-                                    _P]),
-    "vst_freeu": (_I, [_P, _I, _I, _P, _I, _I, _P, _I, _P, _I, _I, _I, _I, _P, _I, _P]),
-    "vst_probe_mfma": (_I, [_I, _I, _P, _P]),
-    "vst_probe_hbm_read": (_I, [_P, _S, _I, _P, _P]),
-    "vst_probe_fetch": (_I, [_I, _P, _I, _I, _I, _P, _P]),
-    "vst_probe_mix": (_I, [_I, _I, _P, _I, _I, _I, _P, _P]),
-    "vst_version": (ctypes.c_char_p, []),
-}
-
-_lib = None
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vst.h")
 
 
 class VstError(RuntimeError):
     pass
+
+
+_SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "size_t": ctypes.c_size_t, "unsigned": ctypes.c_uint}
+
+
+def _ctype(decl: str, what: str, ret: bool = False):
+    """The ctypes type of one parameter (or return) declaration: any pointer is c_void_p (a `const char*` return
+    c_char_p), the scalars are _SCALARS; anything else raises."""
+    words = decl.replace("*", " * ").split()
+    if "*" in words:
+        return ctypes.c_char_p if ret and words[:3] == ["const", "char", "*"] else ctypes.c_void_p
+    if not ret and len(words) > 1:
+        words = words[:-1]  # the parameter's name
+    if len(words) != 1 or words[0] not in _SCALARS:
+        raise VstError(f"include/vst.h: cannot map `{decl.strip()}` of {what} to a ctypes type")
+    return _SCALARS[words[0]]
+
+
+def parse_header(text: str) -> dict:
+    """name -> (restype, argtypes) of every prototype in the text of include/vst.h."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^\s*#.*$|extern\s+\"C\"\s*\{|\}", " ", text, flags=re.M)
+    sigs = {}
+    for stmt in filter(None, (s.strip() for s in text.split(";"))):
+        m = re.fullmatch(r"(.*?)\b(\w+)\s*\((.*)\)", stmt, flags=re.S)
+        if not m:
+            raise VstError(f"include/vst.h: `{' '.join(stmt.split())}` is not a prototype")
+        ret, name, params = m.groups()
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        sigs[name] = (_ctype(ret, name, ret=True), [_ctype(p, name) for p in params])
+    return sigs
+
+
+def _read_header() -> dict:
+    try:
+        with open(HEADER_PATH) as f:
+            return parse_header(f.read())
+    except OSError as e:
+        raise VstError(f"the ABI header {HEADER_PATH} is missing ({e}); the signatures are read from it") from e
+
+
+SIGNATURES = _read_header()  # name -> (restype, argtypes)
+
+_lib = None
 
 
 def load(path: str | None = None):

@@ -642,7 +642,7 @@ static int launch_temporal(const bf16_t* Q, const bf16_t* K, const bf16_t* V, in
   const int wpg = (heads <= 8 && heads * VBYTES <= 64 * 1024) ? heads : 4;
   hipLaunchKernelGGL((temporal_attn_kernel<NT, D>), dim3((units + wpg - 1) / wpg), dim3(64 * wpg), wpg * VBYTES, s,
                      Q, K, V, ld, O, ldo, nclip, F, HW, heads, sl2, bytes);
-  return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
+  return launch_status();
 }
 
 // The (NT, head_dim) instances of the frame-axis forward and backward: fn(TaShape<NT, D>{}) with NT = 1 for F <= 16,
@@ -709,7 +709,7 @@ extern "C" int vst_spatial_attention(const void* q, int ldq, const void* k, cons
   const dim3 grid(nqb * heads * nbatch);
   const size_t lds = pre ? (size_t)pre * 2 * SA_TILE : SA_LDS;
   hipStream_t st = (hipStream_t)stream;
-  const float sl2 = scale * 1.4426950408889634f;
+  const float sl2 = scale * kLog2e;
 #define VST_SA_LAUNCH(P)                                                                                         \
   hipLaunchKernelGGL(spatial_attn_kernel<P>, grid, dim3(256), lds, st, (const bf16_t*)q, ldq, (const bf16_t*)k, \
                      (const bf16_t*)v, ldkv, (bf16_t*)o, ldo, nbatch, heads, Nq, Nk, kv_div, sl2, qb, kvb_v, lse)
@@ -719,7 +719,7 @@ extern "C" int vst_spatial_attention(const void* q, int ldq, const void* k, cons
     const dim3 g2(((Nq + 127) / 128) * heads * nbatch);
     hipLaunchKernelGGL(sa_self_kernel, g2, dim3(256), SA_LDS, st, (const bf16_t*)q, ldq, (const bf16_t*)k,
                        (const bf16_t*)v, ldkv, (bf16_t*)o, ldo, nbatch, heads, Nq, Nk, sl2, qb, kvb_v, lse);
-    return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
+    return launch_status();
   }
   switch (pre) {
     case 1: VST_SA_LAUNCH(1); break;
@@ -727,7 +727,7 @@ extern "C" int vst_spatial_attention(const void* q, int ldq, const void* k, cons
     default: VST_SA_LAUNCH(0); break;
   }
 #undef VST_SA_LAUNCH
-  return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
+  return launch_status();
 }
 
 // Causal self-attention over N tokens, head_dim 64 (the CLIP text encoders' CLIPAttention with the causal mask of
@@ -744,8 +744,8 @@ extern "C" int vst_causal_attention(const void* q, int ldq, const void* k, const
   const dim3 grid(nqb * heads * nbatch);
   hipLaunchKernelGGL(spatial_attn_kernel<0>, grid, dim3(256), SA_LDS, (hipStream_t)stream, (const bf16_t*)q, ldq,
                      (const bf16_t*)k, (const bf16_t*)v, ldkv, (bf16_t*)o, ldo, nbatch, heads, N, N, 1,
-                     scale * 1.4426950408889634f, qb, kvb, (float*)nullptr, 1);
-  return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
+                     scale * kLog2e, qb, kvb, (float*)nullptr, 1);
+  return launch_status();
 }
 
 extern "C" int vst_temporal_attention(const void* q, const void* k, const void* v, int ldqkv, void* o, int ldo,
@@ -755,7 +755,7 @@ extern "C" int vst_temporal_attention(const void* q, const void* k, const void* 
   if ((ldqkv & 7) || (ldo & 7) || (head_dim & 7)) return VST_ERR_ARG;
   const uint32_t bytes = fit(((size_t)(nclip * F * HW - 1) * ldqkv + heads * head_dim) * 2);
   if (fit.over) return VST_ERR_ARG;  // past the 32-bit buffer offsets: refuse, never read zeros
-  const float sl2 = scale * 1.4426950408889634f;
+  const float sl2 = scale * kLog2e;
   hipStream_t s = (hipStream_t)stream;
   const bf16_t *Q = (const bf16_t*)q, *K = (const bf16_t*)k, *V = (const bf16_t*)v;
   bf16_t* O = (bf16_t*)o;
@@ -777,7 +777,7 @@ extern "C" int vst_temporal_attention_bwd(const void* q, const void* k, const vo
   const uint32_t qkvb = fit(((size_t)(nclip * F * HW - 1) * ldqkv + heads * head_dim) * 2);
   const uint32_t dob = fit(((size_t)(nclip * F * HW - 1) * lddo + heads * head_dim) * 2);
   if (fit.over) return VST_ERR_ARG;  // past the 32-bit buffer offsets: refuse, never read zeros
-  const float sl2 = scale * 1.4426950408889634f;
+  const float sl2 = scale * kLog2e;
   hipStream_t s = (hipStream_t)stream;
   const bf16_t *Q = (const bf16_t*)q, *K = (const bf16_t*)k, *V = (const bf16_t*)v, *G = (const bf16_t*)dout;
   bf16_t *GQ = (bf16_t*)dq, *GK = (bf16_t*)dk, *GV = (bf16_t*)dv;
@@ -789,7 +789,7 @@ extern "C" int vst_temporal_attention_bwd(const void* q, const void* k, const vo
     hipLaunchKernelGGL((temporal_attn_bwd_kernel<S::NT, S::D>), dim3((unsigned)((units + wpg - 1) / wpg)),
                        dim3(64 * wpg), wpg * wave_bytes, s, Q, K, V, ldqkv, G, lddo, GQ, GK, GV, lddqkv, nclip, F, HW,
                        heads, scale, sl2, qkvb, dob);
-    return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
+    return launch_status();
   });
 }
 
@@ -811,7 +811,7 @@ extern "C" int vst_spatial_attention_bwd(const void* q, int ldq, const void* k, 
   hipStream_t s = (hipStream_t)stream;
   float* dvec = (float*)workspace;
   const int nkv = nbatch / kv_div;
-  const float sl2 = scale * 1.4426950408889634f;
+  const float sl2 = scale * kLog2e;
   const uint32_t qb = fit(((size_t)(nbatch * Nq - 1) * ldq + heads * 64) * 2);
   const uint32_t ob = fit(((size_t)(nbatch * Nq - 1) * ldo + heads * 64) * 2);
   const uint32_t dob = fit(((size_t)(nbatch * Nq - 1) * lddo + heads * 64) * 2);
@@ -826,5 +826,5 @@ extern "C" int vst_spatial_attention_bwd(const void* q, int ldq, const void* k, 
                        (const bf16_t*)q, ldq, (const bf16_t*)k, (const bf16_t*)v, ldkv, (const bf16_t*)dout, lddo, lse,
                        dvec, (bf16_t*)dk, (bf16_t*)dv, lddkv, nkv, heads, Nq, Nk, kv_div, scale, sl2, qb, dob, kvb);
   }
-  return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
+  return launch_status();
 }

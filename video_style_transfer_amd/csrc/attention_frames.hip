@@ -255,6 +255,6 @@ extern "C" int vst_spatial_attention_frames(const void* q, int ldq, const void* 
   if (nwg > 0x7fffffffULL) return VST_ERR_ARG;
   hipLaunchKernelGGL(sa_frames_kernel, dim3((unsigned)nwg), dim3(256), SA_LDS, (hipStream_t)stream, (const bf16_t*)q,
                      ldq, (const bf16_t*)k, (const bf16_t*)v, ldkv, (bf16_t*)o, ldo, nclip, F, heads, N, src1, src2,
-                     scale * 1.4426950408889634f, qb, kvb);
-  return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
+                     scale * kLog2e, qb, kvb);
+  return launch_status();
 }

@@ -599,7 +599,7 @@ extern "C" int vst_vae_sample(const void* moments, int ld, int n, int HW, const 
 extern "C" int vst_softmax_rows(const float* S, int lds, int rows, int n, float scale, void* P, int ldp, void* stream) {
   if (!S || !P || rows <= 0 || n <= 0 || lds < n || ldp < n || (lds & 3) || (ldp & 3)) return VST_ERR_ARG;
   hipLaunchKernelGGL(softmax_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, S, lds, rows, n,
-                     scale * 1.4426950408889634f, (bf16_t*)P, ldp);
+                     scale * kLog2e, (bf16_t*)P, ldp);
   return launch_status();
 }
 

@@ -188,7 +188,7 @@ __global__ __launch_bounds__(256, 2) void conv_gather_kernel(GemmArgs p) {
 static int launch_gather(const GemmArgs& a, hipStream_t s) {
   const int nwg = ((a.M + BM - 1) / BM) * ((a.N + GBN - 1) / GBN);
   hipLaunchKernelGGL(conv_gather_kernel, dim3(nwg), dim3(256), GATHER_LDS, s, a);
-  return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
+  return launch_status();
 }
 
 
@@ -292,7 +292,7 @@ static int launch_skinny(const GemmArgs& a, hipStream_t s) {
     case 4: hipLaunchKernelGGL(gemm_skinny_kernel<4>, grid, dim3(512), 0, s, a); break;
     default: return VST_ERR_ARG;
   }
-  return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
+  return launch_status();
 }
 
 // Row-vector GEMM for M <= 8 (the time-embedding MLPs and the batched time_emb_proj of every ResnetBlock2D: M = the
@@ -372,7 +372,7 @@ static int launch_rows(const GemmArgs& a, hipStream_t s) {
   if (a.M <= 2) hipLaunchKernelGGL(gemm_rows_kernel<2>, grid, dim3(256), 0, s, a);
   else if (a.M <= 4) hipLaunchKernelGGL(gemm_rows_kernel<4>, grid, dim3(256), 0, s, a);
   else hipLaunchKernelGGL(gemm_rows_kernel<8>, grid, dim3(256), 0, s, a);
-  return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
+  return launch_status();
 }
 
 // Sum the ring kernel's split-K slabs and apply the epilogue.  geglu: slab columns are the interleaved
@@ -685,7 +685,7 @@ static int launch_plan(GemmArgs& a, const GemmPlan& p, hipStream_t s) {
   const size_t chunks = (size_t)a.M * ((Nout + 7) / 8);
   const int grid = (int)std::min<size_t>((chunks + 255) / 256, 4096);
   hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3(grid), dim3(256), 0, s, a, p.epi == 1 ? 1 : 0);
-  return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
+  return launch_status();
 }
 
 }  // namespace vst
@@ -726,7 +726,6 @@ extern "C" size_t vst_gemm_workspace_bytes(int M, int N, int K) {
 
 // ---------------- entry points ----------------
 constexpr size_t kMaxExtent = 0x7fffffffULL;  // the largest byte extent a buffer descriptor's 32-bit offsets reach
-constexpr float kLog2e = 1.4426950408889634f;
 
 // GemmArgs of a dense call: A [M][K1] (row stride lda; vst_gemm_ex adds the second source), W [N][K], bias, C, the
 // operands' extents through fit, one split, stride 1.  Everything else is zero.

@@ -465,7 +465,7 @@ static int launch_ring_k(const GemmArgs& a, hipStream_t s, dim3 grid) {
     attr = true;
   }
   hipLaunchKernelGGL((gemm_ring_kernel<Cfg, AMODE, EPI>), grid, dim3(Cfg::THREADS), Cfg::LDS, s, a);
-  return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
+  return launch_status();
 }
 
 template <class Cfg, int AMODE, int EPI>

@@ -1122,7 +1122,7 @@ static int launch_p8_tile_per_wg(const GemmArgs& a, hipStream_t s) {
   }
   const int nwg = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
   hipLaunchKernelGGL((gemm_p8_kernel<EPI, BN, LORA, BM, CONV, false, GATE>), dim3(nwg), dim3(512), lds, s, a);
-  return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
+  return launch_status();
 }
 
 // Persistent tiles (default; VST_P8_PERSIST=0 restores one workgroup per tile): a grid of one workgroup per CU walks
@@ -1143,7 +1143,7 @@ static int launch_p8_persist(const GemmArgs& a, hipStream_t s) {
   const int grid = ntiles < p8_cus() ? (ntiles & ~7) : p8_cus();
   if (grid < 8) return VST_ERR_ARG;
   hipLaunchKernelGGL((gemm_p8_kernel<EPI, BN, LORA, BM, false, true, GATE>), dim3(grid), dim3(512), 160 * 1024, s, a);
-  return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
+  return launch_status();
 }
 
 // BN = 320 runs 128-row tiles (P8Cfg).  The persistent grid exists for the plain / GEGLU / GELU epilogues and for the

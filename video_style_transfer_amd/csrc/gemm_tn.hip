@@ -192,5 +192,5 @@ extern "C" int vst_gemm_tn(const void* A, int lda, const void* B, int ldb, int M
     hipLaunchKernelGGL(gemm_tn_reduce_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s,
                        (const float*)workspace, splits, N, K, (bf16_t*)C, ldc);
   }
-  return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
+  return launch_status();
 }

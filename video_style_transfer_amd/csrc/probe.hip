@@ -180,7 +180,7 @@ extern "C" int vst_probe_mix(int mode, int pieces, const void* src, int bytes, i
   else if (mode == 2 && pieces == 8) VST_MIX(2, 8);
   else return VST_ERR_ARG;
 #undef VST_MIX
-  return hipGetLastError() == hipSuccess ? 0 : VST_ERR_LAUNCH;
+  return vst::launch_status();
 }
 
 extern "C" int vst_probe_fetch(int mode, const void* src, int bytes, int grid, int iters, unsigned* out, void* stream) {
@@ -192,17 +192,17 @@ extern "C" int vst_probe_fetch(int mode, const void* src, int bytes, int grid, i
     case 2: hipLaunchKernelGGL(vst::probe_fetch_kernel<2>, dim3(grid), dim3(512), 65536, s, src, bytes, iters, out); break;
     default: return VST_ERR_ARG;
   }
-  return hipGetLastError() == hipSuccess ? 0 : VST_ERR_LAUNCH;
+  return vst::launch_status();
 }
 
 extern "C" int vst_probe_mfma(int grid, int iters, float* out, void* stream) {
   if (grid <= 0 || iters <= 0 || !out) return VST_ERR_ARG;
   hipLaunchKernelGGL(vst::probe_mfma_kernel, dim3(grid), dim3(512), 0, (hipStream_t)stream, iters, out);
-  return hipGetLastError() == hipSuccess ? 0 : VST_ERR_LAUNCH;
+  return vst::launch_status();
 }
 
 extern "C" int vst_probe_hbm_read(const void* src, size_t bytes, int grid, unsigned* out, void* stream) {
   if (!src || bytes < 16 || grid <= 0 || !out) return VST_ERR_ARG;
   hipLaunchKernelGGL(vst::probe_hbm_read_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, src, bytes, out);
-  return hipGetLastError() == hipSuccess ? 0 : VST_ERR_LAUNCH;
+  return vst::launch_status();
 }

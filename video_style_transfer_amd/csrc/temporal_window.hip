@@ -220,7 +220,7 @@ static int launch_windowed(const bf16_t* Q, const bf16_t* K, const bf16_t* V, in
   hipLaunchKernelGGL((temporal_attn_windowed_kernel<NT, D>), dim3((units + wpg - 1) / wpg), dim3(64 * wpg),
                      wpg * W::WBYTES, s, Q, K, V, ld, PQ, PK, PV, ldpos, O, ldo, nclip, F, HW, heads, L, S, pyramid,
                      sl2, bytes);
-  return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH;
+  return launch_status();
 }
 
 }  // namespace vst
@@ -243,7 +243,7 @@ extern "C" int vst_temporal_attention_windowed(const void* q, const void* k, con
   if ((size_t)nclip * F * HW > 0x7fffffffULL) return VST_ERR_ARG;
   const uint32_t bytes = fit(((size_t)(nclip * F * HW - 1) * ldqkv + heads * head_dim) * 2);
   if (fit.over) return VST_ERR_ARG;  // past the 32-bit buffer offsets: refuse, never read zeros
-  const float sl2 = scale * 1.4426950408889634f;
+  const float sl2 = scale * kLog2e;
   hipStream_t s = (hipStream_t)stream;
   const bf16_t *Q = (const bf16_t*)q, *K = (const bf16_t*)k, *V = (const bf16_t*)v;
   bf16_t* O = (bf16_t*)o;

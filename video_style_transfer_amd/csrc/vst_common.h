@@ -8,6 +8,8 @@
 #include <stdlib.h>
 #include <algorithm>
 
+#include "../../include/vst.h"  // the C ABI: every entry point is defined with its prototype (and VST_* status) in sight
+
 namespace vst {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -158,13 +160,9 @@ __device__ __forceinline__ int xcd_remap(int orig, int nwg) {
 
 }  // namespace vst
 
-// C-ABI status codes (see include/vst.h)
-#define VST_OK 0
-#define VST_ERR_ARG 1
-#define VST_ERR_LAUNCH 2
-#define VST_ERR_UNSUPPORTED 3
-
 namespace vst {
+// Host side: log2(e), folded into a softmax scale so the kernels exponentiate with v_exp_f32 (2^x).
+constexpr float kLog2e = 1.4426950408889634f;
 // Host side: the status an entry point returns after its launches.
 inline int launch_status() { return hipGetLastError() == hipSuccess ? VST_OK : VST_ERR_LAUNCH; }
 // Host side: 256-thread blocks for a grid-stride kernel over `total` items.

@@ -4,6 +4,9 @@ Every function takes device tensors (bf16 activations/weights, fp32 bias/norm pa
 shapes, and launches on torch's current HIP stream.  Activations are token-major 2-D views
 [rows, C] (row stride may exceed C, e.g. a column slice of a fused QKV buffer).
 No CPU fallback exists: a CPU tensor or a missing library raises.
+
+Every pointer handed to the library has either passed one of the validators below (_view, _block, _vec, _table,
+_qkv) or was allocated by the wrapper itself a few lines above the call (DESIGN.md "Entry points").
 """
 from __future__ import annotations
 
@@ -13,6 +16,7 @@ from . import _lib
 
 BF16 = torch.bfloat16
 F32 = torch.float32
+I32 = torch.int32
 
 
 def _stream():
@@ -116,13 +120,15 @@ def _splits():
     return s if s or not _ROW_INVARIANT[0] else 1
 
 
+_WS = {}
+_WS_BYTES = 80 << 20  # fp32 split-K slabs
+
+
 def gemm_kernel_name(M, N, K, kind):
     """Kernel the library launches for a GEMM / conv of this size (kind: 0 linear, 1 GEGLU, 2 conv,
     3 scalar-gather conv) under the current GEMM_POLICY."""
     name = _lib.load().vst_gemm_kernel_name(M, N, K, kind, GEMM_POLICY["tile"], _splits(), _WS_BYTES)
     return name.decode() if name else None
-_WS = {}
-_WS_BYTES = 80 << 20  # fp32 split-K slabs
 
 
 def _workspace(device):
@@ -136,39 +142,77 @@ def _workspace(device):
     return ws
 
 
-def _out(t, shape, dtype, name, fn):
-    """Validate an output view before a launch writes it through its raw pointer: on the device, the expected dtype,
-    2-D with unit column stride, exactly `shape`.  A kernel given anything else writes outside the view."""
+# ---- operand validators: what a kernel addresses through a raw pointer is checked here, on the host, first ----
+def _fail(fn, name, why):
+    raise _lib.VstError(f"{fn}: {name} {why}")
+
+
+def _on_device(t, dtype, name, fn):
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise _lib.VstError(f"{fn}: {name} must be a device tensor; the HIP path has no CPU fallback")
+        _fail(fn, name, "must be a device tensor; the HIP path has no CPU fallback")
     if t.dtype != dtype:
-        raise _lib.VstError(f"{fn}: {name} expected {dtype}, got {t.dtype}")
-    if t.dim() != 2 or t.stride(1) != 1:
-        raise _lib.VstError(f"{fn}: {name} expected a 2-D row-major view, got shape {tuple(t.shape)} stride "
-                            f"{t.stride()}")
-    if tuple(t.shape) != tuple(shape):
-        raise _lib.VstError(f"{fn}: {name} shape {tuple(t.shape)} != {tuple(shape)}")
+        _fail(fn, name, f"expected {dtype}, got {t.dtype}")
     return t
 
 
-def _out_flat(t, shape, dtype, name, fn):
-    """Validate an output the kernel addresses as one contiguous block (no row stride in its ABI)."""
+def _view(t, dtype, name, fn, shape=None, rows=None, min_cols=None):
+    """A 2-D row view (an operand whose ABI carries a row stride): on the device, `dtype`, unit column stride; with
+    `shape` exactly that shape, with `rows` that many rows, with `min_cols` at least that many columns.  A kernel
+    given anything else reads or writes outside the view."""
+    _on_device(t, dtype, name, fn)
+    if t.dim() != 2 or t.stride(1) != 1:
+        _fail(fn, name, f"expected a 2-D row-major view, got shape {tuple(t.shape)} stride {t.stride()}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        _fail(fn, name, f"shape {tuple(t.shape)} != {tuple(shape)}")
+    if (rows is not None and t.shape[0] != rows) or (min_cols is not None and t.shape[1] < min_cols):
+        _fail(fn, name, f"shape {tuple(t.shape)}: expected {'any' if rows is None else rows} rows of >= "
+                        f"{min_cols or 0} columns")
+    return t
+
+
+def _block(t, dtype, name, fn, shape=None, numel=None):
+    """A tensor the kernel addresses as one contiguous block (no row stride in its ABI): on the device, `dtype`,
+    contiguous, of `shape` (or of `numel` elements in any shape; neither: any size)."""
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise _lib.VstError(f"{fn}: {name} must be a device tensor; the HIP path has no CPU fallback")
-    if t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
-        raise _lib.VstError(f"{fn}: {name} must be contiguous {dtype} {tuple(shape)}, got {t.dtype} "
-                            f"{tuple(t.shape)} stride {t.stride()}")
+        _fail(fn, name, "must be a device tensor; the HIP path has no CPU fallback")
+    if t.dtype != dtype or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)) \
+            or (numel is not None and t.numel() != numel):
+        want = f" {tuple(shape)}" if shape is not None else ("" if numel is None else f" [{numel}]")
+        _fail(fn, name, f"must be contiguous {dtype}{want}, got {t.dtype} {tuple(t.shape)} stride {t.stride()}")
     return t
 
 
-def _dev(t: torch.Tensor, dtype, name):
-    if not t.is_cuda:
-        raise _lib.VstError(f"{name}: tensor is on {t.device}; the HIP path has no CPU fallback")
-    if t.dtype != dtype:
-        raise _lib.VstError(f"{name}: expected {dtype}, got {t.dtype}")
-    if t.dim() != 2 or t.stride(1) != 1:
-        raise _lib.VstError(f"{name}: expected a 2-D row-major view, got shape {tuple(t.shape)} stride {t.stride()}")
-    return t
+def _vec(t, n, name, fn):
+    """An fp32 per-channel vector of n elements on the device (bias, gamma, beta), read as float4s."""
+    return _block(t, F32, name, fn, numel=n)
+
+
+def _table(t, rows, cols, name, fn, exact=True, align=True):
+    """An fp32 table the kernel reads by row (row_bias, gate, pos, pe): a 2-D device view with unit column stride, at
+    least `rows` rows and exactly (exact=False: at least) `cols` columns; align: the rows are read as float4s, so the
+    base is 16-byte aligned and the row stride a multiple of 4.  Returns the row stride to pass (a single row's own
+    stride is never used: `cols`)."""
+    _on_device(t, F32, name, fn)
+    if t.dim() != 2 or t.stride(1) != 1 or t.shape[0] < rows or (t.shape[1] != cols if exact else t.shape[1] < cols):
+        _fail(fn, name, f"must be a 2-D fp32 view of >= {rows} rows x {cols} columns with unit column stride, got "
+                        f"shape {tuple(t.shape)} stride {t.stride()}")
+    ld = t.stride(0) if t.shape[0] > 1 else cols
+    if align and (ld < cols or ld % 4 or t.data_ptr() % 16):
+        _fail(fn, name, f"needs a row stride >= {cols} that is a multiple of 4 and a 16-byte aligned base, got "
+                        f"stride {t.stride()}")
+    return ld
+
+
+def _qkv(fn, q, k, v, rows, kv_rows=None, q_shares=False, **like_q):
+    """The q/k/v triple of an attention entry: bf16 views of `rows` (k / v: `kv_rows`, default `rows`) rows; k and v
+    share one row stride (q_shares: q too, the entries with a single ldqkv); like_q: further views of q's row count
+    (o, dout)."""
+    kv_rows = rows if kv_rows is None else kv_rows
+    for name, t, n in (("q", q, rows), ("k", k, kv_rows), ("v", v, kv_rows)) + tuple((m, t, rows)
+                                                                                     for m, t in like_q.items()):
+        _view(t, BF16, name, fn, rows=n)
+    if k.stride(0) != v.stride(0) or (q_shares and q.stride(0) != k.stride(0)):
+        _fail(fn, "q/k/v" if q_shares else "k and v", "must share a row stride")
 
 
 def _p(t):
@@ -179,45 +223,46 @@ def _ld(t):
     return t.stride(0) if t.shape[0] > 1 else t.shape[1]
 
 
+def _new(out, shape, like, name, fn, dtype=BF16):
+    """The output view: `out` validated as exactly `shape`, or a fresh tensor next to `like`."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=like.device)
+    return _view(out, dtype, name, fn, shape=shape)
+
+
 def linear(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None = None, *, x2: torch.Tensor | None = None,
            residual: torch.Tensor | None = None, row_bias: torch.Tensor | None = None, row_bias_div: int = 1,
            out: torch.Tensor | None = None, geglu: bool = False, alg_k2: int | None = None,
            kind: str | None = None, alg_n: int | None = None, act: str | None = None) -> torch.Tensor:
     """out[M, N'] = epilogue([x | x2] @ w^T + bias + row_bias[m // div] + residual); N' = N or N/2 (GEGLU).
     act="gelu": GELU(erf) of (x @ w^T + bias) — no residual / row bias with it."""
-    _dev(x, BF16, "x")
-    _dev(w, BF16, "w")
+    fn = "linear"
+    _view(x, BF16, "x", fn)
+    _view(w, BF16, "w", fn)
     M, K1 = x.shape
     N, K = w.shape
     if x2 is not None:
-        _dev(x2, BF16, "x2")
-        if x2.shape[0] != M or K1 + x2.shape[1] != K:
+        _view(x2, BF16, "x2", fn, rows=M)
+        if K1 + x2.shape[1] != K:
             raise _lib.VstError(f"linear: x {tuple(x.shape)} + x2 {tuple(x2.shape)} vs w {tuple(w.shape)}")
     elif K1 != K:
         raise _lib.VstError(f"linear: x {tuple(x.shape)} vs w {tuple(w.shape)}")
     if act not in (None, "gelu") or (act and (geglu or residual is not None or row_bias is not None)):
         raise _lib.VstError(f"linear: act={act!r} supports only bias (no GEGLU / residual / row bias)")
     n_out = N // 2 if geglu else N
-    if out is None:
-        out = torch.empty((M, n_out), dtype=BF16, device=x.device)
-    _out(out, (M, n_out), BF16, "out", "linear")
-    if bias is not None and (bias.dtype != F32 or bias.numel() != N or not bias.is_cuda):
-        raise _lib.VstError("linear: bias must be fp32 [N] on device")
+    out = _new(out, (M, n_out), x, "out", fn)
+    if bias is not None:
+        _vec(bias, N, "bias", fn)
     if residual is not None:
-        _dev(residual, BF16, "residual")
-        if residual.shape != (M, n_out):
-            raise _lib.VstError("linear: residual shape mismatch")
+        _view(residual, BF16, "residual", fn, shape=(M, n_out))
+    ldrb = 0
     if row_bias is not None:
-        if row_bias.dtype != F32 or not row_bias.is_cuda or row_bias.shape[-1] != N:
-            raise _lib.VstError("linear: row_bias must be fp32 [M/div, N]")
-        if row_bias.dim() == 2 and row_bias.shape[0] > 1 and (row_bias.stride(1) != 1 or row_bias.stride(0) % 4
-                                                              or row_bias.data_ptr() % 16):
-            raise _lib.VstError("linear: row_bias view needs unit column stride, a row stride that is a multiple of "
-                                "4 and a 16-byte aligned base")
-        if row_bias.dim() != 2 and not row_bias.is_contiguous():
-            raise _lib.VstError("linear: row_bias must be a 2-D view or contiguous")
-        if row_bias_div <= 0 or (M - 1) // row_bias_div >= row_bias.numel() // N:
-            raise _lib.VstError(f"linear: row_bias has {row_bias.numel() // N} rows, M={M} div={row_bias_div}")
+        if row_bias_div <= 0:
+            raise _lib.VstError(f"linear: row_bias_div {row_bias_div}")
+        rb = row_bias  # (a contiguous table of any rank whose last dimension is N is its [rows, N] form)
+        if isinstance(rb, torch.Tensor) and rb.dim() != 2 and rb.is_contiguous() and rb.numel() and rb.shape[-1] == N:
+            rb = rb.view(-1, N)
+        ldrb = _table(rb, (M - 1) // row_bias_div + 1, N, "row_bias", fn)
     # algorithmic work: the LoRA columns count only their real rank (alg_k2), not the zero padding
     k_alg = K1 + (0 if x2 is None else (x2.shape[1] if alg_k2 is None else alg_k2))
     kind = kind or ("gemm_geglu" if geglu else ("gemm_lora" if x2 is not None and alg_k2 is not None else "gemm"))
@@ -226,8 +271,7 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None = None, *
               lambda: gemm_kernel_name(M, N, K, 1 if geglu else 0), (M, N, K)):
         ws = _workspace(x.device)
         _lib.call("vst_gemm_ex", _p(x), _ld(x), _p(x2), 0 if x2 is None else _ld(x2), K1, _p(w), _ld(w), M, N, K,
-                  _p(bias), _p(row_bias), row_bias_div,
-                  0 if row_bias is None else (_ld(row_bias) if row_bias.dim() == 2 else N), _p(residual),
+                  _p(bias), _p(row_bias), row_bias_div, ldrb, _p(residual),
                   0 if residual is None else _ld(residual), _p(out), _ld(out), 1 if geglu else (2 if act else 0),
                   GEMM_POLICY["tile"], _splits(), _p(ws), _WS_BYTES, _stream())
     return out
@@ -236,15 +280,12 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None = None, *
 def linear_tn(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
     """out[N, K] (bf16) = a^T b with a [M, N] and b [M, K] row-major over the M tokens (vst_gemm_tn): the weight
     gradients of the training backward (dW = g^T x, dA = s v^T x, dB = s g^T u) without transposed copies."""
-    _dev(a, BF16, "a")
-    _dev(b, BF16, "b")
+    fn = "linear_tn"
+    _view(a, BF16, "a", fn)
     M, N = a.shape
-    if b.shape[0] != M:
-        raise _lib.VstError(f"linear_tn: a {tuple(a.shape)} and b {tuple(b.shape)} differ in tokens")
+    _view(b, BF16, "b", fn, rows=M)
     K = b.shape[1]
-    if out is None:
-        out = torch.empty((N, K), dtype=BF16, device=a.device)
-    _out(out, (N, K), BF16, "out", "linear_tn")
+    out = _new(out, (N, K), a, "out", fn)
     wsb = int(_lib.load().vst_gemm_tn_workspace_bytes(M, N, K))
     ws = torch.empty(max(wsb // 4, 1), dtype=F32, device=a.device) if wsb else None
     with _Rec("gemm_tn", 2.0 * M * N * K, 2.0 * (M * N + M * K + N * K), lambda: "gemm_tn", (N, K, M)):
@@ -253,70 +294,51 @@ def linear_tn(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor | None = None)
 
 
 _LORA_BN = {}
+_XATTN_OK = {}
 
 
-class p8_conv:
-    """Context manager routing 3x3 convs to the 8-phase kernel (on=True) or the ring kernel (vst_p8_conv); tests and
-    A/B runs only."""
+class _Toggle:
+    """Context manager around one of the library's process-wide test / A-B switches: `entry(value)` on entry (it
+    returns the previous setting), `entry(previous)` on exit; `caches` (host policy answers that depend on the switch)
+    are cleared both times.  Tests and A/B runs only."""
 
-    def __init__(self, on=True):
-        self.on = int(bool(on))
+    def __init__(self, entry, value, caches=()):
+        self.entry, self.value, self.caches = entry, int(value), caches
+
+    def _set(self, value):
+        prev = int(getattr(_lib.load(), self.entry)(value))
+        for c in self.caches:
+            c.clear()
+        return prev
 
     def __enter__(self):
-        self.prev = int(_lib.load().vst_p8_conv(self.on))
+        self.prev = self._set(self.value)
         return self
 
     def __exit__(self, *a):
-        _lib.load().vst_p8_conv(self.prev)
+        self._set(self.prev)
 
 
-class p8_persist:
-    """Context manager switching the 8-phase GEMM's persistent grid on / off (vst_p8_persist) for the GEMMs launched
-    inside it; tests and A/B runs only (the outputs are the same bits either way)."""
-
-    def __init__(self, on=True):
-        self.on = int(bool(on))
-
-    def __enter__(self):
-        self.prev = int(_lib.load().vst_p8_persist(self.on))
-        return self
-
-    def __exit__(self, *a):
-        _lib.load().vst_p8_persist(self.prev)
+def p8_conv(on=True):
+    """Inside: 3x3 convs run on the 8-phase kernel (on=True) or the ring kernel (vst_p8_conv)."""
+    return _Toggle("vst_p8_conv", bool(on))
 
 
-class sa_self:
-    """Context manager routing the long self-attention to sa_self_kernel (on=True, the default) or to the general
-    spatial kernel (vst_sa_self); tests and A/B runs only (the outputs are the same bits either way)."""
-
-    def __init__(self, on=True):
-        self.on = int(bool(on))
-
-    def __enter__(self):
-        self.prev = int(_lib.load().vst_sa_self(self.on))
-        return self
-
-    def __exit__(self, *a):
-        _lib.load().vst_sa_self(self.prev)
+def p8_persist(on=True):
+    """Inside: the 8-phase GEMM's persistent grid is on / off (vst_p8_persist); the outputs are the same bits."""
+    return _Toggle("vst_p8_persist", bool(on))
 
 
-class p8_tile_width:
-    """Context manager forcing the 8-phase GEMM's tile width (256 / 192 / 320 where legal; 0 = the library's
-    policy) for the GEMMs launched inside it (vst_p8_force_bn); tests and A/B runs only."""
+def sa_self(on=True):
+    """Inside: the long self-attention runs on sa_self_kernel (on=True, the default) or on the general spatial kernel
+    (vst_sa_self); the outputs are the same bits."""
+    return _Toggle("vst_sa_self", bool(on))
 
-    def __init__(self, bn):
-        self.bn = int(bn)
 
-    def __enter__(self):
-        self.prev = int(_lib.load().vst_p8_force_bn(self.bn))
-        _LORA_BN.clear()
-        _XATTN_OK.clear()
-        return self
-
-    def __exit__(self, *a):
-        _lib.load().vst_p8_force_bn(self.prev)
-        _LORA_BN.clear()
-        _XATTN_OK.clear()
+def p8_tile_width(bn):
+    """Inside: the 8-phase GEMM's tile width is forced (256 / 192 / 320 where legal; 0 = the library's policy)
+    (vst_p8_force_bn)."""
+    return _Toggle("vst_p8_force_bn", bn, (_LORA_BN, _XATTN_OK))
 
 
 def gemm_lora_tile(M, N, K, P, group_n, group_r):
@@ -329,36 +351,25 @@ def gemm_lora_tile(M, N, K, P, group_n, group_r):
     return bn
 
 
-def _check_gate(gate, gate_div, M, P, what):
-    """The row gate of the gated entries: fp32 [>= ceil(M / gate_div), >= P] on the device, unit column stride, row
-    stride a multiple of 4, 16-byte aligned."""
-    if not isinstance(gate, torch.Tensor) or gate.dtype != F32 or not gate.is_cuda or gate.dim() != 2:
-        raise _lib.VstError(f"{what}: gate must be a 2-D fp32 device tensor")
+def _gate(gate, gate_div, M, P, fn):
+    """The row gate of the gated entries: an fp32 table of >= ceil(M / gate_div) rows x >= P columns (a single row of
+    any stride).  Returns the three arguments the gated entries append."""
     if int(gate_div) <= 0:
-        raise _lib.VstError(f"{what}: gate_div {gate_div}")
-    ng = (M + int(gate_div) - 1) // int(gate_div)
-    if gate.shape[0] < ng or gate.shape[1] < P:
-        raise _lib.VstError(f"{what}: gate {tuple(gate.shape)} for {ng} gate rows x {P} u columns")
-    if gate.stride(1) != 1 or (gate.shape[0] > 1 and (gate.stride(0) < P or gate.stride(0) & 3)) or gate.data_ptr() & 15:
-        raise _lib.VstError(f"{what}: gate strides {gate.stride()} / alignment")
-
-
-def _gate_ld(gate, P):
-    return gate.stride(0) if gate.shape[0] > 1 else P  # (one gate row: its stride is never used)
+        raise _lib.VstError(f"{fn}: gate_div {gate_div}")
+    ld = _table(gate, (M + int(gate_div) - 1) // int(gate_div), P, "gate", fn, exact=False)
+    return [_p(gate), ld, int(gate_div)]
 
 
 def lora_gate(u: torch.Tensor, gate: torch.Tensor, gate_div: int, out: torch.Tensor | None = None) -> torch.Tensor:
     """out[m, c] = bf16(gate[m // gate_div, c] * float(u[m, c])) (vst_lora_gate): the per-row content / style gate on
     an explicit LoRA down-projection u [M, P]; out may be u itself."""
-    _dev(u, BF16, "u")
+    fn = "lora_gate"
+    _view(u, BF16, "u", fn)
     M, P = u.shape
-    _check_gate(gate, gate_div, M, P, "lora_gate")
-    if out is None:
-        out = torch.empty((M, P), dtype=BF16, device=u.device)
-    _out(out, (M, P), BF16, "out", "lora_gate")
+    g = _gate(gate, gate_div, M, P, fn)
+    out = _new(out, (M, P), u, "out", fn)
     with _Rec("lora_gate", 1.0 * M * P, 4.0 * M * P, lambda: "lora_gate", (M, P)):
-        _lib.call("vst_lora_gate", _p(u), _ld(u), M, P, _p(gate), _gate_ld(gate, P), int(gate_div), _p(out), _ld(out),
-                  _stream())
+        _lib.call("vst_lora_gate", _p(u), _ld(u), M, P, *g, _p(out), _ld(out), _stream())
     return out
 
 
@@ -370,25 +381,21 @@ def linear_lora(x: torch.Tensor, w: torch.Tensor, a: torch.Tensor, group_n: int,
     (vst_gemm_lora).  w: [N, K + P] = [W | V], a: [P, K]; output columns n use u columns of group n // group_n.
     gate (fp32 [ceil(M / gate_div), >= P]): row m's u column c is scaled by gate[m // gate_div, c] after its bf16
     rounding and rounded again (vst_gemm_lora_gated); the same tile as without."""
-    _dev(x, BF16, "x")
-    _dev(w, BF16, "w")
-    _dev(a, BF16, "a")
+    fn = "linear_lora"
+    _view(x, BF16, "x", fn)
+    _view(w, BF16, "w", fn)
+    _view(a, BF16, "a", fn)
     M, K = x.shape
     N = w.shape[0]
     P = a.shape[0]
     if a.shape[1] != K or w.shape[1] != K + P:
         raise _lib.VstError(f"linear_lora: x {tuple(x.shape)} a {tuple(a.shape)} w {tuple(w.shape)}")
-    if out is None:
-        out = torch.empty((M, N), dtype=BF16, device=x.device)
-    _out(out, (M, N), BF16, "out", "linear_lora")
-    if bias is not None and (bias.dtype != F32 or bias.numel() != N or not bias.is_cuda):
-        raise _lib.VstError("linear_lora: bias must be fp32 [N] on device")
+    out = _new(out, (M, N), x, "out", fn)
+    if bias is not None:
+        _vec(bias, N, "bias", fn)
     if residual is not None:
-        _dev(residual, BF16, "residual")
-        if residual.shape != (M, N):
-            raise _lib.VstError("linear_lora: residual shape mismatch")
-    if gate is not None:
-        _check_gate(gate, gate_div, M, P, "linear_lora")
+        _view(residual, BF16, "residual", fn, shape=(M, N))
+    gated = [] if gate is None else _gate(gate, gate_div, M, P, fn)
     bn = gemm_lora_tile(M, N, K, P, group_n, group_r)
     if not bn:
         raise _lib.VstError(f"linear_lora: shape M={M} N={N} K={K} P={P} groups ({group_n}, {group_r}) unsupported")
@@ -397,20 +404,13 @@ def linear_lora(x: torch.Tensor, w: torch.Tensor, a: torch.Tensor, group_n: int,
     flops = 2.0 * M * N * (K + r) + 2.0 * M * K * r
     nbytes = 2.0 * (M * K + N * (K + r) + r * K + M * N * (2 if residual is not None else 1))
     sym = f"gemm_p8<128x{bn},lora>" if bn == 320 else f"gemm_p8<256x{bn},lora>"
-    if gate is not None:
+    if gated:
         sym = sym[:-1] + ",gate>"
     with _Rec("gemm_lora", flops, nbytes, lambda: sym, (M, N, K + P)):
-        if gate is None:
-            _lib.call("vst_gemm_lora", _p(x), _ld(x), _p(a), _ld(a), P, group_n, group_r, _p(w), _ld(w), M, N, K,
-                      _p(bias), _p(residual), 0 if residual is None else _ld(residual), _p(out), _ld(out), _stream())
-        else:
-            _lib.call("vst_gemm_lora_gated", _p(x), _ld(x), _p(a), _ld(a), P, group_n, group_r, _p(w), _ld(w), M, N, K,
-                      _p(bias), _p(residual), 0 if residual is None else _ld(residual), _p(out), _ld(out), _p(gate),
-                      _gate_ld(gate, P), int(gate_div), _stream())
+        _lib.call("vst_gemm_lora_gated" if gated else "vst_gemm_lora", _p(x), _ld(x), _p(a), _ld(a), P, group_n,
+                  group_r, _p(w), _ld(w), M, N, K, _p(bias), _p(residual), 0 if residual is None else _ld(residual),
+                  _p(out), _ld(out), *gated, _stream())
     return out
-
-
-_XATTN_OK = {}
 
 
 def cross_attention_fusable(M, N, K, lora, P, group_n, group_r, Nq, Nk):
@@ -433,15 +433,16 @@ def linear_cross_attention(x: torch.Tensor, w: torch.Tensor, a: torch.Tensor | N
     same launch (vst_gemm_cross_attention); k / v: [text_batches * Nk, N] views (row stride >= N), the text batch of
     frame f = (m // Nq) is f // kv_div.  gate / gate_div: the row gate of linear_lora on q's down-projection
     (vst_gemm_cross_attention_gated; needs a)."""
-    _dev(x, BF16, "x")
-    _dev(w, BF16, "w")
-    _dev(k, BF16, "k")
-    _dev(v, BF16, "v")
+    fn = "linear_cross_attention"
+    _view(x, BF16, "x", fn)
+    _view(w, BF16, "w", fn)
+    _view(k, BF16, "k", fn)
+    _view(v, BF16, "v", fn)
     M, K = x.shape
     N = w.shape[0]
     P = 0 if a is None else a.shape[0]
     if a is not None:
-        _dev(a, BF16, "a")
+        _view(a, BF16, "a", fn)
         if a.shape[1] != K or w.shape[1] != K + P:
             raise _lib.VstError(f"linear_cross_attention: x {tuple(x.shape)} a {tuple(a.shape)} w {tuple(w.shape)}")
     elif w.shape[1] != K:
@@ -450,32 +451,26 @@ def linear_cross_attention(x: torch.Tensor, w: torch.Tensor, a: torch.Tensor | N
         raise _lib.VstError(f"linear_cross_attention: k {tuple(k.shape)} v {tuple(v.shape)} N={N} Nk={Nk}")
     if M % Nq or (M // Nq - 1) // kv_div >= k.shape[0] // Nk:
         raise _lib.VstError(f"linear_cross_attention: M={M} Nq={Nq} kv_div={kv_div} vs {k.shape[0] // Nk} text rows")
-    if bias is not None and (bias.dtype != F32 or bias.numel() != N or not bias.is_cuda):
-        raise _lib.VstError("linear_cross_attention: bias must be fp32 [N] on device")
+    if bias is not None:
+        _vec(bias, N, "bias", fn)
+    gated = []
     if gate is not None:
         if a is None:
             raise _lib.VstError("linear_cross_attention: a gate needs the LoRA operand a")
-        _check_gate(gate, gate_div, M, P, "linear_cross_attention")
+        gated = _gate(gate, gate_div, M, P, fn)
     if not cross_attention_fusable(M, N, K, a is not None, P, group_n, group_r, Nq, Nk):
         raise _lib.VstError(f"linear_cross_attention: M={M} N={N} K={K} Nq={Nq} Nk={Nk} not fusable")
-    if out is None:
-        out = torch.empty((M, N), dtype=BF16, device=x.device)
-    _out(out, (M, N), BF16, "out", "linear_cross_attention")
+    out = _new(out, (M, N), x, "out", fn)
     r = P if r_alg is None else r_alg
     flops = 2.0 * M * N * (K + r) + 2.0 * M * K * r + 4.0 * M * N * Nk
     nbytes = 2.0 * (M * K + N * (K + r) + r * K + 2 * (k.shape[0]) * N + M * N)
     sym = "gemm_p8<256x192,lora,xattn>" if a is not None else "gemm_p8<256x192,xattn>"
-    if gate is not None:
+    if gated:
         sym = "gemm_p8<256x192,lora,gate,xattn>"
     with _Rec("gemm_xattn", flops, nbytes, lambda: sym, (M, N, K + P)):
-        if gate is None:
-            _lib.call("vst_gemm_cross_attention", _p(x), _ld(x), _p(a), 0 if a is None else _ld(a), P, group_n,
-                      group_r, _p(w), _ld(w), _p(bias), M, N, K, _p(k), _p(v), _ld(k), k.shape[0], Nq, Nk, kv_div,
-                      float(scale), _p(out), _ld(out), _stream())
-        else:
-            _lib.call("vst_gemm_cross_attention_gated", _p(x), _ld(x), _p(a), _ld(a), P, group_n, group_r, _p(w),
-                      _ld(w), _p(bias), M, N, K, _p(k), _p(v), _ld(k), k.shape[0], Nq, Nk, kv_div, float(scale),
-                      _p(out), _ld(out), _p(gate), _gate_ld(gate, P), int(gate_div), _stream())
+        _lib.call("vst_gemm_cross_attention_gated" if gated else "vst_gemm_cross_attention", _p(x), _ld(x), _p(a),
+                  0 if a is None else _ld(a), P, group_n, group_r, _p(w), _ld(w), _p(bias), M, N, K, _p(k), _p(v),
+                  _ld(k), k.shape[0], Nq, Nk, kv_div, float(scale), _p(out), _ld(out), *gated, _stream())
     return out
 
 
@@ -521,20 +516,17 @@ def linear_temporal_attention(x: torch.Tensor, w_t: torch.Tensor, b_t: torch.Ten
                               out: torch.Tensor | None = None) -> torch.Tensor:
     """o = the motion modules' frame-axis attention of q/k/v = x w^T + b, in one launch (vst_gemm_temporal_attention);
     x: [nclip*F*HW, K] rows (clip, frame, pixel), w_t / b_t from temporal_qkv_layout.  Returns [M, heads*head_dim]."""
-    _dev(x, BF16, "x")
-    _dev(w_t, BF16, "w_t")
+    fn = "linear_temporal_attention"
+    _view(x, BF16, "x", fn)
     M, K = x.shape
     N = heads // (256 // (3 * head_dim)) * 256
-    if w_t.shape != (N, K):
-        raise _lib.VstError(f"linear_temporal_attention: w_t {tuple(w_t.shape)} != {(N, K)}")
-    if b_t is not None and (b_t.dtype != F32 or b_t.numel() != N or not b_t.is_cuda):
-        raise _lib.VstError("linear_temporal_attention: b_t must be fp32 [N] on device")
+    _view(w_t, BF16, "w_t", fn, shape=(N, K))
+    if b_t is not None:
+        _vec(b_t, N, "b_t", fn)
     if not temporal_attention_fusable(M, K, nclip, F, HW, heads, head_dim):
         raise _lib.VstError(f"linear_temporal_attention: M={M} K={K} F={F} HW={HW} heads={heads} not fusable")
     C = heads * head_dim
-    if out is None:
-        out = torch.empty((M, C), dtype=BF16, device=x.device)
-    _out(out, (M, C), BF16, "out", "linear_temporal_attention")
+    out = _new(out, (M, C), x, "out", fn)
     flops = 2.0 * M * 3 * C * K + 4.0 * M * F * C
     nbytes = 2.0 * (M * K + 3 * C * K + M * C)
     with _Rec("gemm_tattn", flops, nbytes, lambda: "gemm_p8<256x256,tattn>", (M, N, K)):
@@ -543,22 +535,24 @@ def linear_temporal_attention(x: torch.Tensor, w_t: torch.Tensor, b_t: torch.Ten
     return out
 
 
+def _conv_in(x, rows, name, fn):
+    """A conv input: the kernels address it as one contiguous [nimg*H*W, C] bf16 block."""
+    _view(x, BF16, name, fn, rows=rows)
+    if not x.is_contiguous():
+        _fail(fn, name, f"must be contiguous [nimg*H*W, C], got stride {x.stride()}")
+    return x.shape[1]
+
+
 def conv3x3(x1: torch.Tensor, nimg: int, H: int, W: int, w: torch.Tensor, bias: torch.Tensor | None, *,
             x2: torch.Tensor | None = None, stride: int = 1, upsample: bool = False,
             row_bias: torch.Tensor | None = None, row_bias_div: int = 1, residual: torch.Tensor | None = None,
             out: torch.Tensor | None = None) -> torch.Tensor:
     """NHWC 3x3 conv (pad 1).  x1: [nimg*H*W, C1] (+ x2: [nimg*H*W, C2] concatenated on channels).
     w: [Cout, 9*(C1+C2)] laid out (ky, kx, ci).  Returns [nimg*OH*OW, Cout]."""
-    _dev(x1, BF16, "x1")
-    C1 = x1.shape[1]
-    C2 = 0
-    if x2 is not None:
-        _dev(x2, BF16, "x2")
-        C2 = x2.shape[1]
-    for t, c in ((x1, C1), (x2, C2)):
-        if t is not None and (not t.is_contiguous() or t.shape[0] != nimg * H * W):
-            raise _lib.VstError("conv3x3: inputs must be contiguous [nimg*H*W, C]")
-    _dev(w, BF16, "w")
+    fn = "conv3x3"
+    C1 = _conv_in(x1, nimg * H * W, "x1", fn)
+    C2 = 0 if x2 is None else _conv_in(x2, nimg * H * W, "x2", fn)
+    _view(w, BF16, "w", fn)
     Cout = w.shape[0]
     kreal = 9 * (C1 + C2)
     if w.shape[1] != ((kreal + 7) & ~7) and w.shape[1] != kreal:
@@ -570,24 +564,22 @@ def conv3x3(x1: torch.Tensor, nimg: int, H: int, W: int, w: torch.Tensor, bias: 
     else:
         OH, OW = H, W
     M = nimg * OH * OW
-    if out is None:
-        out = torch.empty((M, Cout), dtype=BF16, device=x1.device)
-    _out(out, (M, Cout), BF16, "out", "conv3x3")
-    if bias is not None and (bias.dtype != F32 or bias.numel() != Cout):
-        raise _lib.VstError("conv3x3: bias must be fp32 [Cout]")
+    out = _new(out, (M, Cout), x1, "out", fn)
+    if bias is not None:
+        _vec(bias, Cout, "bias", fn)
     if residual is not None:
-        _dev(residual, BF16, "residual")
-        if residual.shape != (M, Cout):
-            raise _lib.VstError(f"conv3x3: residual shape {tuple(residual.shape)} != {(M, Cout)}")
-    if row_bias is not None and (row_bias.dtype != F32 or not row_bias.is_cuda or row_bias.dim() != 2
-                                 or row_bias.stride(1) != 1 or row_bias.shape[1] != Cout):
-        raise _lib.VstError("conv3x3: row_bias must be an fp32 [nimg/div, Cout] device view with unit column stride")
+        _view(residual, BF16, "residual", fn, shape=(M, Cout))
+    ldrb = 0
+    if row_bias is not None:
+        if row_bias_div <= 0:
+            raise _lib.VstError(f"conv3x3: row_bias_div {row_bias_div}")
+        ldrb = _table(row_bias, (M - 1) // row_bias_div + 1, Cout, "row_bias", fn, align=False)
     kind = "conv3x3" if (C1 + C2) % 64 == 0 else "conv3x3_small_cin"
     with _Rec(kind, 2.0 * M * Cout * kreal, 2.0 * (nimg * H * W * (C1 + C2) + Cout * kreal + M * Cout),
               lambda: gemm_kernel_name(M, Cout, w.shape[1], 2 if kind == "conv3x3" else 3), (M, Cout, w.shape[1])):
         ws = _workspace(x1.device)
         _lib.call("vst_conv3x3_ex", _p(x1), C1, _p(x2), C2, nimg, H, W, stride, 1 if upsample else 0, _p(w), Cout,
-                  _p(bias), _p(row_bias), row_bias_div, 0 if row_bias is None else _ld(row_bias), _p(residual), 0 if residual is None else _ld(residual),
+                  _p(bias), _p(row_bias), row_bias_div, ldrb, _p(residual), 0 if residual is None else _ld(residual),
                   _p(out), _ld(out) if Cout >= 8 else Cout, GEMM_POLICY["tile"], _splits(), _p(ws),
                   _WS_BYTES, _stream())
     return out
@@ -596,18 +588,11 @@ def conv3x3(x1: torch.Tensor, nimg: int, H: int, W: int, w: torch.Tensor, bias: 
 def spatial_attention(q, k, v, nbatch, heads, Nq, Nk, kv_div=1, out=None, scale=None, lse=None):
     """q: [nbatch*Nq, >=heads*64] view; k/v: [nbatch/kv_div*Nk, >=heads*64] views.  lse: optional fp32
     [nbatch*heads*Nq] output of the log2-domain logsumexp per query (the training backward recomputes P from it)."""
-    for n, t in (("q", q), ("k", k), ("v", v)):
-        _dev(t, BF16, n)
-    if q.shape[0] != nbatch * Nq or k.shape[0] != (nbatch // kv_div) * Nk or v.shape[0] != k.shape[0]:
-        raise _lib.VstError("spatial_attention: row counts do not match batch/Nq/Nk")
-    if k.stride(0) != v.stride(0):
-        raise _lib.VstError("spatial_attention: k and v must share a row stride")
-    if out is None:
-        out = torch.empty((nbatch * Nq, heads * 64), dtype=BF16, device=q.device)
-    _out(out, (nbatch * Nq, heads * 64), BF16, "out", "spatial_attention")
-    if lse is not None and (lse.dtype != F32 or not lse.is_cuda or lse.numel() != nbatch * heads * Nq
-                            or not lse.is_contiguous()):
-        raise _lib.VstError("spatial_attention: lse must be contiguous fp32 [nbatch*heads*Nq] on device")
+    fn = "spatial_attention"
+    _qkv(fn, q, k, v, nbatch * Nq, (nbatch // kv_div) * Nk)
+    out = _new(out, (nbatch * Nq, heads * 64), q, "out", fn)
+    if lse is not None:
+        _block(lse, F32, "lse", fn, numel=nbatch * heads * Nq)
     scale = 0.125 if scale is None else scale
     with _Rec("spatial_attention", 4.0 * nbatch * heads * Nq * Nk * 64,
               2.0 * 64 * heads * (2 * nbatch * Nq + 2 * (nbatch // kv_div) * Nk), None, (nbatch * heads, Nq, Nk)):
@@ -648,20 +633,14 @@ def spatial_attention_frames(q, k, v, nclip, F, heads, N, sources, scale=None, o
     of frame_list(f, F, sources) of the same clip under one softmax.  q/k/v: [nclip*F*N, >= heads*64] views (k and v
     share a row stride); sources: up to two of "first", "prev" or a frame index.  Bad sources reach the library, which
     refuses them before any launch (VstError, status 1)."""
-    for n, t in (("q", q), ("k", k), ("v", v)):
-        _dev(t, BF16, n)
+    fn = "spatial_attention_frames"
     rows = nclip * F * N
-    if q.shape[0] != rows or k.shape[0] != rows or v.shape[0] != rows:
-        raise _lib.VstError("spatial_attention_frames: rows != nclip*F*N")
-    if k.stride(0) != v.stride(0):
-        raise _lib.VstError("spatial_attention_frames: k and v must share a row stride")
+    _qkv(fn, q, k, v, rows)
     src = [frame_source(s) for s in sources]
     if len(src) > 2:
         raise _lib.VstError(f"spatial_attention_frames: {len(src)} sources; at most two")
     src1, src2 = (src + [-1, -1])[:2]
-    if out is None:
-        out = torch.empty((rows, heads * 64), dtype=BF16, device=q.device)
-    _out(out, (rows, heads * 64), BF16, "out", "spatial_attention_frames")
+    out = _new(out, (rows, heads * 64), q, "out", fn)
     scale = 0.125 if scale is None else scale
     ok = all(s < F for s in src) and len(set(src)) == len(src)  # else the library refuses; nothing to count
     keys = sum(len(frame_list(f, F, sources)) for f in range(F)) * N if ok else 0
@@ -674,17 +653,11 @@ def spatial_attention_frames(q, k, v, nclip, F, heads, N, sources, scale=None, o
 
 def temporal_attention(q, k, v, nclip, F, HW, heads, head_dim, out=None, scale=None):
     """Frame-axis attention; rows (b*F + f)*HW + p.  q/k/v views share one row stride."""
-    for n, t in (("q", q), ("k", k), ("v", v)):
-        _dev(t, BF16, n)
-    if not (q.stride(0) == k.stride(0) == v.stride(0)):
-        raise _lib.VstError("temporal_attention: q/k/v must share a row stride")
-    if q.shape[0] != nclip * F * HW:
-        raise _lib.VstError("temporal_attention: rows != nclip*F*HW")
-    if out is None:
-        out = torch.empty((q.shape[0], heads * head_dim), dtype=BF16, device=q.device)
-    _out(out, (q.shape[0], heads * head_dim), BF16, "out", "temporal_attention")
-    scale = head_dim ** -0.5 if scale is None else scale
+    fn = "temporal_attention"
     T = nclip * F * HW
+    _qkv(fn, q, k, v, T, q_shares=True)
+    out = _new(out, (T, heads * head_dim), q, "out", fn)
+    scale = head_dim ** -0.5 if scale is None else scale
     with _Rec("temporal_attention", 4.0 * T * F * heads * head_dim, 2.0 * 4 * T * heads * head_dim):
         _lib.call("vst_temporal_attention", _p(q), _p(k), _p(v), q.stride(0), _p(out), _ld(out), nclip, F, HW, heads,
                   head_dim, float(scale), _stream())
@@ -727,34 +700,22 @@ def temporal_attention_windowed(q, k, v, pos, nclip, F, HW, heads, head_dim, con
     clips"); rows (b*F + f)*HW + p.  q/k/v views share one row stride and hold the projections WITHOUT the positional
     term; pos: fp32 [context_length, 3*heads*head_dim] = pe[:L] @ Wqkv^T (its q | k | v column blocks are added at the
     position inside each window), or None."""
-    for n, t in (("q", q), ("k", k), ("v", v)):
-        _dev(t, BF16, n)
+    fn = "temporal_attention_windowed"
     L, S, C = int(context_length), int(context_stride), heads * head_dim
-    context_windows(F, L, S)
+    nwin = len(context_windows(F, L, S))
     if weighting not in WEIGHTINGS:
         raise ValueError(f"weighting {weighting!r} not in {sorted(WEIGHTINGS)}")
     if F < L:
         raise _lib.VstError(f"temporal_attention_windowed: F = {F} < context_length {L}")
-    if not (q.stride(0) == k.stride(0) == v.stride(0)):
-        raise _lib.VstError("temporal_attention_windowed: q/k/v must share a row stride")
-    if q.shape[0] != nclip * F * HW:
-        raise _lib.VstError("temporal_attention_windowed: rows != nclip*F*HW")
+    T = nclip * F * HW
+    _qkv(fn, q, k, v, T, q_shares=True)
     pq = pk = pv = None
     ldpos = 0
     if pos is not None:
-        _dev(pos, F32, "pos")
-        if tuple(pos.shape) != (L, 3 * C):
-            raise _lib.VstError(f"temporal_attention_windowed: pos shape {tuple(pos.shape)} != {(L, 3 * C)}")
-        ldpos = pos.stride(0) if L > 1 else 3 * C
-        if pos.data_ptr() % 16 or ldpos % 4:
-            raise _lib.VstError("temporal_attention_windowed: pos must be 16-byte aligned with a row stride % 4 == 0")
+        ldpos = _table(pos, L, 3 * C, "pos", fn)
         pq, pk, pv = pos[:, :C], pos[:, C:2 * C], pos[:, 2 * C:]
-    if out is None:
-        out = torch.empty((q.shape[0], C), dtype=BF16, device=q.device)
-    _out(out, (q.shape[0], C), BF16, "out", "temporal_attention_windowed")
+    out = _new(out, (T, C), q, "out", fn)
     scale = head_dim ** -0.5 if scale is None else scale
-    T = nclip * F * HW
-    nwin = len(context_windows(F, L, S))
     with _Rec("temporal_attention_windowed", 4.0 * nclip * HW * nwin * L * L * C, 2.0 * 4 * T * C,
               lambda: "temporal_attn_windowed_kernel"):
         _lib.call("vst_temporal_attention_windowed", _p(q), _p(k), _p(v), q.stride(0), _p(pq), _p(pk), _p(pv), ldpos,
@@ -764,15 +725,13 @@ def temporal_attention_windowed(q, k, v, pos, nclip, F, HW, heads, head_dim, con
 
 
 def group_norm(x1, nsamples, rows_per_sample, groups, eps, gamma, beta, *, silu=False, x2=None, out=None):
-    _dev(x1, BF16, "x1")
-    C = x1.shape[1] + (0 if x2 is None else x2.shape[1])
-    if x2 is not None:
-        _dev(x2, BF16, "x2")
-    if x1.shape[0] != nsamples * rows_per_sample:
-        raise _lib.VstError("group_norm: rows != nsamples*rows_per_sample")
-    if out is None:
-        out = torch.empty((x1.shape[0], C), dtype=BF16, device=x1.device)
-    _out(out, (x1.shape[0], C), BF16, "out", "group_norm")
+    fn = "group_norm"
+    rows = nsamples * rows_per_sample
+    _view(x1, BF16, "x1", fn, rows=rows)
+    C = x1.shape[1] + (0 if x2 is None else _view(x2, BF16, "x2", fn, rows=rows).shape[1])
+    _vec(gamma, C, "gamma", fn)
+    _vec(beta, C, "beta", fn)
+    out = _new(out, (rows, C), x1, "out", fn)
     ws_bytes = _lib.load().vst_groupnorm_workspace_bytes(nsamples, rows_per_sample, groups, C)
     ws = torch.empty((ws_bytes + 3) // 4, dtype=F32, device=x1.device)
     with _Rec("groupnorm", 0.0, 2.0 * 3 * x1.shape[0] * C):  # two reads + one write
@@ -785,15 +744,13 @@ def group_norm(x1, nsamples, rows_per_sample, groups, eps, gamma, beta, *, silu=
 def group_norm_frame_partials(x, nframes, rows_per_frame, groups, *, out=None):
     """fp32 (sum, sumsq) chunk partials of every frame, [nframes, chunks, groups, 2] (vst_groupnorm_frame_partials):
     a frame's partials depend on that frame only, so the frame-sharded motion GroupNorm all-gathers them."""
-    _dev(x, BF16, "x")
+    fn = "group_norm_frame_partials"
+    _view(x, BF16, "x", fn, rows=nframes * rows_per_frame)
     C = x.shape[1]
-    if x.shape[0] != nframes * rows_per_frame:
-        raise _lib.VstError("group_norm_frame_partials: rows != nframes*rows_per_frame")
     nck = int(_lib.load().vst_groupnorm_frame_chunks(rows_per_frame))
     if out is None:
         out = torch.empty((nframes, nck, groups, 2), dtype=F32, device=x.device)
-    if out.dtype != F32 or not out.is_cuda or not out.is_contiguous() or out.numel() != nframes * nck * groups * 2:
-        raise _lib.VstError("group_norm_frame_partials: out must be contiguous fp32 [nframes, chunks, groups, 2]")
+    _block(out, F32, "out", fn, numel=nframes * nck * groups * 2)
     with _Rec("groupnorm", 0.0, 2.0 * x.shape[0] * C):
         _lib.call("vst_groupnorm_frame_partials", _p(x), _ld(x), C, nframes, rows_per_frame, groups, _p(out),
                   _stream())
@@ -805,18 +762,14 @@ def group_norm_apply_partials(x, nclips, frames_local, rows_per_frame, groups, e
     """GroupNorm of this rank's rows (clips x frames_local frames) with statistics over all nranks * frames_local
     frames of each clip, merged in one fixed order from `part` = [nranks, nclips, frames_local, chunks, groups, 2]
     (the all-gather of every rank's group_norm_frame_partials; nranks = 1: the whole clip is here)."""
-    _dev(x, BF16, "x")
+    fn = "group_norm_apply_partials"
+    _view(x, BF16, "x", fn, rows=nclips * frames_local * rows_per_frame)
     C = x.shape[1]
     nck = int(_lib.load().vst_groupnorm_frame_chunks(rows_per_frame))
-    if x.shape[0] != nclips * frames_local * rows_per_frame:
-        raise _lib.VstError("group_norm_apply_partials: rows != nclips*frames_local*rows_per_frame")
-    if part.dtype != F32 or not part.is_cuda or not part.is_contiguous() or \
-            part.numel() != nranks * nclips * frames_local * nck * groups * 2:
-        raise _lib.VstError("group_norm_apply_partials: part must be contiguous fp32 "
-                            "[nranks, nclips, frames_local, chunks, groups, 2] on device")
-    if out is None:
-        out = torch.empty((x.shape[0], C), dtype=BF16, device=x.device)
-    _out(out, (x.shape[0], C), BF16, "out", "group_norm_apply_partials")
+    _block(part, F32, "part", fn, numel=nranks * nclips * frames_local * nck * groups * 2)
+    _vec(gamma, C, "gamma", fn)
+    _vec(beta, C, "beta", fn)
+    out = _new(out, (x.shape[0], C), x, "out", fn)
     ss = torch.empty(2 * nclips * C, dtype=F32, device=x.device)
     with _Rec("groupnorm", 0.0, 2.0 * 2 * x.shape[0] * C):
         _lib.call("vst_groupnorm_apply_partials", _p(x), _ld(x), C, nclips, frames_local, rows_per_frame, groups,
@@ -827,12 +780,13 @@ def group_norm_apply_partials(x, nclips, frames_local, rows_per_frame, groups, e
 
 def permute_rows(src, dims, perm, out=None):
     """src rows indexed (i0,i1,i2,i3) over `dims`; returns rows in order (i_perm[0], .., i_perm[3])."""
-    _dev(src, BF16, "src")
-    if not src.is_contiguous() or src.shape[0] != dims[0] * dims[1] * dims[2] * dims[3]:
+    fn = "permute_rows"
+    _block(src, BF16, "src", fn)
+    if src.dim() != 2 or src.shape[0] != dims[0] * dims[1] * dims[2] * dims[3]:
         raise _lib.VstError("permute_rows: src must be contiguous with prod(dims) rows")
     if out is None:
         out = torch.empty_like(src)
-    _out_flat(out, src.shape, BF16, "out", "permute_rows")
+    _block(out, BF16, "out", fn, src.shape)
     with _Rec("permute", 0.0, 2.0 * 2 * src.numel()):
         _lib.call("vst_permute_rows", _p(src), _p(out), src.shape[1], *dims, *perm, _stream())
     return out
@@ -840,45 +794,42 @@ def permute_rows(src, dims, perm, out=None):
 
 def add_row_table(x, table, *, div=1, mod=1, out=None):
     """out[row] = x[row] + table[(row // div) % mod]; table fp32 [>= mod, C] on device."""
-    _dev(x, BF16, "x")
+    fn = "add_row_table"
+    _view(x, BF16, "x", fn)
     rows, C = x.shape
-    if table.dtype != F32 or not table.is_cuda or table.dim() != 2 or table.shape[1] != C or table.shape[0] < mod:
-        raise _lib.VstError("add_row_table: table must be fp32 [>= mod, C] on device")
-    if out is None:
-        out = torch.empty((rows, C), dtype=BF16, device=x.device)
-    _out(out, (rows, C), BF16, "out", "add_row_table")
+    table = _on_device(table, F32, "table", fn).contiguous()
+    _table(table, mod, C, "table", fn, align=False)
+    out = _new(out, (rows, C), x, "out", fn)
     with _Rec("add_row_table", 0.0, 2.0 * 2 * rows * C):
-        _lib.call("vst_add_row_table", _p(x), _ld(x), C, rows, _p(table.contiguous()), div, mod, _p(out), _ld(out),
-                  _stream())
+        _lib.call("vst_add_row_table", _p(x), _ld(x), C, rows, _p(table), div, mod, _p(out), _ld(out), _stream())
     return out
 
 
 def unpack_tokens(src, out):
     """bf16 token rows ((b*F + f)*HW + p, C) -> fp32 out (B, C, F, H, W) (contiguous)."""
-    _dev(src, BF16, "src")
-    if out.dtype != F32 or not out.is_cuda or not out.is_contiguous() or out.dim() != 5:
+    fn = "unpack_tokens"
+    _block(out, F32, "out", fn)
+    if out.dim() != 5:
         raise _lib.VstError("unpack_tokens: out must be a contiguous fp32 (B, C, F, H, W) device tensor")
     B, C, F, H, W = out.shape
-    if not src.is_contiguous() or src.shape != (B * F * H * W, C):
-        raise _lib.VstError(f"unpack_tokens: src {tuple(src.shape)} vs out {tuple(out.shape)}")
+    _block(src, BF16, "src", fn, (B * F * H * W, C))
     _lib.call("vst_unpack_tokens", _p(src), B, C, F, H * W, _p(out), _stream())
     return out
 
 
 def layer_norm_lora(x, gamma, beta, eps, A, *, r_alg=None, out=None, u=None):
     """(LN(x), LN(x) @ A^T) in one pass; A: bf16 [R, C] (R % 16 == 0, <= 64) — LayerNorm + UnZipLoRA down."""
-    _dev(x, BF16, "x")
-    _dev(A, BF16, "A")
+    fn = "layer_norm_lora"
+    _view(x, BF16, "x", fn)
+    _view(A, BF16, "A", fn)
     rows, C = x.shape
     R = A.shape[0]
     if A.shape[1] != C or R % 16 or R > 64 or C % 32 or C > 1280 or not A.is_contiguous():
         raise _lib.VstError(f"layer_norm_lora: x {tuple(x.shape)} A {tuple(A.shape)}")
-    if out is None:
-        out = torch.empty((rows, C), dtype=BF16, device=x.device)
-    _out(out, (rows, C), BF16, "out", "layer_norm_lora")
-    if u is None:
-        u = torch.empty((rows, R), dtype=BF16, device=x.device)
-    _out(u, (rows, R), BF16, "u", "layer_norm_lora")
+    _vec(gamma, C, "gamma", fn)
+    _vec(beta, C, "beta", fn)
+    out = _new(out, (rows, C), x, "out", fn)
+    u = _new(u, (rows, R), x, "u", fn)
     with _Rec("layernorm_lora", 2.0 * rows * C * (r_alg or R), 2.0 * (2 * rows * C + rows * R)):
         _lib.call("vst_layernorm_lora", _p(x), _ld(x), C, rows, _p(gamma), _p(beta), float(eps), _p(A), R, _p(out),
                   _ld(out), _p(u), _ld(u), _stream())
@@ -886,55 +837,115 @@ def layer_norm_lora(x, gamma, beta, eps, A, *, r_alg=None, out=None, u=None):
 
 
 def layer_norm(x, gamma, beta, eps=1e-5, *, pe=None, pe_div=1, pe_mod=1, out=None):
-    _dev(x, BF16, "x")
+    fn = "layer_norm"
+    _view(x, BF16, "x", fn)
     rows, C = x.shape
-    if out is None:
-        out = torch.empty((rows, C), dtype=BF16, device=x.device)
-    _out(out, (rows, C), BF16, "out", "layer_norm")
+    _vec(gamma, C, "gamma", fn)
+    _vec(beta, C, "beta", fn)
+    if pe is not None and (pe_mod <= 0 or _table(pe, pe_mod, C, "pe", fn) != C):
+        _fail(fn, "pe", f"must be contiguous rows of C = {C} for pe_mod = {pe_mod} > 0")
+    out = _new(out, (rows, C), x, "out", fn)
     with _Rec("layernorm", 0.0, 2.0 * 2 * rows * C):
         _lib.call("vst_layernorm", _p(x), _ld(x), C, rows, _p(gamma), _p(beta), float(eps), _p(pe), pe_div, pe_mod,
                   _p(out), _ld(out), _stream())
     return out
 
 
+def _step_counter(step_idx, fn):
+    return _block(step_idx, I32, "step_idx", fn, (1,))
+
+
 def timestep_embedding(t, n, dim, out, *, col0=0, per_row=1, step_idx=None, flip=True, shift=0.0):
-    """diffusers Timesteps(dim, flip_sin_to_cos, shift): value i -> out[i // per_row, col0 + (i % per_row)*dim]."""
-    if t.dtype != F32 or not t.is_cuda:
-        raise _lib.VstError("timestep_embedding: t must be fp32 on device")
+    """diffusers Timesteps(dim, flip_sin_to_cos, shift): value i -> out[i // per_row, col0 + (i % per_row)*dim].
+    With step_idx (the device step counter) every value is t[step_idx], t the schedule's timestep table."""
+    fn = "timestep_embedding"
+    _block(t, F32, "t", fn)
+    if step_idx is not None:
+        _step_counter(step_idx, fn)
+    if n <= 0 or per_row <= 0 or col0 < 0 or t.numel() < (1 if step_idx is not None else n):
+        raise _lib.VstError(f"timestep_embedding: t {tuple(t.shape)} for n={n} values, per_row={per_row} col0={col0}")
+    _view(out, BF16, "out", fn, min_cols=col0 + per_row * dim)
+    if out.shape[0] * per_row < n:
+        _fail(fn, "out", f"has {out.shape[0]} rows for n={n} values, {per_row} per row")
     _lib.call("vst_timestep_embedding", _p(t), _p(step_idx), n, dim, 1 if flip else 0, float(shift), _p(out),
               _ld(out), col0, per_row, _stream())
     return out
 
 
-def _elementwise(fn, out, *ins):
-    """silu / add address every operand as one flat bf16 block of the first input's size."""
+def _elementwise(entry, out, *ins):
+    """silu / add / quick_gelu address every operand as one flat bf16 block of the first input's size."""
+    fn, n = entry[4:], ins[0].numel() if isinstance(ins[0], torch.Tensor) else None
     for name, t in (("out", out),) + tuple((f"input {i}", t) for i, t in enumerate(ins)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != BF16 or not t.is_contiguous() \
-                or t.numel() != ins[0].numel():
-            raise _lib.VstError(f"{fn}: {name} must be a contiguous bf16 device tensor of {ins[0].numel()} elements")
-
-
-def silu(x, out=None):
-    out = torch.empty_like(x) if out is None else out
-    _elementwise("silu", out, x)
-    _lib.call("vst_silu", _p(x), _p(out), x.numel(), _stream())
+        _block(t, BF16, name, fn, numel=n)
+    _lib.call(entry, *map(_p, ins), _p(out), n, _stream())
     return out
 
 
+def silu(x, out=None):
+    return _elementwise("vst_silu", torch.empty_like(x) if out is None else out, x)
+
+
 def add(a, b, out=None):
-    out = torch.empty_like(a) if out is None else out
-    _elementwise("add", out, a, b)
-    _lib.call("vst_add", _p(a), _p(b), _p(out), a.numel(), _stream())
+    return _elementwise("vst_add", torch.empty_like(a) if out is None else out, a, b)
+
+
+def quick_gelu(x, out=None):
+    """x * sigmoid(1.702 x) (the CLIP ViT-L/14 MLP activation); out may be x."""
+    return _elementwise("vst_quick_gelu", torch.empty_like(x) if out is None else out, x)
+
+
+# ---- SDXL text encoders (text_encoder.py) ----
+def embed_tokens(ids, L, tok, pos):
+    """fp32 [rows, C]: tok[ids[r]] + pos[r % L] (CLIPTextEmbeddings).  ids: int32 [rows] on the device, in range (the
+    caller checks them against the vocabulary on the host); tok [vocab, C] and pos [>= L, C]: contiguous bf16."""
+    fn = "embed_tokens"
+    _block(ids, I32, "ids", fn)
+    _block(tok, BF16, "tok", fn)
+    if ids.dim() != 1 or tok.dim() != 2 or L <= 0 or ids.numel() == 0:
+        raise _lib.VstError(f"embed_tokens: ids {tuple(ids.shape)} (1-D), tok {tuple(tok.shape)} (2-D), L={L}")
+    C = tok.shape[1]
+    _block(pos, BF16, "pos", fn)
+    if pos.dim() != 2 or pos.shape[1] != C or pos.shape[0] < L:
+        _fail(fn, "pos", f"shape {tuple(pos.shape)}: expected >= {L} rows of C = {C}")
+    h = torch.empty((ids.numel(), C), dtype=F32, device=ids.device)
+    _lib.call("vst_embed_tokens", _p(ids), ids.numel(), L, _p(tok), _p(pos), C, _p(h), C, _stream())
+    return h
+
+
+def residual_layer_norm(h, y, gamma, beta, eps):
+    """(h + y fp32, LayerNorm of it bf16) (vst_residual_layernorm): h the fp32 residual stream [rows, C], y bf16
+    [rows, C] or None."""
+    fn = "residual_layer_norm"
+    _view(h, F32, "h", fn)
+    rows, C = h.shape
+    if y is not None:
+        _view(y, BF16, "y", fn, shape=(rows, C))
+    _vec(gamma, C, "gamma", fn)
+    _vec(beta, C, "beta", fn)
+    ho = torch.empty((rows, C), dtype=F32, device=h.device)
+    n = torch.empty((rows, C), dtype=BF16, device=h.device)
+    _lib.call("vst_residual_layernorm", _p(h), _ld(h), _p(y), 0 if y is None else _ld(y), rows, C, _p(gamma),
+              _p(beta), float(eps), _p(ho), C, _p(n), C, _stream())
+    return ho, n
+
+
+def causal_attention(q, k, v, nbatch, heads, N, head_dim=64, out=None, scale=None):
+    """CLIPAttention: softmax(q k^T * scale + causal mask) v over the N tokens of each of nbatch sequences; q/k/v:
+    [nbatch*N, >= heads*head_dim] views (k and v share a row stride)."""
+    fn = "causal_attention"
+    _qkv(fn, q, k, v, nbatch * N)
+    out = _new(out, (nbatch * N, heads * head_dim), q, "out", fn)
+    scale = head_dim ** -0.5 if scale is None else scale
+    _lib.call("vst_causal_attention", _p(q), _ld(q), _p(k), _p(v), k.stride(0), _p(out), _ld(out), nbatch, heads, N,
+              head_dim, float(scale), _stream())
     return out
 
 
 def transpose(x, out=None):
     """bf16 [rows, cols] (row-major view) -> [cols, rows]."""
-    _dev(x, BF16, "x")
+    _view(x, BF16, "x", "transpose")
     rows, cols = x.shape
-    if out is None:
-        out = torch.empty((cols, rows), dtype=BF16, device=x.device)
-    _out(out, (cols, rows), BF16, "out", "transpose")
+    out = _new(out, (cols, rows), x, "out", "transpose")
     with _Rec("transpose", 0.0, 2.0 * 2 * rows * cols):
         _lib.call("vst_transpose", _p(x), _ld(x), rows, cols, _p(out), _ld(out), _stream())
     return out
@@ -943,9 +954,11 @@ def transpose(x, out=None):
 def layer_norm_bwd(x, g, gamma, eps=1e-5, need_affine=True):
     """LayerNorm backward: (dx bf16 [rows, C], dgamma fp32 [C], dbeta fp32 [C]); need_affine=False (frozen
     affine) computes dx only and returns (dx, None, None)."""
-    _dev(x, BF16, "x")
-    _dev(g, BF16, "g")
+    fn = "layer_norm_bwd"
+    _view(x, BF16, "x", fn)
     rows, C = x.shape
+    _view(g, BF16, "g", fn, shape=(rows, C))
+    _vec(gamma, C, "gamma", fn)
     dx = torch.empty((rows, C), dtype=BF16, device=x.device)
     dgamma = dbeta = ws = None
     if need_affine:
@@ -961,11 +974,12 @@ def layer_norm_bwd(x, g, gamma, eps=1e-5, need_affine=True):
 
 def group_norm_bwd(x, g, nsamples, rows_per_sample, groups, eps, gamma, beta, *, silu=False):
     """GroupNorm (+SiLU) backward: (dx bf16, dgamma fp32 [C], dbeta fp32 [C])."""
-    _dev(x, BF16, "x")
-    _dev(g, BF16, "g")
+    fn = "group_norm_bwd"
+    _view(x, BF16, "x", fn, rows=nsamples * rows_per_sample)
     rows, C = x.shape
-    if rows != nsamples * rows_per_sample or g.shape != x.shape:
-        raise _lib.VstError("group_norm_bwd: shapes")
+    _view(g, BF16, "g", fn, shape=(rows, C))
+    _vec(gamma, C, "gamma", fn)
+    _vec(beta, C, "beta", fn)
     dx = torch.empty((rows, C), dtype=BF16, device=x.device)
     dgamma = torch.empty(C, dtype=F32, device=x.device)
     dbeta = torch.empty(C, dtype=F32, device=x.device)
@@ -981,12 +995,11 @@ def colsum(x, out=None):
     """fp32 [N] column sums of a bf16 [M, N] row-major view (bias gradients), deterministic (vst_colsum).  The kernel
     reads 16-B chunks of 8 columns: a view whose width, row stride or base is not 8-column aligned is first copied
     into a zero-padded [M, ceil8(N)] buffer (the padding columns sum to zero and are dropped)."""
-    _dev(x, BF16, "x")
+    _view(x, BF16, "x", "colsum")
     M, N = x.shape
     if out is None:
         out = torch.empty(N, dtype=F32, device=x.device)
-    if not out.is_cuda or out.dtype != F32 or out.dim() != 1 or out.numel() != N or not out.is_contiguous():
-        raise _lib.VstError(f"colsum: out must be contiguous fp32 [{N}] on device")
+    _block(out, F32, "out", "colsum", (N,))
     if N % 8 or _ld(x) % 8 or x.data_ptr() % 16:
         n8 = (N + 7) // 8 * 8
         xp = torch.zeros((M, n8), dtype=BF16, device=x.device)
@@ -1002,14 +1015,10 @@ def colsum(x, out=None):
 
 def geglu_bwd(p, g, out=None):
     """dp (32-interleaved like p) from p = the GEGLU projection output and g = dL/d(h * gelu(gate))."""
-    _dev(p, BF16, "p")
-    _dev(g, BF16, "g")
+    _view(g, BF16, "g", "geglu_bwd")
     M, Nh = g.shape
-    if p.shape != (M, 2 * Nh):
-        raise _lib.VstError(f"geglu_bwd: p {tuple(p.shape)} vs g {tuple(g.shape)}")
-    if out is None:
-        out = torch.empty((M, 2 * Nh), dtype=BF16, device=p.device)
-    _out(out, (M, 2 * Nh), BF16, "out", "geglu_bwd")
+    _view(p, BF16, "p", "geglu_bwd", shape=(M, 2 * Nh))
+    out = _new(out, (M, 2 * Nh), p, "out", "geglu_bwd")
     with _Rec("geglu_bwd", 0.0, 2.0 * 5 * M * Nh):
         _lib.call("vst_geglu_bwd", _p(p), _ld(p), _p(g), _ld(g), M, Nh, _p(out), _ld(out), _stream())
     return out
@@ -1019,46 +1028,34 @@ def spatial_attention_bwd(q, k, v, o, dout, lse, nbatch, heads, Nq, Nk, kv_div=1
                           need_dkv=True):
     """(dq [nbatch*Nq, heads*64], dk, dv [nbatch/kv_div*Nk, heads*64] as column views of one [.., 2*heads*64], or
     None, None when need_dkv is False: frozen K/V skip the dK/dV kernel).  lse: the forward's logsumexp output."""
-    for n, t in (("q", q), ("k", k), ("v", v), ("o", o), ("dout", dout)):
-        _dev(t, BF16, n)
-    if k.stride(0) != v.stride(0):
-        raise _lib.VstError("spatial_attention_bwd: k and v must share a row stride")
-    if lse.dtype != F32 or not lse.is_cuda or lse.numel() != nbatch * heads * Nq:
-        raise _lib.VstError("spatial_attention_bwd: lse must be the forward's fp32 [nbatch*heads*Nq] logsumexp")
+    fn = "spatial_attention_bwd"
     C = heads * 64
     nkv = nbatch // kv_div
-    if dq is None:
-        dq = torch.empty((nbatch * Nq, C), dtype=BF16, device=q.device)
-    if need_dkv and dkv is None:
-        dkv = torch.empty((nkv * Nk, 2 * C), dtype=BF16, device=q.device)
-    _out(dq, (nbatch * Nq, C), BF16, "dq", "spatial_attention_bwd")
+    _qkv(fn, q, k, v, nbatch * Nq, nkv * Nk, o=o, dout=dout)
+    _block(lse, F32, "lse", fn, numel=nbatch * heads * Nq)
+    dq = _new(dq, (nbatch * Nq, C), q, "dq", fn)
+    dk = dv = None
     if need_dkv:
-        _out(dkv, (nkv * Nk, 2 * C), BF16, "dkv", "spatial_attention_bwd")
+        dkv = _new(dkv, (nkv * Nk, 2 * C), q, "dkv", fn)
+        dk, dv = dkv[:, :C], dkv[:, C:]
     ws = torch.empty((_lib.load().vst_spatial_attention_bwd_workspace_bytes(nbatch, heads, Nq, Nk) + 3) // 4,
                      dtype=F32, device=q.device)
     scale = 0.125 if scale is None else scale
     # MFMA work: dQ pass 3 products (S, dP, dQ), dK/dV pass 4 (S, dP, dV, dK), 2*64 flop per (q, key) each
     with _Rec("spatial_attention_bwd", (6.0 + (8.0 if need_dkv else 0.0)) * nbatch * heads * Nq * Nk * 64, 0.0):
         _lib.call("vst_spatial_attention_bwd", _p(q), _ld(q), _p(k), _p(v), k.stride(0), _p(o), _ld(o), _p(dout),
-                  _ld(dout), _p(lse), _p(dq), _ld(dq), _p(dkv[:, :C]) if need_dkv else None,
-                  _p(dkv[:, C:]) if need_dkv else None, dkv.stride(0) if need_dkv else 0, nbatch, heads, Nq, Nk,
-                  kv_div, 64, float(scale), _p(ws), _stream())
-    if not need_dkv:
-        return dq, None, None
-    return dq, dkv[:, :C], dkv[:, C:]
+                  _ld(dout), _p(lse), _p(dq), _ld(dq), _p(dk), _p(dv), dkv.stride(0) if need_dkv else 0, nbatch,
+                  heads, Nq, Nk, kv_div, 64, float(scale), _p(ws), _stream())
+    return dq, dk, dv
 
 
 def temporal_attention_bwd(q, k, v, dout, nclip, F, HW, heads, head_dim, scale=None, out=None):
     """(dq, dk, dv) of temporal_attention as column views of one [tokens, 3C] bf16 buffer."""
-    for n, t in (("q", q), ("k", k), ("v", v), ("dout", dout)):
-        _dev(t, BF16, n)
-    if not (q.stride(0) == k.stride(0) == v.stride(0)):
-        raise _lib.VstError("temporal_attention_bwd: q/k/v must share a row stride")
+    fn = "temporal_attention_bwd"
     C = heads * head_dim
     rows = nclip * F * HW
-    if out is None:
-        out = torch.empty((rows, 3 * C), dtype=BF16, device=q.device)
-    _out(out, (rows, 3 * C), BF16, "out", "temporal_attention_bwd")
+    _qkv(fn, q, k, v, rows, q_shares=True, dout=dout)
+    out = _new(out, (rows, 3 * C), q, "out", fn)
     scale = head_dim ** -0.5 if scale is None else scale
     with _Rec("temporal_attention_bwd", 0.0, 2.0 * 7 * rows * C):
         _lib.call("vst_temporal_attention_bwd", _p(q), _p(k), _p(v), q.stride(0), _p(dout), _ld(dout), _p(out[:, :C]),
@@ -1067,21 +1064,18 @@ def temporal_attention_bwd(q, k, v, dout, nclip, F, HW, heads, head_dim, scale=N
     return out[:, :C], out[:, C:2 * C], out[:, 2 * C:]
 
 
-def _sampler_in(fn, x, rows, what):
+def _sampler_in(fn, x, rows):
     """The sampler dgrad kernels address x as one contiguous [rows, C] block of 16-byte chunks (no row stride in their
-    ABI): a shorter, strided or misaligned x would be read past its end."""
-    if not x.is_contiguous() or x.shape[0] != rows or rows <= 0:
-        raise _lib.VstError(f"{fn}: x must be contiguous [{what} = {rows}, C], got shape {tuple(x.shape)} stride "
-                            f"{x.stride()}")
-    if x.shape[1] % 8 or x.data_ptr() % 16:
-        raise _lib.VstError(f"{fn}: C = {x.shape[1]} must be a multiple of 8 and x 16-byte aligned")
+    ABI): a shorter, strided or misaligned x would be read past its end.  Returns C."""
+    _block(x, BF16, "x", fn)
+    if x.dim() != 2 or x.shape[0] != rows or rows <= 0 or x.shape[1] % 8 or x.data_ptr() % 16:
+        _fail(fn, "x", f"must be a 16-byte aligned [{rows}, C % 8 == 0] block, got shape {tuple(x.shape)}")
+    return x.shape[1]
 
 
 def zero_insert(x, nimg, h, w):
     """[nimg*h*w, C] -> [nimg*2h*2w, C] with x on the even (2i, 2j) pixels, zeros elsewhere."""
-    _dev(x, BF16, "x")
-    C = x.shape[1]
-    _sampler_in("zero_insert", x, nimg * h * w, "nimg*h*w")
+    C = _sampler_in("zero_insert", x, nimg * h * w)
     out = torch.zeros((nimg * 4 * h * w, C), dtype=BF16, device=x.device)
     _lib.call("vst_zero_insert", _p(x), nimg, h, w, C, _p(out), _stream())
     return out
@@ -1089,25 +1083,32 @@ def zero_insert(x, nimg, h, w):
 
 def sumpool2x2(x, nimg, h, w):
     """[nimg*2h*2w, C] -> [nimg*h*w, C], 2x2 block sums (h, w: output size)."""
-    _dev(x, BF16, "x")
-    C = x.shape[1]
-    _sampler_in("sumpool2x2", x, nimg * 4 * h * w, "nimg*2h*2w")
+    C = _sampler_in("sumpool2x2", x, nimg * 4 * h * w)
     out = torch.empty((nimg * h * w, C), dtype=BF16, device=x.device)
     _lib.call("vst_sumpool2x2", _p(x), nimg, h, w, C, _p(out), _stream())
     return out
 
 
 def copy2d(x, out):
-    _dev(x, BF16, "x")
-    _out(out, x.shape, BF16, "out", "copy2d")
+    _view(x, BF16, "x", "copy2d")
+    _view(out, BF16, "out", "copy2d", shape=x.shape)
     _lib.call("vst_copy2d", _p(x), _ld(x), _p(out), _ld(out), x.shape[0], x.shape[1], _stream())
     return out
 
 
 def pack_latents(lat, out, *, sigmas=None, step_idx=None, fixed_scale=1.0, ncopy=1):
+    """fp32 latents (B, C, F, H, W) -> bf16 token rows out [ncopy*B*F*H*W, C] (each copy the same rows), scaled by
+    fixed_scale, or with sigmas by 1 / sqrt(sigmas[step_idx]^2 + 1) read on the device."""
+    fn = "pack_latents"
+    _block(lat, F32, "lat", fn)
+    if lat.dim() != 5 or lat.numel() == 0 or ncopy <= 0:
+        raise _lib.VstError(f"pack_latents: latents must be (B,C,F,H,W), got {tuple(lat.shape)}; ncopy {ncopy}")
     B, Cl, F, H, W = lat.shape
-    if lat.dtype != F32 or not lat.is_contiguous():
-        raise _lib.VstError("pack_latents: latents must be contiguous fp32 (B,C,F,H,W)")
+    if sigmas is not None:
+        _schedule(sigmas, step_idx, fn)
+    elif step_idx is not None:
+        _step_counter(step_idx, fn)
+    _block(out, BF16, "out", fn, (ncopy * B * F * H * W, Cl))
     _lib.call("vst_pack_latents", _p(lat), B, Cl, F, H * W, _p(sigmas), _p(step_idx), float(fixed_scale), ncopy,
               _p(out), _stream())
     return out
@@ -1123,7 +1124,7 @@ def euler_cfg_step(noise, lat, sigmas, step_idx, *, guidance=7.5, ncopy=2):
 
 def step_advance(step_idx, num_steps):
     """step_idx <- (step_idx + 1) mod num_steps on the device (a schedule of num_steps steps)."""
-    _lib.call("vst_step_advance", _p(step_idx), int(num_steps), _stream())
+    _lib.call("vst_step_advance", _p(_step_counter(step_idx, "step_advance")), int(num_steps), _stream())
 
 
 # ---- FreeU in the up path (freeu.FreeU, DESIGN.md §17) ----
@@ -1132,23 +1133,14 @@ def freeu(x, skip, nimg, H, W, table, stage, *, x_out=None, skip_out=None):
     (x_out, skip_out) with x_out[:, :Cx/2] = bf16(x * b), the rest x's bits, and skip_out the skip with the four lowest
     frequency bins of every (image, channel) map scaled by s; (s, b) = table[stage], fp32 [2, 2] on the device (read
     there: new values replay a captured step).  x_out may be x (in place); skip_out must not overlap skip.  The
-    filtered skip is a new tensor to the GroupNorm that follows: no column statistics are registered for it, so
-    group_norm_stats computes them."""
-    _dev(x, BF16, "x")
-    _dev(skip, BF16, "skip")
+    GroupNorm that follows reads the filtered skip like any other tensor."""
     rows = nimg * H * W
-    if x.shape[0] != rows or skip.shape[0] != rows:
-        raise _lib.VstError(f"freeu: x {tuple(x.shape)} / skip {tuple(skip.shape)} rows, expected nimg*H*W = {rows}")
-    if not isinstance(table, torch.Tensor) or not table.is_cuda or table.dtype != F32 or tuple(table.shape) != (2, 2) \
-            or not table.is_contiguous():
-        raise _lib.VstError("freeu: table must be a contiguous fp32 [2, 2] device tensor ((s, b) per stage)")
+    _view(x, BF16, "x", "freeu", rows=rows)
+    _view(skip, BF16, "skip", "freeu", rows=rows)
+    _block(table, F32, "table", "freeu", (2, 2))
     Cx, Cs = x.shape[1], skip.shape[1]
-    if x_out is None:
-        x_out = torch.empty((rows, Cx), dtype=BF16, device=x.device)
-    if skip_out is None:
-        skip_out = torch.empty((rows, Cs), dtype=BF16, device=x.device)
-    _out(x_out, (rows, Cx), BF16, "x_out", "freeu")
-    _out(skip_out, (rows, Cs), BF16, "skip_out", "freeu")
+    x_out = _new(x_out, (rows, Cx), x, "x_out", "freeu")
+    skip_out = _new(skip_out, (rows, Cs), x, "skip_out", "freeu")
     inplace = x_out.data_ptr() == x.data_ptr()
     nbytes = 4.0 * rows * Cs + 2.0 * rows * (Cx if inplace else 2 * Cx)
     with _Rec("freeu", 28.0 * rows * Cs, nbytes, lambda: "freeu_kernel", (rows, Cs, Cx)):
@@ -1158,21 +1150,9 @@ def freeu(x, skip, nimg, H, W, table, stage, *, x_out=None, skip_out=None):
 
 
 # ---- video-to-video: start latents from a source clip, the masked Euler step (pipeline.set_source) ----
-def _flat(t, dtype, shape, name, fn):
-    """Validate a tensor a kernel addresses as one contiguous block: on the device, `dtype`, contiguous, `shape`
-    (None: any)."""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise _lib.VstError(f"{fn}: {name} must be a device tensor; the HIP path has no CPU fallback")
-    if t.dtype != dtype or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
-        want = "" if shape is None else f" {tuple(shape)}"
-        raise _lib.VstError(f"{fn}: {name} must be contiguous {dtype}{want}, got {t.dtype} {tuple(t.shape)} stride "
-                            f"{t.stride()}")
-    return t
-
-
 def _schedule(sigmas, step_idx, fn):
-    _flat(sigmas, F32, None, "sigmas", fn)
-    _flat(step_idx, torch.int32, (1,), "step_idx", fn)
+    _block(sigmas, F32, "sigmas", fn)
+    _step_counter(step_idx, fn)
     if sigmas.dim() != 1 or sigmas.numel() < 2:
         raise _lib.VstError(f"{fn}: sigmas must be a 1-D table of num_steps + 1 entries, got {tuple(sigmas.shape)}")
 
@@ -1180,13 +1160,13 @@ def _schedule(sigmas, step_idx, fn):
 def _step_operands(noise, lat, sigmas, step_idx, ncopy, fn):
     """What every denoise step takes: lat (B, Cl, F, H, W) fp32, ncopy 1 or 2, noise rows (ncopy * B * F * H * W, Cl)
     bf16, the sigma table and the step counter.  Returns lat's dimensions."""
-    _flat(lat, F32, None, "lat", fn)
+    _block(lat, F32, "lat", fn)
     if lat.dim() != 5 or lat.numel() == 0:
         raise _lib.VstError(f"{fn}: lat must be (B, Cl, F, H, W), got {tuple(lat.shape)}")
     B, Cl, F, H, W = lat.shape
     if ncopy not in (1, 2):
         raise _lib.VstError(f"{fn}: ncopy {ncopy} (1 or 2)")
-    _flat(noise, BF16, (ncopy * B * F * H * W, Cl), "noise", fn)
+    _block(noise, BF16, "noise", fn, (ncopy * B * F * H * W, Cl))
     _schedule(sigmas, step_idx, fn)
     return B, Cl, F, H, W
 
@@ -1194,9 +1174,9 @@ def _step_operands(noise, lat, sigmas, step_idx, ncopy, fn):
 def _keep_mask(lat, z0, eps, mask, fn):
     """The keep-mask triple of a step on lat: z0 and eps of lat's shape, mask (1 or B, F, H, W).  Returns mask_clips."""
     B, _, F, H, W = lat.shape
-    _flat(z0, F32, lat.shape, "z0", fn)
-    _flat(eps, F32, lat.shape, "eps", fn)
-    _flat(mask, F32, None, "mask", fn)
+    _block(z0, F32, "z0", fn, lat.shape)
+    _block(eps, F32, "eps", fn, lat.shape)
+    _block(mask, F32, "mask", fn)
     if mask.dim() != 4 or mask.shape[0] not in (1, B) or tuple(mask.shape[1:]) != (F, H, W):
         raise _lib.VstError(f"{fn}: mask {tuple(mask.shape)} vs (1 or {B}, {F}, {H}, {W})")
     return mask.shape[0]
@@ -1205,14 +1185,14 @@ def _keep_mask(lat, z0, eps, mask, fn):
 def noise_latents(z0, eps, sigmas, step_idx, out=None):
     """fp32 z0 + sigmas[step_idx] * eps (the start latents of a source-clip run; sigma is read on the device)."""
     fn = "noise_latents"
-    _flat(z0, F32, None, "z0", fn)
-    _flat(eps, F32, z0.shape, "eps", fn)
+    _block(z0, F32, "z0", fn)
+    _block(eps, F32, "eps", fn, z0.shape)
     _schedule(sigmas, step_idx, fn)
     if z0.numel() == 0:
         raise _lib.VstError(f"{fn}: empty latents")
     if out is None:
         out = torch.empty_like(z0)
-    _flat(out, F32, z0.shape, "out", fn)
+    _block(out, F32, "out", fn, z0.shape)
     _lib.call("vst_noise_latents", _p(z0), _p(eps), _p(sigmas), _p(step_idx), _p(out), z0.numel(), _stream())
     return out
 
@@ -1228,27 +1208,34 @@ def euler_cfg_step_masked(noise, lat, sigmas, step_idx, z0, eps, mask, *, guidan
 
 
 # ---- few-step sampling: the table-driven sampler step and guidance rescale (pipeline._step) ----
+def _sampler_operands(fn, noise, lat, hist, sigmas, coef, ncoef, step_idx, ncopy, factor, z0, eps, mask):
+    """What sampler_step and sampler_step_noise share: the step operands, hist (never lat itself), the coefficient
+    table [num_steps, ncoef], the optional rescale factor [B] and keep-mask triple.  Returns (B, Cl, F, H*W,
+    mask_clips)."""
+    B, Cl, F, H, W = _step_operands(noise, lat, sigmas, step_idx, ncopy, fn)
+    _block(hist, F32, "hist", fn, lat.shape)
+    if hist.data_ptr() == lat.data_ptr():
+        raise _lib.VstError(f"{fn}: hist must not be lat")
+    _block(coef, F32, "coef", fn, (sigmas.numel() - 1, ncoef))
+    if factor is not None:
+        _block(factor, F32, "factor", fn, (B,))
+        if ncopy != 2:
+            raise _lib.VstError(f"{fn}: a rescale factor needs both CFG branches (ncopy 2)")
+    given = [t is not None for t in (z0, eps, mask)]
+    if any(given) and not all(given):
+        raise _lib.VstError(f"{fn}: z0, eps and mask go together")
+    return B, Cl, F, H * W, _keep_mask(lat, z0, eps, mask, fn) if mask is not None else 0
+
+
 def sampler_step(noise, lat, hist, sigmas, coef, step_idx, *, guidance=7.5, ncopy=2, factor=None, z0=None, eps=None,
                  mask=None):
     """One fused sampler step on lat and hist (B, Cl, F, H, W) fp32, in place: e = u + guidance * (c - u) (times
     factor[b] when given), D = lat - sigmas[s] * e, lat = a * lat + b * D + c * hist with (a, b, c) = coef[s]
     (scheduler.sampler_coefficients as fp32 [n, 3]), hist = D; with z0 / eps / mask (all three) the keep-mask blend of
     euler_cfg_step_masked follows.  hist is not read where c == 0."""
-    fn = "sampler_step"
-    B, Cl, F, H, W = _step_operands(noise, lat, sigmas, step_idx, ncopy, fn)
-    _flat(hist, F32, lat.shape, "hist", fn)
-    if hist.data_ptr() == lat.data_ptr():
-        raise _lib.VstError(f"{fn}: hist must not be lat")
-    _flat(coef, F32, (sigmas.numel() - 1, 3), "coef", fn)
-    if factor is not None:
-        _flat(factor, F32, (B,), "factor", fn)
-        if ncopy != 2:
-            raise _lib.VstError(f"{fn}: a rescale factor needs both CFG branches (ncopy 2)")
-    given = [t is not None for t in (z0, eps, mask)]
-    if any(given) and not all(given):
-        raise _lib.VstError(f"{fn}: z0, eps and mask go together")
-    mask_clips = _keep_mask(lat, z0, eps, mask, fn) if mask is not None else 0
-    _lib.call("vst_sampler_step", _p(noise), ncopy, float(guidance), _p(lat), _p(hist), B, Cl, F, H * W, _p(sigmas),
+    B, Cl, F, HW, mask_clips = _sampler_operands("sampler_step", noise, lat, hist, sigmas, coef, 3, step_idx, ncopy,
+                                                 factor, z0, eps, mask)
+    _lib.call("vst_sampler_step", _p(noise), ncopy, float(guidance), _p(lat), _p(hist), B, Cl, F, HW, _p(sigmas),
               _p(coef), _p(step_idx), _p(factor), _p(z0), _p(eps), _p(mask), mask_clips, _stream())
 
 
@@ -1256,8 +1243,8 @@ def sampler_step(noise, lat, hist, sigmas, coef, step_idx, *, guidance=7.5, ncop
 def _noise_operands(seed, step_idx, stream_id, shape, F_total, f0, fn):
     """What every noise entry takes: the device seed (int64 [1], read as the uint64 of its bits) and step counter, a
     stream below 2^16, and a (B, Cl, F, H, W) shape holding frames [f0, f0 + F) of F_total.  Returns F_total."""
-    _flat(seed, torch.int64, (1,), "seed", fn)
-    _flat(step_idx, torch.int32, (1,), "step_idx", fn)
+    _block(seed, torch.int64, "seed", fn, (1,))
+    _step_counter(step_idx, fn)
     if len(shape) != 5 or min(shape) <= 0:
         raise _lib.VstError(f"{fn}: shape {tuple(shape)} must be (B, Cl, F, H, W), all positive")
     F_total = shape[2] if F_total is None else int(F_total)
@@ -1274,7 +1261,7 @@ def _noise_fill(entry, dtype, seed, step_idx, shape, stream_id, F_total, f0, out
     F_total = _noise_operands(seed, step_idx, stream_id, shape, F_total, f0, fn)
     if out is None:
         out = torch.empty(shape, dtype=dtype, device=seed.device)
-    _flat(out, dtype, shape, "out", fn)
+    _block(out, dtype, "out", fn, shape)
     B, Cl, F, H, W = shape
     _lib.call(entry, _p(out), _p(seed), _p(step_idx), int(stream_id), B, Cl, F, F_total, int(f0), H * W, _stream())
     return out
@@ -1283,7 +1270,7 @@ def _noise_fill(entry, dtype, seed, step_idx, shape, stream_id, F_total, f0, out
 def noise_bits(seed, step_idx, shape, *, stream_id=0, F_total=None, f0=0, out=None):
     """The Philox4x32-10 word of every element of a (B, Cl, F, H, W) tensor holding frames [f0, f0 + F) of clips of
     F_total frames (default F), as int32 bit patterns (view them as torch.uint32): scheduler.noise_reference's bits."""
-    return _noise_fill("vst_noise_bits", torch.int32, seed, step_idx, shape, stream_id, F_total, f0, out)
+    return _noise_fill("vst_noise_bits", I32, seed, step_idx, shape, stream_id, F_total, f0, out)
 
 
 def noise_normal(seed, step_idx, shape, *, stream_id=0, F_total=None, f0=0, out=None):
@@ -1298,22 +1285,11 @@ def sampler_step_noise(noise, lat, hist, sigmas, coef, step_idx, seed, *, F_tota
     lat = a * lat + b * D + c * hist + d * xi, xi = noise_normal(seed, step_idx, lat.shape, F_total=, f0=) generated in
     the kernel; the keep-mask blend follows.  Where d == 0 no noise is generated and lat has sampler_step's bits."""
     fn = "sampler_step_noise"
-    B, Cl, F, H, W = _step_operands(noise, lat, sigmas, step_idx, ncopy, fn)
-    _flat(hist, F32, lat.shape, "hist", fn)
-    if hist.data_ptr() == lat.data_ptr():
-        raise _lib.VstError(f"{fn}: hist must not be lat")
-    _flat(coef, F32, (sigmas.numel() - 1, 4), "coef", fn)
+    B, Cl, F, HW, mask_clips = _sampler_operands(fn, noise, lat, hist, sigmas, coef, 4, step_idx, ncopy, factor, z0,
+                                                 eps, mask)
     F_total = _noise_operands(seed, step_idx, 0, tuple(lat.shape), F_total, f0, fn)
-    if factor is not None:
-        _flat(factor, F32, (B,), "factor", fn)
-        if ncopy != 2:
-            raise _lib.VstError(f"{fn}: a rescale factor needs both CFG branches (ncopy 2)")
-    given = [t is not None for t in (z0, eps, mask)]
-    if any(given) and not all(given):
-        raise _lib.VstError(f"{fn}: z0, eps and mask go together")
-    mask_clips = _keep_mask(lat, z0, eps, mask, fn) if mask is not None else 0
     _lib.call("vst_sampler_step_noise", _p(noise), ncopy, float(guidance), _p(lat), _p(hist), B, Cl, F, F_total,
-              int(f0), H * W, _p(sigmas), _p(coef), _p(step_idx), _p(seed), _p(factor), _p(z0), _p(eps), _p(mask),
+              int(f0), HW, _p(sigmas), _p(coef), _p(step_idx), _p(seed), _p(factor), _p(z0), _p(eps), _p(mask),
               mask_clips, _stream())
 
 
@@ -1331,16 +1307,16 @@ def cfg_rescale_factor(noise, lat_shape, *, guidance, phi, out=None, workspace=N
     if len(lat_shape) != 5 or min(lat_shape) <= 0:
         raise _lib.VstError(f"{fn}: latent shape {tuple(lat_shape)} must be (B, Cl, F, H, W), all positive")
     B, Cl, F, H, W = lat_shape
-    _flat(noise, BF16, (2 * B * F * H * W, Cl), "noise", fn)
+    _block(noise, BF16, "noise", fn, (2 * B * F * H * W, Cl))
     phi = float(phi)
     if not 0.0 <= phi <= 1.0:  # also refuses NaN
         raise _lib.VstError(f"{fn}: phi {phi} outside [0, 1]")
     if out is None:
         out = torch.empty(B, dtype=F32, device=noise.device)
-    _flat(out, F32, (B,), "out", fn)
+    _block(out, F32, "out", fn, (B,))
     if workspace is None:
         workspace = cfg_rescale_workspace(lat_shape, noise.device)
-    _flat(workspace, F32, None, "workspace", fn)
+    _block(workspace, F32, "workspace", fn)
     need = int(_lib.load().vst_cfg_rescale_factor_workspace_bytes(B, Cl, F, H * W))
     if workspace.numel() * 4 < need:
         raise _lib.VstError(f"{fn}: workspace of {workspace.numel() * 4} bytes, {need} needed")
@@ -1369,7 +1345,7 @@ def probe_hbm_read_gbs(device, nbytes=4 << 30, grid=4096, reps=3):
     """Best-of-`reps` streaming read rate of vst_probe_hbm_read over an `nbytes` buffer (>> the 256 MB
     Infinity Cache, so it is HBM)."""
     buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    sink = torch.empty(grid, dtype=torch.int32, device=device)
+    sink = torch.empty(grid, dtype=I32, device=device)
     best = 0.0
     for _ in range(reps + 1):
         s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -1387,18 +1363,17 @@ def conv3x3_down_pad0(x: torch.Tensor, nimg: int, H: int, W: int, w: torch.Tenso
                       out: torch.Tensor | None = None) -> torch.Tensor:
     """diffusers Downsample2D(padding=0): F.pad(x, (0,1,0,1)) + 3x3 stride-2 conv, NHWC.  Returns
     [nimg*((H-2)//2+1)*((W-2)//2+1), Cout]."""
-    _dev(x, BF16, "x")
-    _dev(w, BF16, "w")
-    C, Cout = x.shape[1], w.shape[0]
-    if not x.is_contiguous() or x.shape[0] != nimg * H * W or w.shape[1] != 9 * C or C % 64:
+    fn = "conv3x3_down_pad0"
+    C = _conv_in(x, nimg * H * W, "x", fn)
+    _view(w, BF16, "w", fn)
+    Cout = w.shape[0]
+    if w.shape[1] != 9 * C or C % 64:
         raise _lib.VstError("conv3x3_down_pad0: x [nimg*H*W, C] contiguous, C % 64 == 0, w [Cout, 9C]")
     OH, OW = (H - 2) // 2 + 1, (W - 2) // 2 + 1
     M = nimg * OH * OW
-    if out is None:
-        out = torch.empty((M, Cout), dtype=BF16, device=x.device)
-    _out(out, (M, Cout), BF16, "out", "conv3x3_down_pad0")
-    if bias is not None and (bias.dtype != F32 or bias.numel() != Cout):
-        raise _lib.VstError("conv3x3_down_pad0: bias must be fp32 [Cout]")
+    out = _new(out, (M, Cout), x, "out", fn)
+    if bias is not None:
+        _vec(bias, Cout, "bias", fn)
     with _Rec("conv3x3", 2.0 * M * Cout * 9 * C, 2.0 * (nimg * H * W * C + Cout * 9 * C + M * Cout),
               lambda: gemm_kernel_name(M, Cout, 9 * C, 2), (M, Cout, 9 * C)):
         ws = _workspace(x.device)
@@ -1409,15 +1384,15 @@ def conv3x3_down_pad0(x: torch.Tensor, nimg: int, H: int, W: int, w: torch.Tenso
 
 def gemm_f32out(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
     """fp32 [M, N] = a[M, K] @ w[N, K]^T without rounding the accumulator."""
-    _dev(a, BF16, "a")
-    _dev(w, BF16, "w")
+    _view(a, BF16, "a", "gemm_f32out")
+    _view(w, BF16, "w", "gemm_f32out")
     M, K = a.shape
     N = w.shape[0]
     if w.shape[1] != K:
         raise _lib.VstError(f"gemm_f32out: a {tuple(a.shape)} vs w {tuple(w.shape)}")
     if out is None:
         out = torch.empty((M, N), dtype=F32, device=a.device)
-    _out_flat(out, (M, N), F32, "out", "gemm_f32out")
+    _block(out, F32, "out", "gemm_f32out", (M, N))
     with _Rec("gemm_f32out", 2.0 * M * N * K, 2.0 * (M * K + N * K) + 4.0 * M * N,
               lambda: gemm_kernel_name(M, N, K, 0), (M, N, K)):
         _lib.call("vst_gemm_f32out", _p(a), _ld(a), _p(w), _ld(w), M, N, K, _p(out), _stream())
@@ -1426,35 +1401,43 @@ def gemm_f32out(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor | None = Non
 
 def softmax_rows(s: torch.Tensor, scale: float, out: torch.Tensor | None = None) -> torch.Tensor:
     """bf16 softmax(scale * s) over the last dim of an fp32 [rows, n] matrix."""
-    if not s.is_cuda or s.dtype != F32 or s.dim() != 2 or s.stride(1) != 1:
-        raise _lib.VstError("softmax_rows: s must be an fp32 2-D row-major device view")
+    _view(s, F32, "s", "softmax_rows")
     rows, n = s.shape
-    if out is None:
-        out = torch.empty((rows, n), dtype=BF16, device=s.device)
-    _out(out, (rows, n), BF16, "out", "softmax_rows")
+    out = _new(out, (rows, n), s, "out", "softmax_rows")
     with _Rec("softmax", 0.0, 4.0 * rows * n + 2.0 * rows * n):
         _lib.call("vst_softmax_rows", _p(s), _ld(s), rows, n, float(scale), _p(out), _ld(out), _stream())
     return out
 
 
+def _padded_width(ldd, C, fn):
+    ldd = C if ldd is None else int(ldd)
+    if ldd < C:
+        raise _lib.VstError(f"{fn}: ldd {ldd} < C {C}")
+    return ldd
+
+
 def nchw_to_nhwc(x: torch.Tensor, mul: float = 1.0, ldd: int | None = None) -> torch.Tensor:
     """fp32 (n, C, H, W) -> bf16 [n*H*W, ldd] (channels >= C zero)."""
-    if not x.is_cuda or x.dtype != F32 or x.dim() != 4 or not x.is_contiguous():
+    _block(x, F32, "x", "nchw_to_nhwc")
+    if x.dim() != 4:
         raise _lib.VstError("nchw_to_nhwc: x must be a contiguous fp32 (n, C, H, W) device tensor")
     n, C, H, W = x.shape
-    ldd = ldd or C
-    if ldd < C:
-        raise _lib.VstError(f"nchw_to_nhwc: ldd {ldd} < C {C}")
+    ldd = _padded_width(ldd or None, C, "nchw_to_nhwc")
     out = torch.empty((n * H * W, ldd), dtype=BF16, device=x.device)
     _lib.call("vst_nchw_to_nhwc", _p(x), n, C, H * W, float(mul), _p(out), ldd, _stream())
     return out
 
 
+def _nhwc_in(x, n, C, H, W, fn, name="x"):
+    """bf16 rows [n*H*W, >= C] with a row stride >= C."""
+    _view(x, BF16, name, fn, rows=n * H * W, min_cols=C)
+    if _ld(x) < C:
+        _fail(fn, name, f"row stride {_ld(x)} < C = {C}")
+
+
 def nhwc_to_nchw(x: torch.Tensor, n: int, C: int, H: int, W: int) -> torch.Tensor:
     """bf16 [n*H*W, >=C] -> fp32 (n, C, H, W)."""
-    _dev(x, BF16, "x")
-    if x.shape[0] != n * H * W or _ld(x) < C or x.shape[1] < C:
-        raise _lib.VstError(f"nhwc_to_nchw: x {tuple(x.shape)} (ld {_ld(x)}) vs n*H*W = {n * H * W} rows of >= C channels")
+    _nhwc_in(x, n, C, H, W, "nhwc_to_nchw")
     out = torch.empty((n, C, H, W), dtype=F32, device=x.device)
     _lib.call("vst_nhwc_to_nchw", _p(x), _ld(x), n, C, H * W, _p(out), _stream())
     return out
@@ -1462,9 +1445,7 @@ def nhwc_to_nchw(x: torch.Tensor, n: int, C: int, H: int, W: int) -> torch.Tenso
 
 def frames_to_u8(x: torch.Tensor, n: int, C: int, H: int, W: int) -> torch.Tensor:
     """bf16 [n*H*W, >=C] decoder output -> uint8 (n, H, W, C) frames (inference_animatediff.py:141-143)."""
-    _dev(x, BF16, "x")
-    if x.shape[0] != n * H * W or _ld(x) < C or x.shape[1] < C:
-        raise _lib.VstError(f"frames_to_u8: x {tuple(x.shape)} (ld {_ld(x)}) vs n*H*W = {n * H * W} rows of >= C channels")
+    _nhwc_in(x, n, C, H, W, "frames_to_u8")
     out = torch.empty((n, H, W, C), dtype=torch.uint8, device=x.device)
     _lib.call("vst_frames_to_u8", _p(x), _ld(x), n, C, H * W, _p(out), _stream())
     return out
@@ -1473,15 +1454,11 @@ def frames_to_u8(x: torch.Tensor, n: int, C: int, H: int, W: int) -> torch.Tenso
 def u8_to_frames(x: torch.Tensor, ldd: int | None = None) -> torch.Tensor:
     """uint8 (n, H, W, C) frames -> bf16 [n*H*W, ldd] rows in [-1, 1] (channels >= C zero): the encoder's input,
     (v / 255 - 0.5) / 0.5 as video_dataset.py:117-118 normalises, rounded to bf16."""
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise _lib.VstError("u8_to_frames: x must be a device tensor; the HIP path has no CPU fallback")
-    if x.dtype != torch.uint8 or x.dim() != 4 or not x.is_contiguous() or x.numel() == 0:
-        raise _lib.VstError(f"u8_to_frames: x must be a contiguous uint8 (n, H, W, C) tensor, got {x.dtype} "
-                            f"{tuple(x.shape)} stride {x.stride()}")
+    _block(x, torch.uint8, "x", "u8_to_frames")
+    if x.dim() != 4 or x.numel() == 0:
+        raise _lib.VstError(f"u8_to_frames: x must be a contiguous uint8 (n, H, W, C) tensor, got {tuple(x.shape)}")
     n, H, W, C = x.shape
-    ldd = C if ldd is None else int(ldd)
-    if ldd < C:
-        raise _lib.VstError(f"u8_to_frames: ldd {ldd} < C {C}")
+    ldd = _padded_width(ldd, C, "u8_to_frames")
     out = torch.empty((n * H * W, ldd), dtype=BF16, device=x.device)
     _lib.call("vst_u8_to_frames", _p(x), n, C, H * W, _p(out), ldd, _stream())
     return out
@@ -1489,12 +1466,9 @@ def u8_to_frames(x: torch.Tensor, ldd: int | None = None) -> torch.Tensor:
 
 def vae_sample(moments: torch.Tensor, n: int, H: int, W: int, eps: torch.Tensor | None, mul: float) -> torch.Tensor:
     """moments bf16 [n*H*W, >=8] -> fp32 (n, 4, H, W) = (mean + exp(logvar/2) * eps) * mul (eps None: mean * mul)."""
-    _dev(moments, BF16, "moments")
-    if moments.shape[0] != n * H * W or _ld(moments) < 8 or moments.shape[1] < 8:
-        raise _lib.VstError(f"vae_sample: moments {tuple(moments.shape)} vs n*H*W = {n * H * W} rows of >= 8 "
-                            "channels (mean | logvar)")
-    if eps is not None and (eps.dtype != F32 or not eps.is_contiguous() or eps.shape != (n, 4, H, W)):
-        raise _lib.VstError("vae_sample: eps must be contiguous fp32 (n, 4, H, W)")
+    _nhwc_in(moments, n, 8, H, W, "vae_sample", "moments")
+    if eps is not None:
+        _block(eps, F32, "eps", "vae_sample", (n, 4, H, W))
     out = torch.empty((n, 4, H, W), dtype=F32, device=moments.device)
     _lib.call("vst_vae_sample", _p(moments), _ld(moments), n, H * W, _p(eps), float(mul), _p(out), _stream())
     return out

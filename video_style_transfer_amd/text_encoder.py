@@ -26,8 +26,8 @@ from typing import Optional, Tuple
 import torch
 from torch import nn
 
-from . import _lib
 from . import kernels as K
+from ._lib import VstError
 
 BF16 = torch.bfloat16
 
@@ -94,10 +94,7 @@ class CLIPAttention(nn.Module):
         C = n.shape[1]
         W, b = self.qkv_operands()
         qkv = K.linear(n, W, b)
-        o = torch.empty((B * L, C), dtype=BF16, device=n.device)
-        _lib.call("vst_causal_attention", qkv.data_ptr(), qkv.stride(0), qkv[:, C:].data_ptr(),
-                  qkv[:, 2 * C:].data_ptr(), qkv.stride(0), o.data_ptr(), o.stride(0), B, self.heads, L,
-                  self.head_dim, float(self.head_dim ** -0.5), K._stream())
+        o = K.causal_attention(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], B, self.heads, L, self.head_dim)
         return K.linear(o, self.out_proj.weight, self.out_proj.f32_bias())
 
 
@@ -115,7 +112,7 @@ class CLIPMLP(nn.Module):
             h = K.linear(n, self.fc1.weight, self.fc1.f32_bias(), act="gelu")
         else:
             h = K.linear(n, self.fc1.weight, self.fc1.f32_bias())
-            _lib.call("vst_quick_gelu", h.data_ptr(), h.data_ptr(), h.numel(), K._stream())
+            K.quick_gelu(h, out=h)
         return K.linear(h, self.fc2.weight, self.fc2.f32_bias())
 
 
@@ -130,14 +127,7 @@ class _LayerNorm(nn.LayerNorm):
 
     def add_run(self, h, y=None):
         """(h + y fp32, LayerNorm of it bf16): vst_residual_layernorm."""
-        g, b = self.f32()
-        rows, C = h.shape
-        ho = torch.empty_like(h)
-        n = torch.empty((rows, C), dtype=BF16, device=h.device)
-        _lib.call("vst_residual_layernorm", h.data_ptr(), h.stride(0), None if y is None else y.data_ptr(),
-                  0 if y is None else y.stride(0), rows, C, g.data_ptr(), b.data_ptr(), float(self.eps),
-                  ho.data_ptr(), ho.stride(0), n.data_ptr(), n.stride(0), K._stream())
-        return ho, n
+        return K.residual_layer_norm(h, y, *self.f32(), self.eps)
 
 
 class CLIPEncoderLayer(nn.Module):
@@ -185,16 +175,14 @@ class CLIPTextTransformer(nn.Module):
             raise ValueError(f"sequence of {L} tokens > max_position_embeddings {cfg.max_position_embeddings}")
         dev = self.embeddings.token_embedding.weight.device
         if dev.type != "cuda":
-            raise _lib.VstError("CLIP text encoder: weights are on CPU; the HIP path has no CPU fallback")
+            raise VstError("CLIP text encoder: weights are on CPU; the HIP path has no CPU fallback")
         ids_cpu = input_ids.detach().to("cpu", torch.int64)
         if int(ids_cpu.min()) < 0 or int(ids_cpu.max()) >= cfg.vocab_size:
             raise IndexError("input_ids out of the vocabulary range")  # nn.Embedding's error, checked on the host
         ids = ids_cpu.to(torch.int32).to(dev)
         C = cfg.hidden_size
         tok, pos = self.embeddings.token_embedding.weight, self.embeddings.position_embedding.weight
-        h = torch.empty((B * L, C), dtype=torch.float32, device=dev)
-        _lib.call("vst_embed_tokens", ids.data_ptr(), B * L, L, tok.data_ptr(), pos.data_ptr(), C, h.data_ptr(), C,
-                  K._stream())
+        h = K.embed_tokens(ids.reshape(-1), L, tok, pos)
         states = [h]
         n = cfg.num_hidden_layers if n_layers is None else n_layers
         layers = list(self.encoder.layers[:n])
