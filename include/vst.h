@@ -198,6 +198,22 @@ int vst_spatial_attention_frames(const void* q, int ldq, const void* k, const vo
                                  int nclip, int F, int heads, int N, int src1, int src2, int head_dim, float scale,
                                  void* stream);
 
+/* StyleAligned AdaIN of q/k(/v) to the anchor frame, ahead of vst_spatial_attention_frames (no line of the reference
+ * does this; the definition is this project's, DESIGN.md §18, after Hertz et al., "Style Aligned Image Generation via
+ * Shared Attention", CVPR 2024).  x: bf16 view, rows (b*F + f)*N + p, columns [0, C), modified in place.  Per clip b,
+ * frame f and column c, in fp32 from the bf16 values:
+ *   mu[b,f,c] = mean over the N tokens;  sd[b,f,c] = sqrt(sum (x - mu)^2 / (N - 1) + eps)  (unbiased, as torch.var);
+ *   x[b,f,p,c] = bf16((x[b,f,p,c] - mu[b,f,c]) * (sd[b,anchor,c] / sd[b,f,c]) + mu[b,anchor,c])  for f != anchor.
+ * The rows of frame `anchor` of every clip are not written.  A constant column has sd = sqrt(eps) and becomes
+ * mu[b,anchor,c].  stats: caller-owned fp32 [nclip * F][2][C] (per frame its mean row, then its sd row), 16-byte
+ * aligned, written for every frame, the anchor included; it is the hand-over between the two launches (statistics,
+ * apply; F == 1: statistics only, x untouched).  No atomics, every sum in an order fixed by (N, C): the same bits on
+ * every call, and a clip's bits do not depend on nclip.  C % 8 == 0, ldx >= C, ldx % 8 == 0, x 16-byte aligned.
+ * Returns 1 before any launch on a NULL pointer, a non-positive size, N < 2, anchor outside [0, F), eps negative or
+ * not finite, a stride or alignment as above, or byte extents past 2^31 - 1. */
+int vst_frame_adain(void* x, int ldx, int nclip, int F, int N, int C, int anchor, float eps, float* stats,
+                    void* stream);
+
 /* Frame-axis attention (motion module / TemporalTransformerBlock, animatediff/temporal_transformer.py:66-68):
  * token (clip b, frame f, pixel p) at row (b*F + f)*HW + p; F <= 32; head_dim in {8,16,32,40,64,80,160}. */
 int vst_temporal_attention(const void* q, const void* k, const void* v, int ldqkv, void* o, int ldo, int nclip,

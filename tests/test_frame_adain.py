@@ -1,0 +1,217 @@
+"""StyleAligned AdaIN of q/k/v to the anchor frame, host side: the C ABI entry's signature, export and
+argument checks, the fp64 reference that the GPU tests (tests/test_frame_adain_gpu.py) compare the HIP path with, the
+`adain` option of CrossFrameAttention, and the wrapper's operand checks (the recorder pattern of
+tests/test_operand_checks.py)."""
+import ctypes
+import types
+
+import pytest
+import torch
+
+from test_host import fake_device_tensor as dev
+
+BF16, F32 = torch.bfloat16, torch.float32
+
+
+# ---------------------------------------------------------------- the fp64 reference
+def adain_ref(x, nclip, F, N, anchor, eps=1e-5):
+    """fp64 torch: rows (b*F + f)*N + p of x [nclip*F*N, C].  Returns (y, mu, sd): y[b, f] = (x - mu_f) * (sd_a / sd_f)
+    + mu_a per column for f != anchor and x itself for the anchor; mu, sd [nclip, F, C] with sd = sqrt(var + eps), var
+    the unbiased variance over the frame's N tokens."""
+    x4 = x.double().reshape(nclip, F, N, -1)
+    mu = x4.mean(2)
+    sd = (x4.var(2, unbiased=True) + eps).sqrt()
+    ratio = sd[:, anchor][:, None] / sd                      # [nclip, F, C]
+    y = (x4 - mu[:, :, None]) * ratio[:, :, None] + mu[:, anchor][:, None, None]
+    y[:, anchor] = x4[:, anchor]
+    return y.reshape(nclip * F * N, -1), mu, sd
+
+
+def test_reference_closed_forms():
+    nclip, F, N, C, a = 2, 4, 24, 16, 2
+    g = torch.Generator().manual_seed(0)
+    x = torch.randn(nclip, F, N, C, generator=g, dtype=torch.float64)
+    x = x * (0.5 + torch.rand(nclip, F, 1, C, generator=g, dtype=torch.float64)) + 3 * torch.randn(
+        nclip, F, 1, C, generator=g, dtype=torch.float64)
+    x[:, 1, :, 3] = 7.25            # a constant column in frame 1
+    x[:, 3] = x[:, a]               # a frame equal to the anchor
+    eps = 1e-5
+    y, mu, sd = adain_ref(x.reshape(-1, C), nclip, F, N, a, eps)
+    y = y.view(nclip, F, N, C)
+    # the anchor is the identity, a frame equal to it is unchanged, a constant column becomes the anchor's mean
+    assert torch.equal(y[:, a], x[:, a])
+    assert (y[:, 3] - x[:, 3]).abs().max() <= 1e-12
+    assert (y[:, 1, :, 3] - mu[:, a, 3][:, None]).abs().max() <= 1e-12
+    assert (sd[:, 1, 3] - eps ** 0.5).abs().max() <= 1e-12
+    # afterwards a frame has the anchor's mean and, up to the eps inside both roots, its sd:
+    #   var(y) = var_f * (var_a + eps) / (var_f + eps)
+    _, mu_y, sd_y = adain_ref(y.reshape(-1, C), nclip, F, N, a, eps)
+    var_f, var_a = sd ** 2 - eps, (sd[:, a] ** 2 - eps)[:, None]
+    assert (mu_y - mu[:, a][:, None]).abs().max() <= 1e-12
+    want = (var_f * (var_a + eps) / (var_f + eps) + eps).sqrt()
+    assert (sd_y - want).abs().max() <= 1e-12
+    keep = torch.ones(F, C, dtype=torch.bool)
+    keep[1, 3] = False              # (the constant column has no variance to rescale)
+    assert ((sd_y - sd[:, a][:, None]).abs() / sd[:, a][:, None])[:, keep].max() <= 2 * eps / var_f[:, keep].min()
+    # statistics as torch states them
+    assert torch.allclose(sd ** 2 - eps, x.var(2, unbiased=True), rtol=0, atol=1e-12)
+
+
+# ---------------------------------------------------------------- the C ABI entry
+def test_entry_declared_exported_and_checks_arguments():
+    """include/vst.h declares vst_frame_adain with the issue's argument list, libvst_hip.so exports it, and the entry
+    refuses bad arguments on the host (no GPU needed: every call below returns VST_ERR_ARG before any launch; the
+    pointers are never dereferenced)."""
+    from video_style_transfer_amd import _lib
+    P, I, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+    assert "vst_frame_adain" in _lib.SIGNATURES
+    assert _lib.SIGNATURES["vst_frame_adain"] == (I, [P, I, I, I, I, I, I, F, P, P])
+    assert hasattr(ctypes.CDLL(_lib.LIB_PATH), "vst_frame_adain")
+    f = _lib.load().vst_frame_adain
+    X, S = 4096, 65536
+
+    def call(x=X, ldx=64, nclip=1, Fr=4, N=16, C=64, anchor=0, eps=1e-5, stats=S):
+        return f(x, ldx, nclip, Fr, N, C, anchor, eps, stats, None)
+
+    assert call(x=None) == 1
+    assert call(stats=None) == 1
+    assert call(N=1) == 1              # the unbiased variance needs two tokens
+    assert call(N=0) == 1
+    assert call(anchor=4) == 1         # anchor outside [0, F)
+    assert call(anchor=-1) == 1
+    assert call(eps=-1e-5) == 1
+    assert call(eps=float("inf")) == 1
+    assert call(eps=float("nan")) == 1
+    assert call(C=60) == 1             # C % 8
+    assert call(C=0) == 1
+    assert call(ldx=56) == 1           # ldx < C
+    assert call(ldx=68) == 1           # ldx % 8
+    assert call(x=X + 8) == 1          # 16-byte bases
+    assert call(stats=S + 4) == 1
+    assert call(nclip=0) == 1
+    assert call(Fr=0) == 1
+    # byte extents past 2^31 - 1: 64 clips x 32 frames x 4096 tokens at a row stride of 2^20 elements
+    assert call(ldx=1 << 20, nclip=64, Fr=32, N=4096) == 1
+
+
+# ---------------------------------------------------------------- the option
+def test_option_adain_values_and_anchor():
+    from video_style_transfer_amd import _lib
+    from video_style_transfer_amd.unet_motion import CrossFrameAttention, as_cross_frame, check_cross_frame
+    model = types.SimpleNamespace(named_modules=lambda: [])
+    for adain, blocks in ((None, 0), ("qk", 2), ("qkv", 3)):
+        cf = CrossFrameAttention(("first",), adain=adain)
+        assert cf.adain == adain and cf.adain_blocks == blocks
+        check_cross_frame(model, 4, cf)
+    for bad in ("q", "kv", "QK", "", True, 2):
+        with pytest.raises(_lib.VstError, match="cross_frame"):
+            check_cross_frame(model, 4, CrossFrameAttention(("first",), adain=bad))
+        with pytest.raises(_lib.VstError, match="cross_frame"):      # a bad value is refused on any clip
+            check_cross_frame(model, 1, CrossFrameAttention(("first",), adain=bad))
+    # the anchor: the first source that is a fixed frame
+    assert CrossFrameAttention(("first",), adain="qk").anchor == 0
+    assert CrossFrameAttention((3,), adain="qk").anchor == 3
+    assert CrossFrameAttention(("prev", 2), adain="qkv").anchor == 2
+    assert CrossFrameAttention((2, "first")).anchor == 2
+    assert CrossFrameAttention(("prev",)).anchor is None
+    check_cross_frame(model, 4, CrossFrameAttention(("prev",)))      # fine without adain
+    for adain in ("qk", "qkv"):
+        with pytest.raises(_lib.VstError, match="cross_frame"):
+            check_cross_frame(model, 4, CrossFrameAttention(("prev",), adain=adain))
+    with pytest.raises(_lib.VstError, match="cross_frame"):          # the anchor is a source: it must be in the clip
+        check_cross_frame(model, 4, CrossFrameAttention((4,), adain="qk"))
+    # plain sources leave adain None; an option object passes through unchanged
+    for src in (("first",), "prev", 3, ("first", "prev")):
+        assert as_cross_frame(src).adain is None
+    cf = CrossFrameAttention(("first",), adain="qk")
+    assert as_cross_frame(cf) is cf
+    assert cf != CrossFrameAttention(("first",)) and cf == CrossFrameAttention("first", "qk")
+    with pytest.raises(Exception):   # frozen
+        cf.adain = "qkv"
+
+
+def test_option_refuses_a_level_below_two_tokens():
+    """The tiny UNet halves the latent once per down block: a 2 x 1 latent leaves its deepest level one token."""
+    from video_style_transfer_amd import _lib
+    from video_style_transfer_amd.config import UNetMotionConfig
+    from video_style_transfer_amd.unet_motion import (CrossFrameAttention, UNetMotionModel, check_cross_frame,
+                                                      spatial_attention_tokens)
+    model = UNetMotionModel(UNetMotionConfig.tiny())
+    tok = spatial_attention_tokens(model, 16, 16)
+    assert max(tok) <= 256 and min(tok) >= 2 and min(tok) < max(tok)
+    cf = CrossFrameAttention(("first",), adain="qk")
+    check_cross_frame(model, 4, cf, None, (16, 16))
+    assert min(spatial_attention_tokens(model, 2, 1)) == 1
+    with pytest.raises(_lib.VstError, match="cross_frame"):
+        check_cross_frame(model, 4, cf, None, (2, 1))
+    check_cross_frame(model, 4, CrossFrameAttention(("first",)), None, (2, 1))   # without adain: no variance taken
+    check_cross_frame(model, 1, cf, None, (2, 1))                                 # single-frame clip: inactive
+
+
+# ---------------------------------------------------------------- the wrapper's operand checks
+@pytest.fixture
+def K(monkeypatch):
+    from video_style_transfer_amd import kernels
+    calls = []
+    monkeypatch.setattr(kernels._lib, "call", lambda name, *args: calls.append((name, args)) or 0)
+    monkeypatch.setattr(kernels, "_stream", lambda: 0)
+    kernels.calls = calls
+    yield kernels
+    del kernels.calls
+
+
+# 2 clips x 3 frames x 4 tokens, C = 64 inside a q|k|v buffer of 192 columns
+def _good():
+    return dict(x=dev(24, 192)[:, :64], nclip=2, F=3, N=4, anchor=1, stats=dev(6, 2, 64, dtype=F32))
+
+
+BAD = {
+    "host x": ("x", lambda: torch.zeros(24, 64, dtype=BF16)),
+    "fp32 x": ("x", lambda: dev(24, 64, dtype=F32)),
+    "short x": ("x", lambda: dev(12, 64)),
+    "C % 8": ("x", lambda: dev(24, 68)),
+    "odd stride": ("x", lambda: dev(24, 68)[:, :64]),
+    "column stride": ("x", lambda: dev(24, 128)[:, ::2]),
+    "short stats": ("stats", lambda: dev(5, 2, 64, dtype=F32)),
+    "narrow stats": ("stats", lambda: dev(6, 2, 32, dtype=F32)),
+    "bf16 stats": ("stats", lambda: dev(6, 2, 64)),
+    "host stats": ("stats", lambda: torch.zeros(6, 2, 64, dtype=F32)),
+    "strided stats": ("stats", lambda: dev(6, 2, 128, dtype=F32)[:, :, :64]),
+    "anchor == F": ("anchor", lambda: 3),
+    "anchor < 0": ("anchor", lambda: -1),
+    "N == 1": ("N", lambda: 1),
+}
+
+
+def _run(K, o, **kw):
+    return K.frame_adain(o["x"], o["nclip"], o["F"], o["N"], o["anchor"], stats=o["stats"], **kw)
+
+
+@pytest.mark.parametrize("label", list(BAD))
+def test_bad_operand_is_refused_before_the_library(K, label):
+    arg, bad = BAD[label]
+    with pytest.raises(K._lib.VstError, match=f"^frame_adain: {arg} "):
+        _run(K, {**_good(), arg: bad()})
+    assert K.calls == []
+
+
+@pytest.mark.parametrize("eps", [-1e-5, float("inf"), float("nan")])
+def test_bad_eps_is_refused_before_the_library(K, eps):
+    with pytest.raises(K._lib.VstError, match="^frame_adain: eps "):
+        _run(K, _good(), eps=eps)
+    assert K.calls == []
+
+
+def test_good_operands_reach_the_library_once(K):
+    o = _good()
+    ret = _run(K, o)
+    assert ret is o["stats"]
+    assert len(K.calls) == 1
+    name, args = K.calls[0]
+    assert name == "vst_frame_adain"
+    assert args == (o["x"].data_ptr(), 192, 2, 3, 4, 64, 1, 1e-5, o["stats"].data_ptr(), 0)
+    # stats not given: allocated next to x, [nclip * F, 2, C] fp32, and returned
+    del K.calls[:]
+    ret = K.frame_adain(o["x"], 2, 3, 4, 0)
+    assert tuple(ret.shape) == (6, 2, 64) and ret.dtype == F32 and len(K.calls) == 1
+    assert K.calls[0][1][8] == ret.data_ptr()

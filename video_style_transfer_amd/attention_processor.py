@@ -121,6 +121,9 @@ class AnimateDiffAttnProcessor2_0:
             if cross_frame is not None:
                 # the frame's own tokens plus those of the source frames of the same clip, read in place
                 cf, Fr = cross_frame
+                if cf.adain is not None:
+                    # StyleAligned: q | k (| v) normalised per column to the anchor frame's statistics, in place
+                    K.frame_adain(qkv[:, :cf.adain_blocks * inner], batch // Fr, Fr, N, cf.anchor)
                 o = K.spatial_attention_frames(qkv[:, :inner], qkv[:, inner:2 * inner], qkv[:, 2 * inner:],
                                                batch // Fr, Fr, heads, N, cf.sources, scale=hd ** -0.5)
             elif hd == 64:

@@ -651,6 +651,43 @@ def spatial_attention_frames(q, k, v, nclip, F, heads, N, sources, scale=None, o
     return out
 
 
+def frame_adain(x, nclip, F, N, anchor, eps=1e-5, stats=None):
+    """StyleAligned AdaIN to the anchor frame, in place (vst_frame_adain): x [nclip*F*N, C] bf16 view,
+    rows (b*F + f)*N + p; every frame f != anchor of a clip becomes (x - mu_f) * (sd_a / sd_f) + mu_a per column, with
+    the mean and the unbiased sd (eps inside the root) over the frame's N tokens; the anchor's rows are not written.
+    stats: fp32 [nclip*F, 2, C] (mean row, sd row per frame), allocated when not given; written for every frame and
+    returned.  F == 1 writes the statistics and leaves x alone."""
+    fn = "frame_adain"
+    nclip, F, N, anchor, eps = int(nclip), int(F), int(N), int(anchor), float(eps)
+    if nclip < 1 or F < 1:
+        _fail(fn, "nclip, F", f"= {nclip}, {F}: expected positive counts")
+    if N < 2:
+        _fail(fn, "N", f"= {N}: the unbiased variance needs at least 2 tokens per frame")
+    if not 0 <= anchor < F:
+        _fail(fn, "anchor", f"= {anchor}: outside the clip's frames 0..{F - 1}")
+    if not 0.0 <= eps < float("inf"):
+        _fail(fn, "eps", f"= {eps}: expected a finite value >= 0")
+    _view(x, BF16, "x", fn, rows=nclip * F * N)
+    C = x.shape[1]
+    if C == 0 or C % 8 or _ld(x) % 8 or x.data_ptr() % 16:
+        _fail(fn, "x", f"needs a multiple of 8 columns, a row stride that is a multiple of 8 and a 16-byte aligned "
+                       f"base, got shape {tuple(x.shape)} stride {x.stride()}")
+    if stats is None:
+        stats = torch.empty((nclip * F, 2, C), dtype=F32, device=x.device)
+    else:
+        _block(stats, F32, "stats", fn, shape=(nclip * F, 2, C))
+        if stats.data_ptr() % 16:
+            _fail(fn, "stats", "needs a 16-byte aligned base")
+    rows, moved = nclip * F * N, nclip * (F - 1) * N
+    # statistics: one add, then subtract + fma per element; apply: subtract + fma.  HBM: x once for the statistics
+    # (their second read is the L2's), once more and back for the apply; the statistics out and in again.
+    nbytes = 2.0 * (rows + 2 * moved) * C + 8.0 * nclip * (3 * F - 2) * C
+    with _Rec("frame_adain", (4.0 * rows + 3.0 * moved) * C, nbytes,
+              lambda: "frame_adain_stats_kernel+frame_adain_apply_kernel", (nclip * F, N, C)):
+        _lib.call("vst_frame_adain", _p(x), _ld(x), nclip, F, N, C, anchor, eps, _p(stats), _stream())
+    return stats
+
+
 def temporal_attention(q, k, v, nclip, F, HW, heads, head_dim, out=None, scale=None):
     """Frame-axis attention; rows (b*F + f)*HW + p.  q/k/v views share one row stride."""
     fn = "temporal_attention"

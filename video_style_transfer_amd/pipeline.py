@@ -105,7 +105,7 @@ class AnimateDiffDenoiser:
         if unet.config.motion_modules:
             check_clip_length(num_frames, unet.config.motion_max_seq_length, self.context)
         self.cross_frame = as_cross_frame(cross_frame)
-        check_cross_frame(unet, num_frames, self.cross_frame, shard)
+        check_cross_frame(unet, num_frames, self.cross_frame, shard, (height // 8, width // 8))
         self.unet = unet
         self.nclips = num_clips
         self.shard = shard

@@ -155,8 +155,13 @@ class CrossFrameAttention:
     """Cross-frame (extended) spatial self-attention (DESIGN.md "Cross-frame spatial self-attention"): attn1 of every
     spatial transformer block attends to its own frame's tokens plus those of the `sources` frames of the same clip,
     under one softmax.  One or two distinct sources, each "first" (frame 0), "prev" (frame max(f - 1, 0)) or a frame
-    index.  Inactive on single-frame clips, which run exactly as without it."""
+    index.  Inactive on single-frame clips, which run exactly as without it.
+    `adain` "qk" or "qkv" (StyleAligned): before that attention, the queries and keys (and values) of
+    every frame are AdaIN-normalised, per column, to the statistics of the anchor frame, the first source that is a
+    fixed frame ("first" or an index).  None: no such step.  Its values and its need of a fixed-frame source are
+    checked by check_cross_frame."""
     sources: tuple = ("first",)
+    adain: Optional[str] = None
 
     def __post_init__(self):
         src = (self.sources,) if isinstance(self.sources, (str, int)) else tuple(self.sources)
@@ -169,17 +174,55 @@ class CrossFrameAttention:
     def active(self, F: int) -> bool:
         return F > 1
 
+    @property
+    def anchor(self) -> Optional[int]:
+        """The frame the AdaIN normalises to: the first source that is a fixed frame, None when there is none."""
+        return next((s for s in map(K.frame_source, self.sources) if s >= 0), None)
+
+    @property
+    def adain_blocks(self) -> int:
+        """How many of the q | k | v column blocks the AdaIN covers (0: no AdaIN)."""
+        return {None: 0, "qk": 2, "qkv": 3}[self.adain]
+
 
 def as_cross_frame(cf) -> Optional[CrossFrameAttention]:
     """None, a CrossFrameAttention, or its sources (("first",), "prev", 3, ...)."""
     return cf if cf is None or isinstance(cf, CrossFrameAttention) else CrossFrameAttention(cf)
 
 
-def check_cross_frame(model, F: int, cf: Optional[CrossFrameAttention], shard=None):
+def spatial_attention_tokens(model, h: int, w: int) -> list:
+    """Tokens per frame (H * W) at every level of `model` that has spatial transformer blocks, for an h x w latent."""
+    out = []
+    for blk in model.down_blocks:
+        if blk.attentions is not None:
+            out.append(h * w)
+        if blk.downsamplers is not None:
+            h, w = (h + 1) // 2, (w + 1) // 2
+    out.append(h * w)  # the mid block
+    for blk in model.up_blocks:
+        if blk.attentions is not None:
+            out.append(h * w)
+        if blk.upsamplers is not None:
+            h, w = 2 * h, 2 * w
+    return out
+
+
+def check_cross_frame(model, F: int, cf: Optional[CrossFrameAttention], shard=None, hw=None):
     """Refuse, before any launch, a cross_frame option the spatial self-attention cannot honour on a clip of F
-    frames (all ranks' frames together)."""
-    if cf is None or not cf.active(F):
+    frames (all ranks' frames together).  `hw`: the latent's (h, w), where the caller knows it; the AdaIN's unbiased
+    variance needs two tokens per frame at every level."""
+    if cf is None:
         return
+    if cf.adain not in (None, "qk", "qkv"):
+        raise K._lib.VstError(f"cross_frame: adain {cf.adain!r}; expected None, \"qk\" or \"qkv\"")
+    if cf.adain is not None and cf.anchor is None:
+        raise K._lib.VstError(f"cross_frame: adain={cf.adain!r} normalises to a fixed anchor frame, and sources "
+                              f"{cf.sources} name none (\"first\" or a frame index)")
+    if not cf.active(F):
+        return
+    if cf.adain is not None and hw is not None and min(spatial_attention_tokens(model, *hw)) < 2:
+        raise K._lib.VstError(f"cross_frame: adain={cf.adain!r} takes a variance over each frame's tokens, and a "
+                              f"{hw[0]} x {hw[1]} latent leaves a level of this model fewer than 2 per frame")
     if shard is not None and shard.world > 1:
         raise K._lib.VstError("cross_frame: a source frame's keys/values live on another rank under frame sharding "
                               f"(world {shard.world}); run the clip unsharded")
@@ -679,7 +722,7 @@ class UNetMotionModel(nn.Module):
         None means off: the enable_freeu default is applied by forward()."""
         freeu = as_freeu(freeu, x.device)
         cross_frame = as_cross_frame(cross_frame)
-        check_cross_frame(self, F * (shard.world if shard is not None else 1), cross_frame, shard)
+        check_cross_frame(self, F * (shard.world if shard is not None else 1), cross_frame, shard, (h, w))
         if lora_gate is not None and lora_gate.rows != B * F:
             raise K._lib.VstError(f"lora_gate: {lora_gate.rows} rows, expected B * F = {B * F}")
         if self.config.motion_modules:
@@ -718,7 +761,7 @@ class UNetMotionModel(nn.Module):
         B, Cin, F, h, w = sample.shape
         cross_frame = as_cross_frame(cross_frame)
         check_cross_frame(self, F * (frame_shard.world if frame_shard is not None else 1), cross_frame,
-                          frame_shard)
+                          frame_shard, (h, w))
         freeu = as_freeu(self.freeu if freeu is None else freeu, sample.device)  # bad values: before any launch
         if self.config.motion_modules:
             check_clip_length(F * (frame_shard.world if frame_shard is not None else 1),
