@@ -156,7 +156,8 @@ int vst_gemm_cross_attention_gated(const void* x, int ldx, const void* Acat, int
 
 /* Diagnostics: short name of the kernel (tile shape, epilogue, split-K) that a vst_gemm_ex
  * (kind 0 linear, 1 GEGLU) or vst_conv3x3_ex (kind 2, kind 3 = Cin not a multiple of 64) call with
- * these sizes and policy would launch.  Used by bench.py to attribute per-launch timings. */
+ * these sizes and policy would launch; kind 4: vst_conv3x3_up_folded, M = its GEMM rows (4 classes of nimg*H*W rows,
+ * each padded to a multiple of 256), K = 4 C1.  Used by bench.py to attribute per-launch timings. */
 const char* vst_gemm_kernel_name(int M, int N, int K, int kind, int tile, int splits, size_t ws_bytes);
 
 /* 3x3 conv, padding 1, NHWC, optional channel-concat second input, stride 1|2, fused nearest-2x
@@ -174,6 +175,23 @@ int vst_conv3x3_ex(const void* x1, int C1, const void* x2, int C2, int nimg, int
                    const void* Wt, int Cout, const float* bias, const float* row_bias, int row_bias_div,
                    int ld_row_bias, const void* R, int ldr, void* out, int ldc, int tile, int splits, void* workspace,
                    size_t ws_bytes, void* stream);
+/* The nearest-2x upsample conv (diffusers Upsample2D: F.interpolate(scale 2, nearest) + conv 3x3) as four 2x2 convs,
+ * one per output parity (py, px), on weights summed over the taps that coincide in the upsampled image: 4/9 of the
+ * multiply-adds of vst_conv3x3(upsample = 1).
+ * vst_fold_upsample_weight: Wt [Cout][3][3][C] -> Wf [4][Cout][2][2][C] (both contiguous, C % 8 == 0),
+ *   Wf[2 py + px][co][a][b][ci] = sum of Wt[co][ky][kx][ci] over ky in S(py, a), kx in S(px, b), with S(0, 0) = {0},
+ *   S(0, 1) = {1, 2}, S(1, 0) = {0, 1}, S(1, 1) = {2}; fp32 sums in ascending (ky, kx) order, rounded once to bf16.
+ *   The weights are constants of a model: fold once, outside the step.
+ * vst_conv3x3_up_folded: x1 [nimg*H*W][C1] (row stride ldx) -> out [nimg, 2H, 2W, Cout] (row stride ldc); Wf as
+ *   above with row stride ldwf >= 4 C1 per (class, co); bias fp32 [Cout] or NULL.  Output pixel (2y + py, 2x + px)
+ *   takes tap (a, b) from input pixel (y + py + a - 1, x + px + b - 1), zero outside the image.  Needs C1 % 64 == 0
+ *   and Cout % 8 == 0; a second source (x2 / C2), row_bias and R are not taken: VST_ERR_UNSUPPORTED for any of these.
+ *   Inputs / outputs past 2^31 - 1 bytes run as chunks of whole images; a row's bits do not depend on nimg.  The
+ *   result differs from vst_conv3x3(upsample = 1) by the one rounding of the folded weights. */
+int vst_fold_upsample_weight(const void* Wt, int Cout, int C, void* Wf, void* stream);
+int vst_conv3x3_up_folded(const void* x1, int ldx, int C1, const void* x2, int C2, int nimg, int H, int W,
+                          const void* Wf, int ldwf, int Cout, const float* bias, const float* row_bias, const void* R,
+                          void* out, int ldc, void* stream);
 
 /* Spatial SDPA, head_dim 64: replaces F.scaled_dot_product_attention in
  * AnimateDiffAttnProcessor2_0.__call__ (animatediff/attention_processor.py:78-80).  K/V row

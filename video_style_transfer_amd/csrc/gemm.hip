@@ -434,6 +434,35 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce_kernel(GemmArgs p, int
   }
 }
 
+// Weight fold of the folded upsample conv (gemm_common.h conv_row_folded): Wt [Cout][3][3][C] -> Wf [4][Cout][2][2][C],
+//   Wf[2 py + px][co][a][b][ci] = sum of Wt[co][ky][kx][ci] over ky in S(py, a), kx in S(px, b),
+//   S(0, 0) = {0}, S(0, 1) = {1, 2}, S(1, 0) = {0, 1}, S(1, 1) = {2},
+// summed in fp32 in ascending (ky, kx) order and rounded once to bf16.  One thread per 8 channels of one output row.
+__global__ __launch_bounds__(256) void fold_upsample_weight_kernel(const bf16_t* __restrict__ Wt, bf16_t* __restrict__ Wf,
+                                                                   int Cout, int C) {
+  const int C8 = C / 8;
+  const size_t total = (size_t)16 * Cout * C8;
+  for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
+    const int c8 = (int)(idx % C8);
+    const size_t t = idx / C8;  // (class, co, tap), the output's row order
+    const int tap = (int)(t & 3), co = (int)((t >> 2) % Cout), cls = (int)((t >> 2) / Cout);
+    const int py = cls >> 1, px = cls & 1, a = tap >> 1, b = tap & 1;
+    const int ky0 = a == 0 ? 0 : (py == 0 ? 1 : 2), ky1 = a == 0 ? (py == 0 ? 0 : 1) : 2;
+    const int kx0 = b == 0 ? 0 : (px == 0 ? 1 : 2), kx1 = b == 0 ? (px == 0 ? 0 : 1) : 2;
+    float acc[8];
+    bool first = true;
+    for (int ky = ky0; ky <= ky1; ++ky)
+      for (int kx = kx0; kx <= kx1; ++kx) {
+        float w8[8];
+        unpack8(*reinterpret_cast<const u32x4*>(Wt + ((size_t)co * 9 + ky * 3 + kx) * C + c8 * 8), w8);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[e] = first ? w8[e] : acc[e] + w8[e];
+        first = false;
+      }
+    *reinterpret_cast<u32x4*>(Wf + idx * 8) = pack8(acc);
+  }
+}
+
 // ---------------- dispatch: one query -> one plan (gemm_plan.h) ----------------
 // Everything the choice of a kernel depends on.  vst_gemm_ex and conv3x3_impl fill it from their arguments;
 // vst_gemm_kernel_name, which sees sizes only, assumes one A source, a packed C inside the 32-bit offsets (a larger
@@ -448,6 +477,7 @@ struct GemmQuery {
   size_t c_bytes;     // byte extent of C (M * ldc * 2)
   bool conv, vec;     // 3x3 conv; its channels allow 16-byte loads
   int C1, C2;
+  bool fold;          // conv: the folded upsample conv (K = 4 C1, M = 4 padded class rows, one source, no split-K)
 };
 
 GemmKnobs& gemm_knobs() {
@@ -621,17 +651,21 @@ static GemmPlan plan_gemm(const GemmQuery& q) {
   auto p8_tile = [&p](int family, int bn) { p.family = family, p.bm = bn == 320 ? 128 : 256, p.bn = bn; };
   if (q.conv) {
     if (p.family == kP8 || p.family == kSkinny) return {};  // convs take the ring's tile codes only
+    if (q.fold && (!q.vec || q.C2 || q.splits != 1 || q.epi != 0)) return {};
+    p.fold = q.fold;
     if (!q.vec) {
       p.family = kGather, p.bm = BM, p.bn = 64;  // (conv_in): register-staged kernel, no split
     } else {
       // 3x3 convs with both sources a multiple of 64 channels run on the 8-phase kernel (implicit im2col; 128x320
       // tiles where Cout is a multiple of 320, else the projection policy's width); VST_P8_CONV=0 restores the ring
       const bool p8 = p8_ok && gemm_knobs().p8_conv && !(q.C1 & 63) && !(q.C2 & 63) && !(N & 63) &&
-                      K == 9 * (q.C1 + q.C2);
+                      K == (q.fold ? 4 : 9) * (q.C1 + q.C2);
       const bool ring128 = p8 && conv_ring128(M, N);
       if (ring128) p.bm = 256, p.bn = 128;
       if (p8 && !ring128) p8_tile(kP8Conv, N % 320 == 0 ? 320 : p8_bn(M, N, false));
       else p.family = kRing, choose(q, ring128 ? 1 : q.splits, p);
+      // folded rows: a tile must divide the class padding (kFoldRowAlign), which the 192-row ring tile does not
+      if (q.fold && p.family == kRing && p.bm == 192) p.bm = 256;
     }
     return p;
   }
@@ -648,14 +682,14 @@ static GemmPlan plan_gemm(const GemmQuery& q) {
 }
 
 // The plan as the name bench.py and tools/pmc_traffic.py group launches by:
-// <family><BMxBN[,geglu][,splitk|,persist|,conv]>, "" for no plan
+// <family><BMxBN[,geglu][,splitk|,persist|,conv|,upfold]>, "" for no plan
 static const char* plan_name(const GemmPlan& p) {
   static const char* const fixed[] = {"", "gemm_rows", "gemm_skinny", "gemm_kernel<conv_in>"};
   if (p.family <= kGather) return fixed[p.family];
   const bool split = p.splits > 1;
   char buf[64];
   snprintf(buf, sizeof buf, "%s<%dx%d%s%s>", p.family == kRing ? "gemm_ring" : "gemm_p8", p.bm, p.bn,
-           p.epi == 1 && !split ? ",geglu" : "", split ? ",splitk" : p.persist ? ",persist" : p.conv ? ",conv" : "");
+           p.epi == 1 && !split ? ",geglu" : "", split ? ",splitk" : p.persist ? ",persist" : p.fold ? ",upfold" : p.conv ? ",conv" : "");
   static std::mutex mu;
   static std::set<std::string> names;  // (the returned pointer stays valid: set nodes do not move)
   std::lock_guard<std::mutex> lock(mu);
@@ -675,7 +709,7 @@ static int launch_plan(GemmArgs& a, const GemmPlan& p, hipStream_t s) {
     case kSkinny: return launch_skinny(a, s);
     case kGather: return launch_gather(a, s);
     case kP8: return launch_gemm_p8(a, p, s);
-    case kP8Conv: return launch_gemm_p8_conv(a, p, s);
+    case kP8Conv: return p.fold ? launch_gemm_p8_conv_folded(a, p, s) : launch_gemm_p8_conv(a, p, s);
     case kRing: break;
     default: return VST_ERR_ARG;
   }
@@ -922,12 +956,14 @@ extern "C" int vst_gemm_temporal_attention(const void* x, int ldx, const void* W
 
 // Name of the kernel a vst_gemm_ex / vst_conv3x3_ex call with these arguments launches (the
 // symbol rocprofv3 reports), so per-launch timings can be attributed to kernels.  kind: 0 linear,
-// 1 GEGLU linear, 2 vectorized conv, 3 scalar-gather conv.  Returns a static string.
+// 1 GEGLU linear, 2 vectorized conv, 3 scalar-gather conv, 4 folded upsample conv (M = its GEMM rows, four padded
+// classes; K = 4 C; tile and splits are not the caller's there).  Returns a static string.
 extern "C" const char* vst_gemm_kernel_name(int M, int N, int K, int kind, int tile, int splits, size_t ws_bytes) {
-  if (kind < 0 || kind > 3) return "";
+  if (kind < 0 || kind > 4) return "";
   GemmQuery q{};
   q.M = M, q.N = N, q.K = q.K1 = K, q.epi = kind == 1, q.no_epi = kind == 0, q.tile = tile, q.splits = splits;
-  q.slab_bytes = ws_bytes, q.conv = kind >= 2, q.vec = kind == 2, q.C1 = K / 9;
+  q.slab_bytes = ws_bytes, q.conv = kind >= 2, q.vec = kind == 2 || kind == 4, q.C1 = K / 9;
+  if (kind == 4) q.fold = true, q.C1 = K / 4, q.tile = 0, q.splits = 1;
   return plan_name(plan_gemm(q));
 }
 
@@ -1084,6 +1120,59 @@ extern "C" int vst_conv3x3_ex(const void* x1, int C1, const void* x2, int C2, in
                               int splits, void* workspace, size_t ws_bytes, void* stream) {
   return conv3x3_impl(x1, C1, x2, C2, nimg, H, W, stride, upsample, 0, Wt, Cout, bias, row_bias, row_bias_div,
                       ld_row_bias, R, ldr, out, ldc, tile, splits, workspace, ws_bytes, stream);
+}
+
+// ---- the nearest-2x upsample conv as four 2x2 convs on folded weights (gemm_common.h conv_row_folded) ----
+extern "C" int vst_fold_upsample_weight(const void* Wt, int Cout, int C, void* Wf, void* stream) {
+  if (!Wt || !Wf || Cout <= 0 || C <= 0) return VST_ERR_ARG;
+  if (C & 7) return VST_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(fold_upsample_weight_kernel, dim3(grid_for((size_t)16 * Cout * (C / 8))), dim3(256), 0,
+                     (hipStream_t)stream, (const bf16_t*)Wt, (bf16_t*)Wf, Cout, C);
+  return launch_status();
+}
+
+extern "C" int vst_conv3x3_up_folded(const void* x1, int ldx, int C1, const void* x2, int C2, int nimg, int H, int W,
+                                     const void* Wf, int ldwf, int Cout, const float* bias, const float* row_bias,
+                                     const void* R, void* out, int ldc, void* stream) {
+  Fit31 fit;
+  if (!x1 || !Wf || !out || nimg <= 0 || H <= 0 || W <= 0 || Cout <= 0 || C1 <= 0) return VST_ERR_ARG;
+  if (x2 || C2 || row_bias || R || (C1 & 63) || (Cout & 7)) return VST_ERR_UNSUPPORTED;
+  if ((ldx & 7) || ldx < C1 || (ldwf & 7) || ldwf < 4 * C1 || (ldc & 7) || ldc < Cout) return VST_ERR_ARG;
+  const size_t hw = (size_t)H * W;
+  {  // byte extents past the 32-bit buffer offsets: chunks of whole images, as conv3x3_impl (a row's k order, and so its
+     // bits, do not depend on nimg)
+    const size_t img_bytes = max(hw * ldx, 4 * hw * ldc) * 2;
+    if ((size_t)nimg * img_bytes > kMaxExtent) {
+      const int per = (int)(kMaxExtent / img_bytes);
+      if (per <= 0) return VST_ERR_ARG;
+      const int nch = (nimg + per - 1) / per, ipc = (nimg + nch - 1) / nch;
+      for (int i0 = 0; i0 < nimg; i0 += ipc) {
+        const int st = vst_conv3x3_up_folded((const char*)x1 + (size_t)i0 * hw * ldx * 2, ldx, C1, nullptr, 0,
+                                             min(ipc, nimg - i0), H, W, Wf, ldwf, Cout, bias, nullptr, nullptr,
+                                             (char*)out + (size_t)i0 * 4 * hw * ldc * 2, ldc, stream);
+        if (st != VST_OK) return st;
+      }
+      return VST_OK;
+    }
+  }
+  GemmArgs a{};
+  a.A1 = (const bf16_t*)x1; a.lda1 = ldx; a.C1 = C1;
+  a.H = H; a.W = W; a.OH = 2 * H; a.OW = 2 * W; a.stride = 1; a.up = 2;
+  a.up_live = nimg * H * W;
+  a.up_rows = (a.up_live + kFoldRowAlign - 1) / kFoldRowAlign * kFoldRowAlign;
+  a.K = a.K1 = 4 * C1;
+  a.M = 4 * a.up_rows; a.N = Cout;
+  a.Wt = (const bf16_t*)Wf; a.ldw = ldwf;
+  a.bias = bias; a.C = (bf16_t*)out; a.ldc = ldc;
+  a.a1_bytes = fit(((size_t)(a.up_live - 1) * ldx + C1) * 2);
+  a.w_bytes = fit(((size_t)(4 * Cout - 1) * ldwf + a.K) * 2);
+  if (fit.over) return VST_ERR_ARG;  // (x / out are chunked above; a weight past 2^31 - 1 bytes is refused)
+  GemmQuery q{};
+  q.M = a.M, q.N = a.N, q.K = q.K1 = a.K, q.splits = 1, q.c_bytes = (size_t)4 * a.up_live * ldc * 2;
+  q.conv = q.vec = q.fold = true, q.C1 = C1;
+  const GemmPlan plan = plan_gemm(q);
+  if (plan.family == kNone) return VST_ERR_ARG;
+  return launch_plan(a, plan, (hipStream_t)stream);
 }
 
 // 3x3 stride-2 conv with padding (0,1,0,1): diffusers Downsample2D(padding=0) = F.pad(x, (0, 1, 0, 1)) + conv(k3, s2,

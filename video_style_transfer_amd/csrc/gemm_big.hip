@@ -1,6 +1,6 @@
 // LDS-DMA ring GEMM: the main bf16 MFMA GEMM of the denoise path (projections, GEGLU FF,
 // implicit-GEMM conv3x3, split-K partials).  Operands: gemm_common.h (GemmArgs; template AMODE
-// 0 dense A, 1 conv A); epilogues: gemm_epilogue.h (EPI 0 / 1) and the fp32 split-K slab (EPI 2).
+// 0 dense A, 1 conv A, 2 the folded upsample conv: conv_row_folded); epilogues: gemm_epilogue.h (EPI 0 / 1) and the fp32 split-K slab (EPI 2).
 // Tiles (template): 256x256 and 256x128 (8 waves, 1 WG/CU), 128x128 and 128x64 (4 waves,
 // 2-3 WG/CU).
 //
@@ -131,6 +131,8 @@ __device__ __forceinline__ void ring_tile(const GemmArgs& p, char* smem, const i
     if (AMODE == 0) {
       rowA[q] = m < p.M ? m : -1;
       oyv[q] = oxv[q] = 0;
+    } else if (AMODE == 2) {
+      conv_row_folded(p, m, rowA[q], oyv[q], oxv[q]);
     } else {
       conv_row(p, m, rowA[q], oyv[q], oxv[q]);  // rowA: the image
     }
@@ -140,6 +142,7 @@ __device__ __forceinline__ void ring_tile(const GemmArgs& p, char* smem, const i
   for (int q = 0; q <= Cfg::B_PIECES; ++q) {
     const int n = n0 + 16 * (q * Cfg::NWAVES + wid) + prow;  // q == B_PIECES: the extra piece
     rowB[q] = n < p.N ? n : -1;
+    if (AMODE == 2 && n < p.N) rowB[q] = (m0 / p.up_rows) * p.N + n;  // the tile's class's weight panel
   }
   const bool has_bx = wid < Cfg::B_EXTRA, has_ax = wid < Cfg::A_EXTRA;  // wave-uniform
   const int n_extra = (has_bx ? 1 : 0) + (has_ax ? 1 : 0);
@@ -167,12 +170,21 @@ __device__ __forceinline__ void ring_tile(const GemmArgs& p, char* smem, const i
   }
   int c_tap = 0, c_ci = 0, run_ci0 = 0;  // conv cursor: next tile's tap and channel (of C1 + C2)
   bool rebase_due = true;
-  if (AMODE == 1) {
+  if (AMODE != 0) {
     const int k00 = kt0 * RBK;
     c_tap = k00 / Ctot;
     c_ci = k00 - c_tap * Ctot;
   }
   auto rebase = [&]() {
+    if constexpr (AMODE == 2) {  // tap (a, b) of the class's 2x2 conv; one source, pixel stride lda1
+#pragma unroll
+      for (int q = 0; q < AQ; ++q) {
+        int px;
+        const bool ok = conv_tap_pixel_folded(p, rowA[q], oyv[q], oxv[q], c_tap >> 1, c_tap & 1, px);
+        bA[q] = ok ? (uint32_t)(px * p.lda1 + lchunk * 8) * 2u : (uint32_t)kOOB;
+      }
+      return;
+    }
     const int ky = c_tap / 3, kx = c_tap - 3 * (c_tap / 3);
     const bool second = c_ci >= p.C1;
     const int cs = second ? p.C2 : p.C1;
@@ -408,7 +420,7 @@ __device__ __forceinline__ void ring_tile(const GemmArgs& p, char* smem, const i
     }
     return;
   } else {
-    tile_epilogue<Cfg, EPI>(p, smem, m0, n0, acc, wr, wc);
+    tile_epilogue<Cfg, EPI, false, AMODE == 2>(p, smem, m0, n0, acc, wr, wc);
   }
 }
 
@@ -490,15 +502,21 @@ static int dispatch_cfg(const GemmArgs& a, int amode, int epi, hipStream_t s, in
     }
     return launch_ring_t<Cfg, 0, 2>(a, s, splits);
   }
+  if (amode == 2) {  // folded upsample conv: plain epilogue, no split-K, tiles that divide the class padding
+    if constexpr (kFoldRowAlign % Cfg::BM == 0) {
+      if (epi == 0 && splits == 1) return launch_ring_t<Cfg, 2, 0>(a, s, 1);
+    }
+    return VST_ERR_ARG;
+  }
   if (epi == 0) return launch_ring_t<Cfg, 1, 0>(a, s, splits);
   if (epi == 2) return launch_ring_t<Cfg, 1, 2>(a, s, splits);
   return VST_ERR_ARG;
 }
 
-// The plan's tile with its A loader (dense / 3x3 conv) and epilogue: 0 plain, 1 GEGLU, 2 fp32 slab (always when the
+// The plan's tile with its A loader (dense / 3x3 conv / folded upsample conv) and epilogue: 0 plain, 1 GEGLU, 2 fp32 slab (always when the
 // plan splits K), 3 bias + GELU
 int launch_gemm_ring(const GemmArgs& a, const GemmPlan& p, hipStream_t s) {
-  const int amode = p.conv ? 1 : 0, epi = p.splits > 1 ? 2 : p.epi, splits = p.splits;
+  const int amode = p.fold ? 2 : p.conv ? 1 : 0, epi = p.splits > 1 ? 2 : p.epi, splits = p.splits;
   switch (p.bm * 1000 + p.bn) {
     case 128128: return dispatch_cfg<Cfg128x128>(a, amode, epi, s, splits);
     case 128064: return epi == 1 ? VST_ERR_ARG : dispatch_cfg<Cfg128x64>(a, amode, epi, s, splits);

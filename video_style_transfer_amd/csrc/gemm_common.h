@@ -9,6 +9,7 @@
 //   conv A: implicit-GEMM 3x3 conv over NHWC activations (per-frame SDXL conv, diffusers ResnetBlock2D /
 //     Downsample2D / Upsample2D): K = (ky, kx, ci), zero padding through out-of-range buffer loads, stride 1 / 2,
 //     fused nearest-2x upsample, two-source channel concat (up-block skip connections); conv_row / conv_tap_pixel.
+//     The upsample conv also as four 2x2 convs on folded weights (K = (a, b, ci), 4/9 of the work): conv_row_folded.
 // The epilogues and their rounding points: gemm_epilogue.h.
 #pragma once
 #include "vst_common.h"
@@ -59,6 +60,9 @@ struct GemmArgs {
   // (p.C / p.ldc) is written in (clip, frame, pixel) rows
   int ta_hw, ta_heads, ta_d;
   float ta_scale_log2;
+  // folded upsample conv (up == 2, conv_row_folded below): rows per output-parity class, live (nimg * H * W) and padded
+  // to the tallest tile (M = 4 * up_rows); lda1 is then the input's pixel stride.  Last members: no other field moves
+  int up_live, up_rows;
 };
 
 __device__ __forceinline__ int swz(int row, int chunk) {
@@ -95,6 +99,47 @@ __device__ __forceinline__ bool conv_tap_pixel(const GemmArgs& p, const int img,
   }
   px = (img * p.H + iy) * p.W + ix;
   return ok;
+}
+
+// Folded nearest-2x upsample conv (up == 2; the loaders and epilogues compile it in by a template flag).  In the
+// upsampled image every input pixel appears four times, so the nine taps of an output pixel of parity (py, px) read
+// only 2x2 distinct input pixels: the conv is four 2x2 convs, one per parity class c = 2 py + px, on weights summed
+// over the coinciding taps (fold_upsample_weight_kernel: Wf [4][Cout][2][2][C]).  K = (tap (a, b), channel) = 4 C.
+// GEMM rows are class-major: m = c * up_rows + r, r = (img * H + y) * W + x on the INPUT grid, r < up_live; up_rows is
+// up_live rounded up to the tallest tile (kFoldRowAlign), so a tile lies in one class and uses that class's weight
+// panel (rows c * N + n of Wf).  Rows of the padding are dead: they load zeros and store nothing.
+//   tap (a, b) of class (py, px) reads input pixel (y + py + a - 1, x + px + b - 1), zero outside the image: with
+//   uy = 2y + py + ky - 1 the upsampled-image test 0 <= uy < 2H is the same as 0 <= (uy >> 1) < H, and uy >> 1 is
+//   y + py + a - 1 for the ky of S(py, a) (S(0,0) = {0}, S(0,1) = {1,2}, S(1,0) = {0,1}, S(1,1) = {2});
+//   output row (img * 2H + 2y + py) * 2W + 2x + px.
+constexpr int kFoldRowAlign = 256;
+
+// m -> (img, oy, ox) = (img, y + py, x + px): tap (a, b) then reads (oy + a - 1, ox + b - 1); img = -1 for a dead row
+__device__ __forceinline__ void conv_row_folded(const GemmArgs& p, const int m, int& img, int& oy, int& ox) {
+  const int cls = m / p.up_rows, r = m - cls * p.up_rows;
+  const int hw = p.H * p.W;
+  const int im = r / hw, rem = r - im * hw;
+  const int y = rem / p.W;
+  img = (r < p.up_live && m < p.M) ? im : -1;
+  oy = y + (cls >> 1);
+  ox = rem - y * p.W + (cls & 1);
+}
+
+__device__ __forceinline__ bool conv_tap_pixel_folded(const GemmArgs& p, const int img, const int oy, const int ox,
+                                                      const int a, const int b, int& px) {
+  const int iy = oy + a - 1, ix = ox + b - 1;
+  px = (img * p.H + iy) * p.W + ix;
+  return img >= 0 && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
+}
+
+// GEMM row m -> row of the [nimg, 2H, 2W] output; -1 for a dead row
+__device__ __forceinline__ int conv_out_row_folded(const GemmArgs& p, const int m) {
+  const int cls = m / p.up_rows, r = m - cls * p.up_rows;
+  if (r >= p.up_live) return -1;
+  const int hw = p.H * p.W;
+  const int img = r / hw, rem = r - img * hw;
+  const int y = rem / p.W, x = rem - y * p.W;
+  return (img * 2 * p.H + 2 * y + (cls >> 1)) * 2 * p.W + 2 * x + (cls & 1);
 }
 
 }  // namespace vst

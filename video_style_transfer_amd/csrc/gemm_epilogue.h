@@ -26,10 +26,13 @@ __device__ __forceinline__ int p8_acc_row(const int i, const int wc) {
   }
 }
 
-template <class Cfg, int EPI, bool ROT = false>
+// FOLD (the folded upsample conv, EPI 0 without row bias / residual): tile row m is stored at conv_out_row_folded(m),
+// dead rows nowhere; the identity for every other mode.
+template <class Cfg, int EPI, bool ROT = false, bool FOLD = false>
 __device__ __forceinline__ void tile_epilogue(const GemmArgs& p, char* smem, const int m0, const int n0,
                                               f32x4 (&acc)[Cfg::MI][Cfg::NJ], const int wr, const int wc,
                                               const int tid = threadIdx.x) {
+  static_assert(!FOLD || EPI == 0, "folded conv rows: plain epilogue");
   constexpr int BM = Cfg::BM, BN = Cfg::BN;
   const int lane = tid & 63;
   const int fr = lane & 15, fq = lane >> 4;
@@ -51,7 +54,7 @@ __device__ __forceinline__ void tile_epilogue(const GemmArgs& p, char* smem, con
   // residual chunks are fetched first (the fragment registers are dead now): their HBM latency
   // overlaps the bias add and the LDS staging below instead of stalling the store pass.
   u32x4 res[EPI == 0 ? ITEMS : 1];
-  if (EPI == 0 && p.R) {
+  if (!FOLD && EPI == 0 && p.R) {
 #pragma unroll
     for (int k = 0; k < ITEMS; ++k) {
       int row, cc;
@@ -142,12 +145,17 @@ __device__ __forceinline__ void tile_epilogue(const GemmArgs& p, char* smem, con
     for (int k = 0; k < ITEMS; ++k) {
       int row, cc;
       const bool ok = item(k, row, cc);
-      const int m = m0 + row, n = n0 + cc * 8;
+      int m = m0 + row;
+      const int n = n0 + cc * 8;
       const int nv = min(8, p.N - n);
       if (!ok || m >= p.M || nv <= 0) continue;
+      if constexpr (FOLD) {
+        m = conv_out_row_folded(p, m);
+        if (m < 0) continue;
+      }
       float v[8];
       unpack8(*reinterpret_cast<const u32x4*>(smem + row * LROW + cc * 16), v);
-      if (EPI == 0 && p.rbias) {
+      if (!FOLD && EPI == 0 && p.rbias) {
         const float* rb = p.rbias + (size_t)(m / p.rbias_div) * p.ldrb + n;
         if (nv == 8) {
           const f32x4 r0 = *reinterpret_cast<const f32x4*>(rb);
@@ -159,7 +167,7 @@ __device__ __forceinline__ void tile_epilogue(const GemmArgs& p, char* smem, con
         }
       }
       if (nv == 8) {
-        if (EPI == 0 && p.R) {
+        if (!FOLD && EPI == 0 && p.R) {
           float r8[8];
           unpack8(res[k], r8);
 #pragma unroll
@@ -169,7 +177,7 @@ __device__ __forceinline__ void tile_epilogue(const GemmArgs& p, char* smem, con
       } else {
         for (int e = 0; e < nv; ++e) {
           float x = v[e];
-          if (EPI == 0 && p.R) x += bf2f(p.R[(size_t)m * p.ldr + n + e]);
+          if (!FOLD && EPI == 0 && p.R) x += bf2f(p.R[(size_t)m * p.ldr + n + e]);
           p.C[(size_t)m * p.ldc + n + e] = f2bf(x);
         }
       }

@@ -584,11 +584,16 @@ __device__ __forceinline__ void tattn_epilogue(const GemmArgs& p, char* smem, co
 // known to be younger), which there also covers the next tile's first k-tiles, issued one to two k-tiles earlier.  An
 // extra load in flight only makes the loop's counted waits stricter.  Compiled in with `if constexpr`: the ungated
 // instantiations are the code they were.
-template <int EPI, int BN, bool LORA = false, int BM = 256, bool CONV = false, bool PERSIST = false, bool GATE = false>
+// FOLD (CONV only; vst_conv3x3_up_folded): the nearest-2x upsample conv as four 2x2 convs on folded weights
+// (gemm_common.h conv_row_folded): four taps, one source, class-major rows, the tile's weight panel that of its
+// class, the output rows through conv_out_row_folded.  A template flag, so the 3x3 instantiations are the code they were.
+template <int EPI, int BN, bool LORA = false, int BM = 256, bool CONV = false, bool PERSIST = false, bool GATE = false,
+          bool FOLD = false>
 __global__ __launch_bounds__(512, 1) void gemm_p8_kernel(GemmArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   using Cfg = P8Cfg<BN, BM>;
   static_assert(!CONV || (!LORA && EPI == 0), "conv: plain epilogue");
+  static_assert(!FOLD || (CONV && kFoldRowAlign % BM == 0), "folded upsample: a conv whose tiles stay inside one class");
   static_assert(EPI != 1 || BN == 256, "GEGLU needs 64-column [hidden | gate] blocks");
   static_assert(!LORA || EPI != 1, "in-GEMM LoRA: linear epilogue");
   static_assert(!GATE || LORA, "the gate scales the in-GEMM LoRA's u");
@@ -682,7 +687,10 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_kernel(GemmArgs p) {
         c8[s][pc] = c * 8;
         if (s < 2) {
           const int m = m0 + (r / HALF) * Cfg::WM + s * HALF + (r % HALF);
-          if constexpr (CONV) {
+          if constexpr (FOLD) {
+            if (pc < NPA) conv_row_folded(p, m, cv_img[s][pc], cv_oy[s][pc], cv_ox[s][pc]);
+            base1[s][pc] = base2[s][pc] = (uint32_t)kOOB;
+          } else if constexpr (CONV) {
             if (pc < NPA) {  // conv_row (gemm_common.h), but oy / ox left unmasked past M: the measured code
               const int hw = p.OH * p.OW;
               const int img = m / hw, rem = m - img * hw;
@@ -704,12 +712,23 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_kernel(GemmArgs p) {
         } else {
           const int rb = s == 2 ? 32 : RB1;
           const int n = n0 + (r / rb) * Cfg::WN + (s - 2) * 32 + (r % rb);
-          base1[s][pc] = (n < p.N && (s == 2 ? pc < 2 : pc < NPB1)) ? (uint32_t)(n * p.ldw + c * 8) * 2u : (uint32_t)kOOB;
+          const int wrow = FOLD ? (m0 / p.up_rows) * p.N + n : n;  // FOLD: the tile's class's weight panel
+          base1[s][pc] = (n < p.N && (s == 2 ? pc < 2 : pc < NPB1)) ? (uint32_t)(wrow * p.ldw + c * 8) * 2u : (uint32_t)kOOB;
         }
       }
   };
   // CONV: A slot s's pieces for its next k-tile (the slot's cursor); live = false issues zeros (counts stay uniform)
   auto conv_rebase = [&](int s) {
+    if constexpr (FOLD) {  // tap (a, b) of the class's 2x2 conv; one source, pixel stride lda1
+#pragma unroll
+      for (int pc = 0; pc < NPA; ++pc) {
+        int px;
+        const bool ok = conv_tap_pixel_folded(p, cv_img[s][pc], cv_oy[s][pc], cv_ox[s][pc], cv_tap[s] >> 1, cv_tap[s] & 1, px);
+        base1[s][pc] = ok ? (uint32_t)(px * p.lda1 + c8[s][pc]) * 2u : (uint32_t)kOOB;
+      }
+      cv_rebase[s] = false;
+      return;
+    }
     const int ky = cv_tap[s] / 3, kx = cv_tap[s] - 3 * (cv_tap[s] / 3);
     cv_second[s] = cv_ci[s] >= p.C1;
     const int cs = cv_second[s] ? p.C2 : p.C1;
@@ -1099,7 +1118,7 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_kernel(GemmArgs p) {
 #else
   if constexpr (EPI == 4) xattn_epilogue<Cfg, LORA>(p, smem, m0, n0, acc, wr, wc);
   else if constexpr (EPI == 5) tattn_epilogue<Cfg>(p, smem, m0, n0, acc, wr, wc);
-  else tile_epilogue<Cfg, EPI, LORA>(p, smem, m0, n0, acc, wr, wc);
+  else tile_epilogue<Cfg, EPI, LORA, FOLD>(p, smem, m0, n0, acc, wr, wc);
 #endif
 #ifdef VST_P8_TRACE
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1110,18 +1129,18 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_kernel(GemmArgs p) {
 
 // One workgroup per tile: every conv, cross- and temporal-attention launch, and the shapes the persistent grid does not
 // take (p8_persist_applies).
-template <int EPI, int BN, bool LORA, int BM, bool CONV = false, bool GATE = false>
+template <int EPI, int BN, bool LORA, int BM, bool CONV = false, bool GATE = false, bool FOLD = false>
 static int launch_p8_tile_per_wg(const GemmArgs& a, hipStream_t s) {
   static bool attr = false;
   using Cfg = P8Cfg<BN, BM>;
   constexpr int lds = EPI == 4 ? 160 * 1024 : (LORA ? Cfg::LDS_LORA : Cfg::LDS);
   if (!attr) {
-    (void)hipFuncSetAttribute((const void*)gemm_p8_kernel<EPI, BN, LORA, BM, CONV, false, GATE>,
+    (void)hipFuncSetAttribute((const void*)gemm_p8_kernel<EPI, BN, LORA, BM, CONV, false, GATE, FOLD>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     attr = true;
   }
   const int nwg = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
-  hipLaunchKernelGGL((gemm_p8_kernel<EPI, BN, LORA, BM, CONV, false, GATE>), dim3(nwg), dim3(512), lds, s, a);
+  hipLaunchKernelGGL((gemm_p8_kernel<EPI, BN, LORA, BM, CONV, false, GATE, FOLD>), dim3(nwg), dim3(512), lds, s, a);
   return launch_status();
 }
 
@@ -1190,6 +1209,19 @@ int launch_gemm_p8_conv(const GemmArgs& a, const GemmPlan& p, hipStream_t s) {
     case 256: return launch_p8_tile_per_wg<0, 256, false, 256, true>(a, s);
     case 192: return launch_p8_tile_per_wg<0, 192, false, 256, true>(a, s);
     case 320: return launch_p8_tile_per_wg<0, 320, false, 128, true>(a, s);
+    default: return VST_ERR_ARG;
+  }
+}
+
+// folded nearest-2x upsample conv (a.up == 2: K = 4 C1, one source, M = 4 up_rows, W = Wf [4 N][K]; bias only)
+int launch_gemm_p8_conv_folded(const GemmArgs& a, const GemmPlan& p, hipStream_t s) {
+  if ((a.C1 & 63) || a.C2 || a.A2 || a.K != 4 * a.C1 || a.up != 2 || a.up_rows % kFoldRowAlign || a.M != 4 * a.up_rows ||
+      a.R || a.rbias)
+    return VST_ERR_ARG;
+  switch (p.bn) {
+    case 256: return launch_p8_tile_per_wg<0, 256, false, 256, true, false, true>(a, s);
+    case 192: return launch_p8_tile_per_wg<0, 192, false, 256, true, false, true>(a, s);
+    case 320: return launch_p8_tile_per_wg<0, 320, false, 128, true, false, true>(a, s);
     default: return VST_ERR_ARG;
   }
 }

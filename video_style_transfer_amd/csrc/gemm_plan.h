@@ -23,6 +23,7 @@ struct GemmPlan {
   int epi;       // 0 bias / row bias / residual, 1 GEGLU, 2 fp32 slab (vst_gemm_f32out), 3 bias + GELU
   bool conv;     // 3x3 conv (A loader of the ring / 8-phase kernel)
   bool persist;  // 8-phase: the persistent grid (p8_persist_applies)
+  bool fold;     // conv: the folded nearest-2x upsample conv (vst_conv3x3_up_folded; GemmArgs::up == 2)
 };
 
 // Every runtime switch of the GEMM dispatch (DESIGN.md §9 lists them), read once per process; vst_p8_force_bn,
@@ -53,6 +54,7 @@ int launch_gemm_ring(const GemmArgs& a, const GemmPlan& p, hipStream_t s);
 // gemm_p8.hip: tile width, epilogue and persist come from the plan; the fused entry points pass theirs
 int launch_gemm_p8(const GemmArgs& a, const GemmPlan& p, hipStream_t s);
 int launch_gemm_p8_conv(const GemmArgs& a, const GemmPlan& p, hipStream_t s);
+int launch_gemm_p8_conv_folded(const GemmArgs& a, const GemmPlan& p, hipStream_t s);
 int launch_gemm_p8_lora(const GemmArgs& a, int bn, bool persist, hipStream_t s);
 int launch_gemm_p8_tattn(const GemmArgs& a, hipStream_t s);
 int launch_gemm_p8_xattn(const GemmArgs& a, hipStream_t s);

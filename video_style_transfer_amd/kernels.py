@@ -585,6 +585,57 @@ def conv3x3(x1: torch.Tensor, nimg: int, H: int, W: int, w: torch.Tensor, bias: 
     return out
 
 
+FOLD_ROW_ALIGN = 256  # rows of one output-parity class are padded to this in the folded conv's GEMM (kFoldRowAlign)
+
+
+def fold_upsample_weight(w: torch.Tensor) -> torch.Tensor:
+    """The 3x3 kernel weight [Cout, 9C] (ky, kx, ci) folded for conv3x3_up_folded: [4*Cout, 4C], rows (class 2 py + px,
+    co), columns (a, b, ci), each the fp32 sum of the taps that coincide in the nearest-2x upsampled image, rounded
+    once to bf16 (vst_fold_upsample_weight)."""
+    fn = "fold_upsample_weight"
+    _block(w, BF16, "w", fn)
+    if w.dim() != 2 or w.shape[1] % 72:
+        _fail(fn, "w", f"must be [Cout, 9C] with C % 8 == 0, got {tuple(w.shape)}")
+    Cout, C = w.shape[0], w.shape[1] // 9
+    wf = torch.empty((4 * Cout, 4 * C), dtype=BF16, device=w.device)
+    with _Rec("fold_upsample_weight", 7.0 * Cout * 4 * C, 2.0 * (9 + 16) * Cout * C, lambda: "fold_upsample_weight",
+              (4 * Cout, 4 * C, 1)):
+        _lib.call("vst_fold_upsample_weight", _p(w), Cout, C, _p(wf), _stream())
+    return wf
+
+
+def conv3x3_up_folded_applies(C: int, Cout: int) -> bool:
+    """Shapes vst_conv3x3_up_folded takes (a shape-only answer: never the number of images)."""
+    return C % 64 == 0 and Cout % 8 == 0
+
+
+def conv3x3_up_folded(x: torch.Tensor, nimg: int, H: int, W: int, wf: torch.Tensor, bias: torch.Tensor | None, *,
+                      out: torch.Tensor | None = None) -> torch.Tensor:
+    """NHWC nearest-2x upsample + 3x3 conv (pad 1) as four 2x2 convs on the folded weight wf = fold_upsample_weight(w).
+    x: [nimg*H*W, C] row view, C % 64 == 0.  Returns [nimg*2H*2W, Cout]; equal to conv3x3(upsample=True) up to the one
+    rounding of the folded weights, at 4/9 of its multiply-adds."""
+    fn = "conv3x3_up_folded"
+    _view(x, BF16, "x", fn, rows=nimg * H * W)
+    _view(wf, BF16, "wf", fn)
+    C = x.shape[1]
+    if wf.shape[0] % 4 or wf.shape[1] != 4 * C:
+        _fail(fn, "wf", f"shape {tuple(wf.shape)}: expected [4*Cout, 4*C] with C = {C}")
+    Cout = wf.shape[0] // 4
+    if not conv3x3_up_folded_applies(C, Cout):
+        raise _lib.VstError(f"conv3x3_up_folded: C={C} Cout={Cout} (needs C % 64 == 0, Cout % 8 == 0)")
+    M = nimg * 4 * H * W
+    out = _new(out, (M, Cout), x, "out", fn)
+    if bias is not None:
+        _vec(bias, Cout, "bias", fn)
+    # the executed work: four padded classes of nimg*H*W rows, K = 4C
+    rows = (nimg * H * W + FOLD_ROW_ALIGN - 1) // FOLD_ROW_ALIGN * FOLD_ROW_ALIGN
+    with _Rec("conv3x3", 2.0 * M * Cout * 4 * C, 2.0 * (nimg * H * W * C + 4 * Cout * 4 * C + M * Cout),
+              lambda: gemm_kernel_name(4 * rows, Cout, 4 * C, 4), (M, Cout, 4 * C)):
+        _lib.call("vst_conv3x3_up_folded", _p(x), _ld(x), C, None, 0, nimg, H, W, _p(wf), _ld(wf), Cout, _p(bias),
+                  None, None, _p(out), _ld(out), _stream())
+    return out
+
+
 def spatial_attention(q, k, v, nbatch, heads, Nq, Nk, kv_div=1, out=None, scale=None, lse=None):
     """q: [nbatch*Nq, >=heads*64] view; k/v: [nbatch/kv_div*Nk, >=heads*64] views.  lse: optional fp32
     [nbatch*heads*Nq] output of the log2-domain logsumexp per query (the training backward recomputes P from it)."""

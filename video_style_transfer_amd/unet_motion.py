@@ -95,7 +95,24 @@ class Conv3x3(nn.Conv2d):
             self.__dict__["_vst_w"] = c
         return c[1]
 
+    def folded_weight(self):
+        """kernel_weight() folded for the upsample conv (K.fold_upsample_weight), cached per weight version like it.  A
+        weight that trains is re-folded on every call (GEGLU.geglu_ops: graph replay updates it without a version
+        bump); a frozen one is folded once, at the first eager call."""
+        if self.weight.requires_grad:
+            return K.fold_upsample_weight(self.kernel_weight())
+        key = (self.weight.data_ptr(), self.weight._version)
+        c = self.__dict__.get("_vst_wfold")
+        if c is None or c[0] != key:
+            c = (key, K.fold_upsample_weight(self.kernel_weight()))
+            self.__dict__["_vst_wfold"] = c
+        return c[1]
+
     def run(self, x1, nimg, H, W, *, x2=None, upsample=False, row_bias=None, row_bias_div=1, residual=None):
+        # the upsample conv as four 2x2 convs on folded weights wherever the shape allows (never a question of nimg)
+        if (upsample and x2 is None and row_bias is None and residual is None and self.stride[0] == 1
+                and K.conv3x3_up_folded_applies(self.in_channels, self.out_channels)):
+            return K.conv3x3_up_folded(x1, nimg, H, W, self.folded_weight(), f32(self.bias))
         return K.conv3x3(x1, nimg, H, W, self.kernel_weight(), f32(self.bias), x2=x2, stride=self.stride[0],
                          upsample=upsample, row_bias=row_bias, row_bias_div=row_bias_div, residual=residual)
 
