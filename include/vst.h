@@ -232,6 +232,25 @@ int vst_spatial_attention_frames(const void* q, int ldq, const void* k, const vo
 int vst_frame_adain(void* x, int ldx, int nclip, int F, int N, int C, int anchor, float eps, float* stats,
                     void* stream);
 
+/* IP-Adapter image attention, added in place onto the attn2 output O ahead of to_out: replaces
+ * to_k_ip / to_v_ip, the second F.scaled_dot_product_attention and `hidden_states + self.scale * ip_hidden_states` of
+ * IPAdapterAttnProcessor2_0 (unziplora_unet/unzip_attention_processor.py:1793-1809) without a q tensor.  The image keys
+ * are folded into the query projection on the host: per row m (frame m / Nq, token batch b = frame / kv_div), head h,
+ *   s[t] = scale * (x[m] . G[(b*heads + h)*16 + t] + gbias[(b*heads + h)*16 + t]),  t < T,
+ *   p = softmax(s),  a = bf16(sum_t bf16(p_t) V[b*16 + t][64h ..] / l)  (P unnormalised in bf16, 1/l at the end),
+ *   O[m][64h ..] = bf16(float(O) + (layer_scale * row_scale[m / Nq]) * float(a)).
+ * x: bf16 [M, K]; G: bf16, 16 rows of K columns per (b, h), row stride ldg; gbias: fp32 [nbatch*heads*16] or NULL;
+ * V: bf16, 16 rows of 64*heads columns per b, row stride ldv; row_scale: fp32 [M / Nq] or NULL (= 1); O: bf16
+ * [M, 64*heads].  Head size 64, 1 <= T <= 16.  Rows t >= T of G, gbias and V never reach the result, whatever they
+ * hold.  A frame whose scale product is exactly 0 is not written at all.  No atomics, no workspace; every sum runs in
+ * an order fixed by (K, heads, T), and a row's bits do not depend on M.  Returns 1 before any launch for a NULL
+ * required pointer, a non-positive size, T > 16, K % 64, M % Nq, (M/Nq - 1)/kv_div >= nbatch, a stride that is no
+ * multiple of 8 or too short, a base that is not 16-byte aligned (row_scale: 4), or byte extents past 2^31 - 1; 3 for
+ * more than 20 heads (the kernel's LDS plan). */
+int vst_ip_attention_add(const void* x, int ldx, int K, const void* G, int ldg, const float* gbias, const void* V,
+                         int ldv, int nbatch, int M, int Nq, int heads, int T, int kv_div, float scale,
+                         float layer_scale, const float* row_scale, void* O, int ldo, void* stream);
+
 /* Frame-axis attention (motion module / TemporalTransformerBlock, animatediff/temporal_transformer.py:66-68):
  * token (clip b, frame f, pixel p) at row (b*F + f)*HW + p; F <= 32; head_dim in {8,16,32,40,64,80,160}. */
 int vst_temporal_attention(const void* q, const void* k, const void* v, int ldqkv, void* o, int ldo, int nclip,

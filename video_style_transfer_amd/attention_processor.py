@@ -57,6 +57,9 @@ class Attention(nn.Module):
             AttnProcessor2_0() if temporal else AnimateDiffAttnProcessor2_0())
 
     def set_processor(self, processor):
+        # (a processor that is an nn.Module, ip_adapter's, registers as a child; a plain one replacing it must not)
+        if "processor" in self._modules and not isinstance(processor, nn.Module):
+            del self._modules["processor"]
         self.processor = processor
 
     def get_processor(self):
@@ -99,6 +102,7 @@ class AnimateDiffAttnProcessor2_0:
         lora_u = kwargs.pop("_vst_lora_u", None)  # x @ Acat^T of the q(/k/v) ops, from K.layer_norm_lora
         cross_frame = kwargs.pop("_vst_cross_frame", None)  # attn1 only: (CrossFrameAttention, frames per clip)
         gate = kwargs.pop("_vst_lora_gate", None)  # lora_gate.LoraGate, one row per image of the batch
+        image_prompt = kwargs.pop("_vst_image_prompt", None)  # attn2 only: ip_adapter.ImagePrompt
         if gate is not None and gate.rows != hidden_states.shape[0]:
             raise K._lib.VstError(f"LoRA gate: {gate.rows} rows for a batch of {hidden_states.shape[0]} images")
         if attn.spatial_norm is not None or attn.group_norm is not None or attn.norm_cross:
@@ -152,12 +156,20 @@ class AnimateDiffAttnProcessor2_0:
                 q = run_ops(x, q_ops, u=lora_u, gate=gate)
                 o = K.spatial_attention(q, kv[:, :inner], kv[:, inner:], batch, heads, N, L, kv_div,
                                         scale=hd ** -0.5)
+            o = self._image_attention(attn, x, o, q_ops, batch, N, image_prompt, gate)
         res2d = None if fused_residual is None else fused_residual.reshape(batch * N, -1)
         out = run_ops(o, build_ops([attn.to_out[0]], s), residual=res2d, gate=gate)
         out = out.view(batch, N, -1)
         if input_ndim == 4:
             out = out.transpose(-1, -2).reshape(b4, c4, h4, w4)
         return _finish(attn, out, hidden_states)
+
+    def _image_attention(self, attn, x, o, q_ops, batch, N, image_prompt, gate):
+        """What a processor adds to the text attention's output o ahead of to_out (ip_adapter's processor: the image
+        attention); here nothing, and an image prompt has no projections to go through."""
+        if image_prompt is not None:
+            raise K._lib.VstError("image_prompt: this attention has no IP-Adapter processor (load_ip_adapter)")
+        return o
 
 
 def _cross_fusable(ops, M: int, Nq: int, Nk: int) -> bool:

@@ -647,6 +647,8 @@ def unet_train_tokens(unet, x, B: int, F: int, h: int, w: int, emb_silu, enc2d, 
     enc2d: [B*L, D] text states (constant)."""
     refuse_context(temporal_context, F)
     refuse_freeu(unet, freeu)
+    from .ip_adapter import refuse_training  # (local import: ip_adapter imports the attention processors)
+    refuse_training(unet)
     temb = unet.batched_temb(emb_silu)
     nimg = B * F
     H, W = h, w

@@ -739,6 +739,59 @@ def frame_adain(x, nclip, F, N, anchor, eps=1e-5, stats=None):
     return stats
 
 
+def ip_attention_add(x, G, gbias, V, out, *, Nq, heads, T, kv_div=1, scale=0.125, layer_scale=1.0, row_scale=None):
+    """IP-Adapter image attention added in place onto the attn2 output (vst_ip_attention_add).
+    x [M, K] bf16: the hidden states attn2's to_q reads; G [nbatch*heads*16, K] bf16: the image keys folded into the
+    query projection, 16 rows per (token batch, head) of which the first T count; gbias fp32 [nbatch*heads*16] or None:
+    their product with to_q's bias; V [nbatch*16, 64*heads] bf16: the image values, 16 rows per token batch; out
+    [M, 64*heads] bf16: the text attention's output, updated as
+    out + layer_scale * row_scale[m // Nq] * softmax_t(scale * (x . G + gbias)) V.  Frame f = m // Nq reads token batch
+    f // kv_div; row_scale fp32 [M // Nq] or None (= 1): a frame whose product with layer_scale is 0 is not written."""
+    fn = "ip_attention_add"
+    Nq, heads, T, kv_div = int(Nq), int(heads), int(T), int(kv_div)
+    if Nq < 1 or heads < 1 or kv_div < 1:
+        _fail(fn, "Nq, heads, kv_div", f"= {Nq}, {heads}, {kv_div}: expected positive counts")
+    if not 1 <= T <= 16:
+        _fail(fn, "T", f"= {T}: the kernel holds 1 to 16 image tokens")
+    _view(x, BF16, "x", fn)
+    M, K = x.shape
+    if M == 0 or K == 0 or K % 64 or _ld(x) % 8 or x.data_ptr() % 16:
+        _fail(fn, "x", f"needs rows, a multiple of 64 columns, a row stride that is a multiple of 8 and a 16-byte "
+                       f"aligned base, got shape {tuple(x.shape)} stride {x.stride()}")
+    if M % Nq:
+        _fail(fn, "x", f"has {M} rows: not a multiple of Nq = {Nq}")
+    nbatch = (M // Nq - 1) // kv_div + 1
+    inner = 64 * heads
+
+    def aligned(t, name):
+        if _ld(t) % 8 or t.data_ptr() % 16:
+            _fail(fn, name, f"needs a row stride that is a multiple of 8 and a 16-byte aligned base, got stride "
+                            f"{t.stride()}")
+    _view(G, BF16, "G", fn, min_cols=K)
+    if G.shape[1] != K or G.shape[0] % (heads * 16) or G.shape[0] < nbatch * heads * 16:
+        _fail(fn, "G", f"shape {tuple(G.shape)}: expected 16 rows of {K} columns per (token batch, head), "
+                       f">= {nbatch} x {heads} of them")
+    aligned(G, "G")
+    nb = G.shape[0] // (heads * 16)
+    _view(V, BF16, "V", fn, shape=(nb * 16, inner))
+    aligned(V, "V")
+    _view(out, BF16, "out", fn, shape=(M, inner))
+    aligned(out, "out")
+    if gbias is not None:
+        _vec(gbias, nb * heads * 16, "gbias", fn)
+        if gbias.data_ptr() % 16:
+            _fail(fn, "gbias", "needs a 16-byte aligned base")
+    if row_scale is not None:
+        _vec(row_scale, M // Nq, "row_scale", fn)
+    # scores 2 M heads 16 K, P.V 2 M heads 16 64 (the MFMAs run all 16 key rows); x once, O read and written, G, V
+    flops = 2.0 * M * heads * 16 * (K + 64)
+    nbytes = 2.0 * (M * K + 2 * M * inner + nb * heads * T * K + nb * T * inner)
+    with _Rec("ip_attention_add", flops, nbytes, lambda: "ip_attention_add_kernel", (M, inner, K)):
+        _lib.call("vst_ip_attention_add", _p(x), _ld(x), K, _p(G), _ld(G), _p(gbias), _p(V), _ld(V), nb, M, Nq, heads,
+                  T, kv_div, float(scale), float(layer_scale), _p(row_scale), _p(out), _ld(out), _stream())
+    return out
+
+
 def temporal_attention(q, k, v, nclip, F, HW, heads, head_dim, out=None, scale=None):
     """Frame-axis attention; rows (b*F + f)*HW + p.  q/k/v views share one row stride."""
     fn = "temporal_attention"

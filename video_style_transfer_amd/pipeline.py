@@ -28,6 +28,7 @@ import torch
 from . import kernels as K
 from .attention_processor import refresh_text_kv
 from .freeu import FreeU, as_freeu, check_freeu_arg
+from .ip_adapter import ImagePrompt, check_forward, refresh_image_kv
 from .lora_gate import LoraGate
 from .scheduler import (SAMPLERS, STOCHASTIC_SAMPLERS, EulerDiscreteScheduler, check_eta, sampler_coefficients,
                         start_index)
@@ -142,6 +143,8 @@ class AnimateDiffDenoiser:
         self.masked = False
         # per-frame content / style strength (set_lora_gates): None = the plain step
         self.lora_gate = None
+        # IP-Adapter image prompt (set_image_prompt): None = the plain step
+        self.image_prompt = None
         # table-driven sampler step: the previous step's denoised estimate, the (a, b, c) rows, the
         # per-clip rescale factor and its workspace; allocated here once, a captured step holds their pointers.  A
         # stochastic sampler (§16) has (a, b, c, d) rows and the seed of its noise, rewritten in place.
@@ -185,7 +188,7 @@ class AnimateDiffDenoiser:
         emb = self.unet.embed(self.timesteps, self.pooled, self.time_ids, B, step_idx=self.step_idx)
         noise = self.unet.forward_tokens(self.x, B, self.F, self.h, self.w, emb, self.enc, shard=self.shard,
                                          temporal_context=self.context, cross_frame=self.cross_frame,
-                                         lora_gate=self.lora_gate, freeu=self.freeu)
+                                         lora_gate=self.lora_gate, freeu=self.freeu, image_prompt=self.image_prompt)
         if self.table_step:
             if self.factor is not None:
                 K.cfg_rescale_factor(noise, self.lat.shape, guidance=self.guidance, phi=self.guidance_rescale,
@@ -285,6 +288,9 @@ class AnimateDiffDenoiser:
         The first call drops a captured step (the gated step runs other kernels); later calls rewrite the gate
         tables in place, re-project the text K/V of every attn2 into their buffers, and keep it, so a schedule can
         be driven from the host: run_steps(k), set_lora_gates(...), run_steps()."""
+        if self.image_prompt is not None:
+            raise K._lib.VstError("image_prompt: not together with a lora_gate (the folded keys would differ per "
+                                  "frame)")
         c = self._gate_rows(content, "content")
         s = self._gate_rows(style, "style")
         if self.lora_gate is None:
@@ -292,6 +298,75 @@ class AnimateDiffDenoiser:
             self.graph = None
         self.lora_gate.set(c, s)
         refresh_text_kv(self.unet, self.lora_gate)
+
+    def _image_tokens(self, embeds, tokens, name):
+        """One branch's image tokens, bf16 [num_clips, T, D] on the device: `tokens` as given, else `embeds` through
+        unet.encoder_hid_proj (ip_adapter.ImageProjection)."""
+        if tokens is None:
+            proj = getattr(self.unet, "encoder_hid_proj", None)
+            if proj is None:
+                raise ValueError(f"{name}: image embeds need unet.encoder_hid_proj (load_ip_adapter); pass tokens=")
+            e = torch.as_tensor(embeds).to(self.device, BF16)
+            if e.dim() != 2 or e.shape[0] not in (1, self.nclips):
+                raise ValueError(f"{name}: image embeds {tuple(e.shape)}, expected (1 or {self.nclips}, dim)")
+            tokens = proj(e)
+        t = torch.as_tensor(tokens).to(self.device, BF16)
+        if t.dim() != 3 or t.shape[0] not in (1, self.nclips):
+            raise ValueError(f"{name}: image tokens {tuple(t.shape)}, expected (1 or {self.nclips}, tokens, dim)")
+        return t.expand(self.nclips, *t.shape[1:])
+
+    def set_image_prompt(self, image_embeds=None, *, tokens=None, negative_image_embeds=None, negative_tokens=None,
+                         strength=1.0):
+        """The image prompt of an IP-Adapter (ip_adapter.load_ip_adapter).  `image_embeds` (1 or
+        num_clips, dim) go through unet.encoder_hid_proj; `tokens` (1 or num_clips, T, D) are taken as they are (the
+        16 tokens of a "plus" Resampler, say).  The uncond branch of CFG takes `negative_tokens`, else
+        `negative_image_embeds`, else zero embeds through the projection, as diffusers does; without the projection
+        it needs `negative_tokens`.  Batch order [uncond clips..., cond clips...], like set_prompt_embeds.
+        `strength`: what the image term of each frame is multiplied by, in the forms set_lora_gates takes (a scalar,
+        (F_total,), (num_clips, F_total) or this rank's (num_clips, F_local)); 0 leaves a frame alone.
+        The first call drops a captured step; later calls rewrite the token and strength buffers in place, re-fold
+        the image keys of every layer into their buffers and keep it.  Not together with set_lora_gates."""
+        if (image_embeds is None) == (tokens is None):
+            raise ValueError("set_image_prompt: give image_embeds or tokens (one of them)")
+        if self.lora_gate is not None:
+            raise K._lib.VstError("image_prompt: not together with a lora_gate (the folded keys would differ per "
+                                  "frame)")
+        cond = self._image_tokens(image_embeds, tokens, "set_image_prompt")
+        if self.cfg:
+            if negative_tokens is None and negative_image_embeds is None:
+                if getattr(self.unet, "encoder_hid_proj", None) is None:
+                    raise ValueError("set_image_prompt: CFG needs negative_tokens when the model has no "
+                                     "encoder_hid_proj")
+                negative_image_embeds = torch.zeros(1, self.unet.encoder_hid_proj.image_embeds.in_features,
+                                                    dtype=BF16, device=self.device)
+            neg = self._image_tokens(negative_image_embeds, negative_tokens, "set_image_prompt (negative)")
+            if neg.shape != cond.shape:
+                raise ValueError(f"set_image_prompt: negative tokens {tuple(neg.shape)} vs {tuple(cond.shape)}")
+            cond = torch.cat([neg, cond], 0)
+        rows = self._gate_rows(strength, "image prompt strength")
+        p = self.image_prompt
+        if p is None or tuple(p.tokens.shape) != tuple(cond.shape):
+            p = ImagePrompt(cond, self.F, rows.view(cond.shape[0], self.F))
+            check_forward(self.unet, p, self.ncopy * self.nclips * self.F, None)  # before it replaces anything
+            self.image_prompt = p
+            self.graph = None
+        else:
+            p.set_tokens(cond)
+            p.set_strength(rows.view(cond.shape[0], self.F))
+            refresh_image_kv(self.unet, p)
+
+    def clear_image_prompt(self):
+        """Back to the plain step (drops a captured step with the image attention).  The IP-Adapter processors, if
+        still installed, refuse a forward without a prompt: take them off with ip_adapter.unload_ip_adapter."""
+        if self.image_prompt is not None:
+            self.image_prompt = None
+            self.graph = None
+
+    def set_ip_adapter_scale(self, scale):
+        """unet.set_ip_adapter_scale, dropping a captured step (the scales are launch arguments, and a layer at 0
+        launches nothing)."""
+        self.unet.set_ip_adapter_scale(scale)
+        self.graph = None
 
     def set_freeu(self, s1: float, s2: float, b1: float, b2: float):
         """FreeU values for the steps that follow.  When FreeU is already on, its device table is rewritten in place

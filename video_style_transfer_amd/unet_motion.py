@@ -269,6 +269,7 @@ class FwdCtx:
     cross_frame: Optional[CrossFrameAttention] = None   # spatial attn1 also attends to source frames when F > 1
     lora_gate: Optional[object] = None  # lora_gate.LoraGate ([B * F] rows): per-frame content / style strength
     freeu: Optional[FreeU] = None       # backbone scale + skip filter before the skip concats of up stages 0 and 1
+    image_prompt: Optional[object] = None  # ip_adapter.ImagePrompt ([B * F] rows): image tokens of the attn2 layers
 
 
 # --------------------------------------------------------------------------------------- blocks
@@ -359,6 +360,8 @@ class BasicTransformerBlock(nn.Module):
             x = self.attn1(n.view(nimg, N, C), _vst_residual=x, _vst_lora_u=u, **kw, **gkw,
                            **ctx.cross_kwargs).view(-1, C)
             n, u = self.norm2.run_lora(x, input_lora_ops(self.attn2, False, scale))
+            if ctx.image_prompt is not None:
+                gkw = dict(gkw, _vst_image_prompt=ctx.image_prompt)
             x = self.attn2(n.view(nimg, N, C), encoder_hidden_states=ctx.enc, _vst_residual=x, _vst_lora_u=u, **gkw,
                            **ctx.cross_kwargs).view(-1, C)
         n = self.norm3.run(x)
@@ -692,6 +695,13 @@ class UNetMotionModel(nn.Module):
     def disable_freeu(self):
         self.freeu = None
 
+    def set_ip_adapter_scale(self, scale):
+        """The weight of the image term of the IP-Adapter layers (ip_adapter.load_ip_adapter): a float, or
+        {attention name prefix: float} with 0 for the layers under no prefix (InstantStyle-like block selection).  A
+        layer at 0 launches nothing, so a captured step must be captured again after a change."""
+        from .ip_adapter import set_ip_adapter_scale
+        set_ip_adapter_scale(self, scale)
+
     # ---- embeddings -----------------------------------------------------------------------
     def embed(self, timestep, text_embeds, time_ids, B, step_idx=None, out=None):
         """SiLU(time_embedding(Timesteps(t)) + add_embedding([text_embeds, Timesteps(time_ids)])) -> [B, T].
@@ -726,7 +736,7 @@ class UNetMotionModel(nn.Module):
 
     # ---- core (NHWC tokens) -----------------------------------------------------------------
     def forward_tokens(self, x, B, F, h, w, emb_silu, enc, cross_kwargs=None, shard=None, fusion_world=None,
-                       temporal_context=None, cross_frame=None, lora_gate=None, freeu=None):
+                       temporal_context=None, cross_frame=None, lora_gate=None, freeu=None, image_prompt=None):
         """x: [B*F*h*w, in_channels] bf16 -> noise prediction [B*F*h*w, out_channels] bf16.
         With `shard` (frame_shard.FrameShard), F is this rank's frames of each clip.  `fusion_world` P (default: the
         shard's world size, else 1): take the shape-dependent fusion decisions a P-way frame-sharded rank takes
@@ -736,7 +746,11 @@ class UNetMotionModel(nn.Module):
         row order; under a shard this rank's frames): the content / style strength of the UnZipLoRA delta of the
         spatial transformer blocks' projections, per row.  The motion modules are not gated.  `freeu` (freeu.FreeU, or
         its (s1, s2, b1, b2)): FreeU in the first two up blocks; None runs today's launches.  Here
-        None means off: the enable_freeu default is applied by forward()."""
+        None means off: the enable_freeu default is applied by forward().  `image_prompt` (ip_adapter.ImagePrompt with
+        B * F rows): the image tokens of the IP-Adapter attn2 layers (load_ip_adapter); required when
+        they are installed, refused when they are not."""
+        from .ip_adapter import check_forward  # (local import: ip_adapter imports the attention processors)
+        check_forward(self, image_prompt, B * F, lora_gate)
         freeu = as_freeu(freeu, x.device)
         cross_frame = as_cross_frame(cross_frame)
         check_cross_frame(self, F * (shard.world if shard is not None else 1), cross_frame, shard, (h, w))
@@ -750,7 +764,7 @@ class UNetMotionModel(nn.Module):
         # no split-K: a row's bits do not depend on the launch's row count (frame shards)
         with K.row_invariant(), K.fusion_world(fusion_world):
             ctx = FwdCtx(B, F, emb_silu, enc, cross_kwargs or {}, shard, self.batched_temb(emb_silu),
-                         temporal_context, cross_frame, lora_gate, freeu)
+                         temporal_context, cross_frame, lora_gate, freeu, image_prompt)
             nimg = B * F
             H, W = h, w
             x = self.conv_in.run(x, nimg, H, W)
@@ -766,16 +780,20 @@ class UNetMotionModel(nn.Module):
 
     def forward(self, sample, timestep, encoder_hidden_states, timestep_cond=None, attention_mask=None,
                 cross_attention_kwargs=None, added_cond_kwargs=None, return_dict=True, frame_shard=None,
-                fusion_world=None, temporal_context=None, cross_frame=None, lora_gate=None, freeu=None, **kwargs):
+                fusion_world=None, temporal_context=None, cross_frame=None, lora_gate=None, freeu=None,
+                image_prompt=None, **kwargs):
         """diffusers UNetMotionModel.forward signature (inference_animatediff.py:110-121).  With
         `frame_shard` (frame_shard.FrameShard) `sample` holds this rank's frames of each clip; `fusion_world`: see
         forward_tokens; `temporal_context` (TemporalContext): the motion modules attend inside sliding windows when the
         clip is longer than its length; `cross_frame` (CrossFrameAttention or its sources, e.g. ("first",)): attn1 of the
         spatial transformer blocks also attends to the source frames of the same clip; `lora_gate`: see
-        forward_tokens; `freeu` (FreeU or (s1, s2, b1, b2)): FreeU for this call, default what enable_freeu set."""
+        forward_tokens; `freeu` (FreeU or (s1, s2, b1, b2)): FreeU for this call, default what enable_freeu set;
+        `image_prompt` (ip_adapter.ImagePrompt): see forward_tokens."""
         if not sample.is_cuda:
             raise K._lib.VstError("UNetMotionModel: sample is on CPU; the HIP path has no CPU fallback")
         B, Cin, F, h, w = sample.shape
+        from .ip_adapter import check_forward
+        check_forward(self, image_prompt, B * F, lora_gate)
         cross_frame = as_cross_frame(cross_frame)
         check_cross_frame(self, F * (frame_shard.world if frame_shard is not None else 1), cross_frame,
                           frame_shard, (h, w))
@@ -798,6 +816,6 @@ class UNetMotionModel(nn.Module):
         y = self.forward_tokens(x, B, F, h, w, emb_silu, enc, cross_attention_kwargs, shard=frame_shard,
                                 fusion_world=fusion_world, temporal_context=temporal_context,
                                 cross_frame=cross_frame, lora_gate=lora_gate,
-                                freeu=freeu)
+                                freeu=freeu, image_prompt=image_prompt)
         out = y.view(B, F, h, w, -1).permute(0, 4, 1, 2, 3).contiguous().to(sample.dtype)
         return UNetMotionOutput(out) if return_dict else (out,)
