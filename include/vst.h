@@ -527,6 +527,34 @@ int vst_sampler_step_noise(const void* noise, int ncopy, float guidance, float* 
 int vst_freeu(const void* x, int ldx, int Cx, const void* skip, int lds, int Cs, void* x_out, int ldxo,
               void* skip_out, int ldso, int nimg, int H, int W, const float* table, int stage, void* stream);
 
+/* ---- FreeInit's frequency mix: the re-initialisation of the latents between two passes of the denoise
+ * loop, after Wu et al., "FreeInit" (ECCV 2024) and diffusers' FreeInitMixin._apply_free_init.  No reference counterpart
+ * (its loop runs once).  x, init, noise, out: fp32 (B, Cl, F, H, W) contiguous, the layout of the latents; per (clip,
+ * channel) volume, with DFT3 the transform over (F, H, W):
+ *   z   = x + init - r          (init NULL: z = x - r)
+ *   out = r + Re IDFT3(filt . DFT3(z))
+ *   r   = scale * noise[b][c][f][h][w]                        (noise != NULL; seed and iter NULL), or
+ *   r   = scale * n, n the normal of vst_noise_normal at (*seed, *iter, stream_id) with HW = H W, F_total = F, f0 = 0
+ *                                                             (noise NULL; seed and iter non-NULL, read on the device).
+ *   In the second form r is generated in the first launch and again in the last, never stored, and is bit for bit
+ *   scale * vst_noise_normal(...) of the same arguments (one fp32 product).
+ * filt: fp32 [F][H][W], the low-pass mask in unshifted DFT order, shared by every clip and channel.  It must be
+ *   symmetric under k -> -k on every axis (free_init.dft_order makes it so): the operator is then real, equal to the
+ *   real part diffusers keeps, and the kernel reads only the bins kw <= W / 2 of the real transform along W.
+ * Every axis is a dense DFT in fp32 on an exact (k n) mod N twiddle table, so any size is taken, not only powers of two.
+ * Three launches (plane forward, frame axis with the multiply, plane inverse), no atomics, every sum in an order fixed
+ * by (F, H, W): the same bits on every call, and a clip's bits do not depend on B.  filt all zeros stores r's bits.
+ * workspace: the spectrum between the launches, B * Cl * F * H * (W / 2 + 1) * 8 bytes, 16-byte aligned; ws_bytes at
+ *   least that.  Nothing past that many bytes is read or written.
+ * out may be x itself (same pointer: in place); otherwise out overlaps no operand, and the workspace overlaps none.
+ * Returns 1 before any launch on a NULL x / out / filt / workspace, both or neither of noise and (seed, iter) (seed and
+ * iter go together), a non-positive size, a stream_id outside [0, 65535] or Cl above 2^18 (as vst_noise_normal), B * Cl
+ * above 65535, a short workspace, a base that is not aligned to its element (workspace: 16 bytes) or a forbidden
+ * overlap; 3 for F, H or W above 128. */
+int vst_free_init_mix(const float* x, const float* init, const float* noise, float* out, const float* filt,
+                      float scale, const uint64_t* seed, const int* iter, int stream_id,
+                      int B, int Cl, int F, int H, int W, void* workspace, size_t ws_bytes, void* stream);
+
 /* Ceiling probes (no reference counterpart; bench.py's measured peaks next to the vendor figures,
  * SURVEY §8(d)).  vst_probe_mfma: `grid` workgroups x 8 waves, each wave `iters` x 16 independent
  * 16x16x32 bf16 MFMAs (flops = grid*8*iters*16*16384).  vst_probe_hbm_read: streams `bytes` of `src`

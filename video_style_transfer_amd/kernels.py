@@ -1466,6 +1466,60 @@ def cfg_rescale_factor(noise, lat_shape, *, guidance, phi, out=None, workspace=N
     return out
 
 
+# ---- FreeInit: the frequency mix between two passes of the loop (free_init.FreeInit) ----
+FREE_INIT_MAX_AXIS = 128  # the longest F, H or W vst_free_init_mix takes
+
+
+def free_init_workspace_bytes(shape) -> int:
+    """Bytes of the spectrum vst_free_init_mix keeps between its launches (the formula of include/vst.h)."""
+    B, Cl, F, H, W = (int(v) for v in shape)
+    return B * Cl * F * H * (W // 2 + 1) * 8
+
+
+def free_init_workspace(shape, device):
+    """The fp32 workspace free_init_mix needs for latents of this (B, Cl, F, H, W) shape."""
+    if len(shape) != 5 or min(shape) <= 0:
+        raise _lib.VstError(f"free_init_mix: shape {tuple(shape)} must be (B, Cl, F, H, W), all positive")
+    return torch.empty(free_init_workspace_bytes(shape) // 4, dtype=F32, device=device)
+
+
+def free_init_mix(x, init, filt, scale, *, noise=None, seed=None, it=None, stream_id=1, out=None, workspace=None):
+    """FreeInit's mix on fp32 (B, Cl, F, H, W) latents (vst_free_init_mix): out = r + L(x + init - r), L the 3-D low-pass
+    with filt = free_init.dft_order(mask) as fp32 [F, H, W]; init may be None.  r = scale * noise (noise of x's shape),
+    or, with seed (int64 [1]) and it (int32 [1]) instead, scale * noise_normal(seed, it, x.shape, stream_id=stream_id),
+    regenerated in the kernel and read on the device, so a captured launch replays with new values.  out may be x."""
+    fn = "free_init_mix"
+    _block(x, F32, "x", fn)
+    if x.dim() != 5 or x.numel() == 0:
+        raise _lib.VstError(f"{fn}: x must be (B, Cl, F, H, W), got {tuple(x.shape)}")
+    B, Cl, F, H, W = x.shape
+    if init is not None:
+        _block(init, F32, "init", fn, x.shape)
+    _block(filt, F32, "filt", fn, (F, H, W))
+    if (noise is None) == (seed is None) or (seed is None) != (it is None):
+        raise _lib.VstError(f"{fn}: give noise, or seed and it (one source of the fresh noise)")
+    if noise is not None:
+        _block(noise, F32, "noise", fn, x.shape)
+    else:
+        _noise_operands(seed, it, stream_id, tuple(x.shape), None, 0, fn)
+    if out is None:
+        out = torch.empty_like(x)
+    _block(out, F32, "out", fn, x.shape)
+    if workspace is None:
+        workspace = free_init_workspace(x.shape, x.device)
+    _block(workspace, F32, "workspace", fn)
+    need = free_init_workspace_bytes(x.shape)
+    if workspace.numel() * 4 < need:
+        raise _lib.VstError(f"{fn}: workspace of {workspace.numel() * 4} bytes, {need} needed")
+    n = x.numel()
+    flops = 8.0 * B * Cl * F * H * (W // 2 + 1) * (W / 2 + 2 * H + 2 * F) + 2.0 * n * (W // 2)
+    with _Rec("free_init_mix", flops, 4.0 * n * (3 if init is None else 4) + 4.0 * need, lambda: "mix_plane_fwd_kernel",
+              tuple(x.shape)):
+        _lib.call("vst_free_init_mix", _p(x), _p(init), _p(noise), _p(out), _p(filt), float(scale), _p(seed), _p(it),
+                  int(stream_id), B, Cl, F, H, W, _p(workspace), workspace.numel() * 4, _stream())
+    return out
+
+
 # ---- ceiling probes (bench.py: measured peaks next to the vendor figures) ----
 def probe_mfma_tflops(device, grid=1024, iters=20000, reps=3):
     """Best-of-`reps` bf16 MFMA rate of vst_probe_mfma (16 independent 16x16x32 chains per wave)."""

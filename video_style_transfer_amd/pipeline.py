@@ -16,6 +16,9 @@ vst_cfg_rescale_factor when rescaling: its coefficients, its history and the res
 The stochastic samplers ("euler_a", "dpmpp_2m_sde", "lcm") step with vst_sampler_step_noise: the fresh
 noise of every step is counter-based, a function of a device seed and the device step counter, so the captured step
 still replays unchanged.
+With free_init= a call runs the loop num_iters times; between two passes vst_free_init_mix re-noises the
+result with the run's initial noise, keeps its low spatio-temporal frequencies and takes the high ones from fresh
+counter-based noise.  The mix runs between passes, outside the step, so the captured step replays untouched.
 """
 from __future__ import annotations
 
@@ -27,6 +30,7 @@ import torch
 
 from . import kernels as K
 from .attention_processor import refresh_text_kv
+from .free_init import FreeInit, as_free_init, check_free_init_arg, check_free_init_run, dft_order, freq_filter
 from .freeu import FreeU, as_freeu, check_freeu_arg
 from .ip_adapter import ImagePrompt, check_forward, refresh_image_kv
 from .lora_gate import LoraGate
@@ -69,7 +73,7 @@ class AnimateDiffDenoiser:
                  scheduler: Optional[EulerDiscreteScheduler] = None, use_graph: bool = True, shard=None,
                  num_clips: int = 1, context_length: Optional[int] = None, context_stride: int = 4,
                  context_weighting: str = "pyramid", cross_frame=None, sampler: str = "euler",
-                 guidance_rescale: float = 0.0, eta: float = 1.0, freeu=None):
+                 guidance_rescale: float = 0.0, eta: float = 1.0, freeu=None, free_init=None):
         """`num_clips` clips are denoised together (the reference loop is one clip, B=1).
         `shard` (frame_shard.FrameShard): this process denoises frames [f0, f0 + F/P) of every clip and
         exchanges with the other ranks inside every motion module.
@@ -93,9 +97,15 @@ class AnimateDiffDenoiser:
         `freeu` (a freeu.FreeU or its (s1, s2, b1, b2), each finite and > 0): FreeU in the UNet's first
         two up blocks, the reference's enable_freeu.  None takes what unet.enable_freeu set, if anything, as it stands
         now.  It is per frame and per channel, so it composes with every other option, a frame shard included; the
-        values live in a device table, so set_freeu keeps a captured step."""
+        values live in a device table, so set_freeu keeps a captured step.
+        `free_init` (a free_init.FreeInit, a dict of its fields or its tuple): FreeInit, diffusers'
+        enable_free_init.  A call (`__call__`) then runs the whole loop num_iters times, with the frequency mix of
+        kernels.free_init_mix between two passes.  It transforms whole clips, so a frame shard of more than one rank
+        is refused, and so is a source run; num_iters 1 or None is the plain run, launch for launch."""
         self.guidance_rescale = check_sampler(sampler, guidance_scale, guidance_rescale, shard, eta, scheduler)
         check_freeu_arg(freeu)
+        check_free_init_arg(free_init)
+        check_free_init_run(free_init, shard)
         if unet is None:  # refused with the other arguments, before anything is allocated
             raise ValueError("AnimateDiffDenoiser needs a UNetMotionModel, got None")
         self.sampler = sampler
@@ -159,6 +169,12 @@ class AnimateDiffDenoiser:
             if self.guidance_rescale > 0.0:
                 self.factor = torch.ones(num_clips, dtype=torch.float32, device=dev)
                 self.rescale_ws = K.cfg_rescale_workspace(self.lat.shape, dev)
+        # FreeInit: the latents the run was entered with, the mask in DFT order, the seed and the
+        # counter of the fresh noise and the spectrum workspace; static device buffers, allocated when it is turned on
+        self.free_init = None
+        self.fi_init = self.fi_filt = self.fi_seed = self.fi_iter = self.fi_ws = None
+        if free_init is not None:
+            self._set_free_init(as_free_init(free_init))
 
     def set_prompt_embeds(self, cond_embeds, cond_pooled, uncond_embeds=None, uncond_pooled=None):
         """(1 or num_clips, L, D) text states and (1 or num_clips, P) pooled embeds per branch
@@ -384,6 +400,38 @@ class AnimateDiffDenoiser:
             self.freeu = None
             self.graph = None
 
+    def _set_free_init(self, fi: FreeInit):
+        check_free_init_run(fi, self.shard)
+        F, h, w = self.lat.shape[2:]
+        if max(F, h, w) > K.FREE_INIT_MAX_AXIS:
+            raise ValueError(f"free_init: a clip of {F} x {h} x {w} latents; the frequency mix takes at most "
+                             f"{K.FREE_INIT_MAX_AXIS} per axis")
+        filt = dft_order(freq_filter(F, h, w, fi)).to(torch.float32)
+        if self.fi_init is None:
+            dev = self.device
+            self.fi_init = self.lat.clone()
+            self.fi_filt = torch.empty(F, h, w, dtype=torch.float32, device=dev)
+            self.fi_seed = torch.zeros(1, dtype=torch.int64, device=dev)
+            self.fi_iter = torch.zeros(1, dtype=torch.int32, device=dev)
+            self.fi_ws = K.free_init_workspace(self.lat.shape, dev)
+        self.fi_filt.copy_(filt)
+        self.free_init = fi
+
+    def enable_free_init(self, num_iters: int = 3, use_fast_sampling: bool = False, method: str = "butterworth",
+                         order: int = 4, spatial_stop_frequency: float = 0.25,
+                         temporal_stop_frequency: float = 0.25):
+        """diffusers' enable_free_init for the calls that follow (free_init.FreeInit).  The mix runs
+        between the passes of a call, so a captured step is kept.  `use_fast_sampling` (fewer steps in the early
+        passes) is refused: the step count is part of the captured step."""
+        if use_fast_sampling:
+            raise ValueError("free_init use_fast_sampling: the number of steps is fixed at construction (the captured "
+                             "step wraps its counter at num_inference_steps)")
+        self._set_free_init(FreeInit(num_iters, method, order, spatial_stop_frequency, temporal_stop_frequency))
+
+    def disable_free_init(self):
+        """Back to one pass per call (the buffers stay; a captured step is kept)."""
+        self.free_init = None
+
     def clear_lora_gates(self):
         """Back to the plain step (drops a captured gated step)."""
         if self.lora_gate is not None:
@@ -399,6 +447,7 @@ class AnimateDiffDenoiser:
         mask: optional keep mask (1 or num_clips, F_total or F_local, h, w) in [0, 1] over the channels; 1 = free to
         change, 0 = keep the source: after every Euler update lat = m * lat + (1 - m) * (z0 + sigmas[i + 1] * eps).
         A new strength, source or mask values reuse a captured step; adding or removing the mask drops it."""
+        check_free_init_run(self.free_init, source=True)
         t_start = start_index(self.num_steps, strength)
         C = self.lat.shape[1]
         z0 = torch.as_tensor(latents)
@@ -440,11 +489,18 @@ class AnimateDiffDenoiser:
         if lat.dim() == 5 and lat.shape[2] == self.F_total and self.F != self.F_total:
             lat = lat[:, :, self.f0:self.f0 + self.F]
         self.lat.copy_(lat.reshape(self.lat.shape))
+        if self.free_init is not None:
+            self.fi_init.copy_(self.lat)  # z_init: what every later pass is re-noised with
+        self._restart()
+        self._set_masked(False)
+
+    def _restart(self):
+        """The step counter, the run bookkeeping and the coefficient table (first order at step 0, so the sampler's
+        history is not read there) as a run from the top of the schedule finds them."""
         self.step_idx.zero_()
         self.t_start = 0
         self.steps_run = 0
         self._write_coef(0)
-        self._set_masked(False)
 
     def init_latents(self, seed: int = 42):
         """randn((1,4,F,h,w), generator=seed) * init_noise_sigma (inference_animatediff.py:88-95); with
@@ -475,7 +531,13 @@ class AnimateDiffDenoiser:
                  content_scale=None, style_scale=None):
         """Plain run from `latents` (or from noise drawn with `seed`), or, with `source` and `strength` (and an
         optional keep `mask`), a video-to-video run (set_source).  `content_scale` / `style_scale`: set_lora_gates
-        for this and later runs (the one not given is 1).  `seed` is also the noise seed of a stochastic sampler."""
+        for this and later runs (the one not given is 1).  `seed` is also the noise seed of a stochastic sampler, and
+        of FreeInit's fresh noise (stream 1 of the same counters, so the two are independent).  With free_init on the
+        loop runs num_iters times: before pass i >= 1 the latents become free_init_mix(lat, z_init, filter,
+        init_noise_sigma) at noise counter i - 1 and the run restarts from the top of the schedule; the captured step
+        is not recaptured."""
+        fi = self.free_init
+        check_free_init_run(fi, self.shard, source is not None)
         if self.noise_seed is not None:
             self.set_noise_seed(seed)
         if content_scale is not None or style_scale is not None:
@@ -491,7 +553,19 @@ class AnimateDiffDenoiser:
             self.init_latents(seed)
         else:
             self.set_latents(latents)
-        return self.run_steps()
+        self.run_steps()
+        if fi is not None and fi.num_iters > 1:
+            v = int(seed) & (2 ** 64 - 1)
+            self.fi_seed.fill_(v - 2 ** 64 if v >= 2 ** 63 else v)  # the same 64 bits as an int64
+            for i in range(1, fi.num_iters):
+                self.fi_iter.fill_(i - 1)
+                K.free_init_mix(self.lat, self.fi_init, self.fi_filt, float(self.scheduler.init_noise_sigma),
+                                seed=self.fi_seed, it=self.fi_iter, stream_id=1, out=self.lat, workspace=self.fi_ws)
+                self._restart()
+                if self.hist is not None:
+                    self.hist.zero_()
+                self.run_steps()
+        return self.lat
 
     def decode(self, vae) -> torch.Tensor:
         """inference_animatediff.py:137-144 for the frames this rank holds: latents / scaling_factor -> VAE decode ->
