@@ -555,6 +555,48 @@ int vst_free_init_mix(const float* x, const float* init, const float* noise, flo
                       float scale, const uint64_t* seed, const int* iter, int stream_id,
                       int B, int Cl, int F, int H, int W, void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- Token merging for the spatial transformer blocks: Bolya & Hoffman, "Token Merging for Fast Stable
+ * Diffusion" (CVPR-W 2023), tomesd's bipartite_soft_matching_random2d with a row layout that depends on no sort order.
+ * No reference counterpart.  Tokens of one image are rows p = y*W + x of a bf16 view [nimg * N, C], N = H * W.
+ * Destinations and sources.  The image is cut into hc x wc = (H / sy) x (W / sx) whole cells of sy x sx tokens (leftover
+ *   rows and columns belong to no cell).  One token per cell, at in-cell offset o(cell), (oy, ox) = (o / sx, o % sx), is a
+ *   destination: Nd = hc * wc of them, numbered j in raster order of the cells.  Every other token is a source:
+ *   Ns = N - Nd, numbered i in ascending token index.  seed == NULL: o = 0.  Otherwise, both read on the device,
+ *     o(cell) = Philox4x32-10(counter (cell, 0, *step_idx, 2 << 16 | layer), key (lo32, hi32 of *seed))[0] % (sy * sx),
+ *   stream 2 of the counters of vst_noise_bits.  The image index is no input: every image of a call, and every frame
+ *   shard of a clip, draws one pattern.
+ * vst_tome_match, per image, on the metric x: s[i][j] = <a_i, b_j> / (|a_i| |b_j|) (bf16 MFMA products with fp32
+ *   accumulation; fp32 norms, lane-strided squares then a butterfly, an order fixed by C; a zero row scores 0, and a
+ *   non-finite product 0: never NaN); best[i] = max_j s[i][j], node[i] the lowest j that attains it; the r sources with
+ *   the largest best (ties: the lower i) are merged into their node.  Outputs: best, fp32 [nimg][Ns], and the plan,
+ *   vst_tome_plan_bytes(nimg, N, r) = nimg * (6 N + 4) * 4 bytes of int32, per image at these offsets:
+ *     0       slot[N]: the merged row of token p; destination j has row j, the Ns - r kept sources the rows Nd ..
+ *             N - r - 1 in ascending token index, a merged source its node's row;
+ *     N       dst_tok[Nd], then src_tok[Ns];
+ *     2 N     node[Ns] (of every source, merged or not);
+ *     3 N     start[Nd + 1], then list[r]: the tokens of the sources merged into destination j, ascending, are
+ *             list[start[j] .. start[j + 1]);
+ *     4 N + 4 kept_tok[Ns - r]: the token of merged row Nd + k;
+ *     5 N + 4 inv[N]: fp32 bits of 1 / |x_p| (0 for a zero row).
+ * vst_tome_merge: y [nimg * (N - r), C]; y[m] = bf16(sum / count) over the members of merged row m (the destination
+ *   and list[start[m] .. start[m + 1]) for m < Nd), summed in fp32 in ascending token index; a row with one member is
+ *   copied bit for bit.
+ * vst_tome_unmerge_add: y[p] = bf16(float(res[p]) + float(o[slot[p]])) over [nimg * N, C], o [nimg * (N - r), C];
+ *   res == NULL: y[p] = o[slot[p]] bit for bit; y may be res (same pointer and stride).
+ * No atomics; every sum in an order fixed by the shapes: the same bits on every call, and an image's plan and rows do
+ * not depend on nimg or on the other images.  Guard columns are neither read into a result nor written.  merge and
+ * unmerge_add clamp what they read from a plan to the image.
+ * Needs N <= 4096, C % 64 == 0, C <= 1280: 3 (VST_ERR_UNSUPPORTED) otherwise, before any launch.  1 before any launch
+ * on a NULL pointer, a non-positive size, sy > H or sx > W, r outside [0, Ns], a layer outside [0, 65535], only one of
+ * seed and step_idx, a stride below C or no multiple of 8, a bf16 base or plan that is not 16-byte aligned. */
+size_t vst_tome_plan_bytes(int nimg, int N, int r);
+int vst_tome_match(const void* x, int ldx, int nimg, int H, int W, int C, int sy, int sx, int r, const uint64_t* seed,
+                   const int* step_idx, int layer, int* plan, float* best, void* stream);
+int vst_tome_merge(const void* x, int ldx, const int* plan, int nimg, int H, int W, int C, int sy, int sx, int r,
+                   void* y, int ldy, void* stream);
+int vst_tome_unmerge_add(const void* o, int ldo, const int* plan, int nimg, int N, int r, int C, const void* res,
+                         int ldr, void* y, int ldy, void* stream);
+
 /* Ceiling probes (no reference counterpart; bench.py's measured peaks next to the vendor figures,
  * SURVEY §8(d)).  vst_probe_mfma: `grid` workgroups x 8 waves, each wave `iters` x 16 independent
  * 16x16x32 bf16 MFMAs (flops = grid*8*iters*16*16384).  vst_probe_hbm_read: streams `bytes` of `src`

@@ -1,0 +1,277 @@
+"""Token merging on the host: `tome_ref`, the fp64 restatement of the definition in include/vst.h that
+tests/test_token_merge_gpu.py holds the kernels to, checked here on hand-worked cases; and the host logic of
+token_merge.TokenMerging (which blocks merge, ratio -> r, the destination draw, the refusals, the ABI)."""
+import types
+
+import pytest
+import torch
+
+F64 = torch.float64
+
+
+def tome_ref(x, H, W, r, sy=2, sx=2, offsets=None):
+    """One image.  x [H*W, C] (any dtype, taken to fp64); offsets int [H//sy, W//sx] (None: zeros), the in-cell offset
+    o of every whole cell, (oy, ox) = (o // sx, o % sx).  Returns a namespace:
+      dst_tok [Nd] (cell raster), src_tok [Ns] (ascending), scores [Ns, Nd], best [Ns], node [Ns] (lowest j on ties),
+      merged bool [Ns] (the r largest best, ties to the lower i), slot [N], members: list over the N - r merged rows of
+      ascending token lists, and merge(t) / unmerge_add(o, res) on fp64."""
+    x = x.to(F64)
+    N = H * W
+    hc, wc = H // sy, W // sx
+    if offsets is None:
+        offsets = torch.zeros(hc, wc, dtype=torch.int64)
+    cy, cx = torch.meshgrid(torch.arange(hc), torch.arange(wc), indexing="ij")
+    dst_tok = ((cy * sy + offsets // sx) * W + cx * sx + offsets % sx).reshape(-1)
+    is_dst = torch.zeros(N, dtype=torch.bool)
+    is_dst[dst_tok] = True
+    src_tok = torch.nonzero(~is_dst).reshape(-1)
+    Nd, Ns = dst_tok.numel(), src_tok.numel()
+    a, b = x[src_tok], x[dst_tok]
+    na, nb = a.norm(dim=1), b.norm(dim=1)
+    den = na[:, None] * nb[None, :]
+    scores = torch.where(den > 0, (a @ b.t()) / den.clamp_min(1e-300), torch.zeros_like(den))
+    best, node = torch.zeros(Ns, dtype=F64), torch.zeros(Ns, dtype=torch.int64)
+    if Ns:
+        best = scores.max(dim=1).values
+        node = (scores == best[:, None]).to(torch.int64).argmax(dim=1)  # the first (lowest) j that attains the max
+    order = sorted(range(Ns), key=lambda i: (-best[i].item(), i))
+    merged = torch.zeros(Ns, dtype=torch.bool)
+    merged[order[:r]] = True
+    slot = torch.empty(N, dtype=torch.int64)
+    slot[dst_tok] = torch.arange(Nd)
+    kept = src_tok[~merged]
+    slot[kept] = Nd + torch.arange(kept.numel())
+    slot[src_tok[merged]] = node[merged]
+    members = [[] for _ in range(N - r)]
+    for p in range(N):
+        members[slot[p]].append(p)
+
+    def merge(t):
+        t = t.to(F64)
+        return torch.stack([t[m].mean(dim=0) if len(m) > 1 else t[m[0]] for m in members])
+
+    def unmerge_add(o, res=None):
+        o = o.to(F64)[slot]
+        return o if res is None else res.to(F64) + o
+
+    return types.SimpleNamespace(N=N, Nd=Nd, Ns=Ns, r=r, dst_tok=dst_tok, src_tok=src_tok, scores=scores, best=best,
+                                 node=node, merged=merged, slot=slot, members=members, merge=merge,
+                                 unmerge_add=unmerge_add)
+
+
+def onehot(N, C, rows):
+    x = torch.zeros(N, C, dtype=F64)
+    for p, v in rows.items():
+        x[p] = torch.tensor(v, dtype=F64)
+    return x
+
+
+# ------------------------------------------------------------------ the reference on hand-worked cases
+def test_ref_hand_worked_4x4():
+    """4 x 4, 2 x 2 cells, top-left destinations 0, 2, 8, 10 = e0 .. e3.  Token 1 = 2 e0 (score 1 with j = 0), token 3 =
+    e1 + e2 (0.707 with j = 1 and j = 2: the lower wins), token 4 = (3, 4, 0, 0) (0.6 with j = 0, 0.8 with j = 1), every
+    other source is a zero row (score 0 everywhere, node 0).  r = 2 merges tokens 1 and 4."""
+    x = onehot(16, 4, {0: [1, 0, 0, 0], 2: [0, 1, 0, 0], 8: [0, 0, 1, 0], 10: [0, 0, 0, 1],
+                       1: [2, 0, 0, 0], 3: [0, 1, 1, 0], 4: [3, 4, 0, 0]})
+    p = tome_ref(x, 4, 4, 2)
+    assert p.dst_tok.tolist() == [0, 2, 8, 10]
+    assert p.src_tok.tolist() == [1, 3, 4, 5, 6, 7, 9, 11, 12, 13, 14, 15]
+    assert torch.allclose(p.best[:3], torch.tensor([1.0, 0.5 ** 0.5, 0.8], dtype=F64), atol=1e-15)
+    assert p.best[3:].abs().max() == 0 and torch.isfinite(p.scores).all()
+    assert p.node.tolist() == [0, 1, 1] + [0] * 9
+    assert p.merged.tolist() == [True, False, True] + [False] * 9
+    assert p.slot.tolist() == [0, 0, 1, 4, 1, 5, 6, 7, 2, 8, 3, 9, 10, 11, 12, 13]
+    assert p.members[0] == [0, 1] and p.members[1] == [2, 4] and p.members[4] == [3]
+    y = p.merge(x)
+    assert y.shape == (14, 4)
+    assert torch.equal(y[0], torch.tensor([1.5, 0, 0, 0], dtype=F64))
+    assert torch.equal(y[1], torch.tensor([1.5, 2.5, 0, 0], dtype=F64))
+    assert torch.equal(y[4], x[3])
+    z = p.unmerge_add(y, x)
+    assert torch.equal(z[1], x[1] + y[0]) and torch.equal(z[4], x[4] + y[1]) and torch.equal(z[15], 2 * x[15])
+
+
+def test_ref_hand_worked_2x6_offsets_and_selection_tie():
+    """2 x 6, cells of 2 x 2 with offsets (1, 3, 2): destinations are tokens 1, 9 and 10.  Tokens 0 and 2 both score
+    exactly 1; with r = 1 the tie goes to the lower token."""
+    off = torch.tensor([[1, 3, 2]])
+    x = onehot(12, 3, {1: [1, 0, 0], 9: [0, 1, 0], 10: [0, 0, 1], 0: [1, 0, 0], 2: [0, 0.5, 0]})
+    p = tome_ref(x, 2, 6, 1, offsets=off)
+    assert p.dst_tok.tolist() == [1, 9, 10]
+    assert p.src_tok.tolist() == [0, 2, 3, 4, 5, 6, 7, 8, 11]
+    assert p.best[:2].tolist() == [1.0, 1.0] and p.node[:2].tolist() == [0, 1]
+    assert p.merged.tolist() == [True] + [False] * 8
+    assert p.slot.tolist() == [0, 0, 3, 4, 5, 6, 7, 8, 9, 1, 2, 10]
+    p2 = tome_ref(x, 2, 6, 2, offsets=off)
+    assert p2.merged.tolist() == [True, True] + [False] * 7 and p2.slot[2] == 1
+
+
+@pytest.mark.parametrize("H,W", [(4, 4), (5, 7)])
+def test_ref_r0_is_the_identity_plan_and_r_ns_merges_every_source(H, W):
+    g = torch.Generator().manual_seed(H * W)
+    x = torch.randn(H * W, 8, generator=g, dtype=F64)
+    p = tome_ref(x, H, W, 0)
+    assert sorted(p.slot.tolist()) == list(range(H * W)) and not p.merged.any()
+    assert torch.equal(p.unmerge_add(p.merge(x)), x)
+    q = tome_ref(x, H, W, p.Ns)
+    assert q.merged.all() and len(q.members) == q.Nd and int(q.slot.max()) == q.Nd - 1
+    assert torch.equal(q.slot[q.src_tok], q.node)
+    assert sum(len(m) for m in q.members) == H * W
+
+
+def test_ref_non_divisible_5x7():
+    """5 x 7 with 2 x 2 cells: 2 x 3 whole cells; row 4 and column 6 are sources."""
+    g = torch.Generator().manual_seed(57)
+    x = torch.randn(35, 16, generator=g, dtype=F64)
+    p = tome_ref(x, 5, 7, 8)
+    assert p.dst_tok.tolist() == [0, 2, 4, 14, 16, 18] and p.Ns == 29
+    assert all(t in p.src_tok.tolist() for t in [6, 13, 20, 27] + list(range(28, 35)))
+    assert int(p.merged.sum()) == 8 and len(p.members) == 27
+    kept = p.src_tok[~p.merged]
+    assert p.slot[kept].tolist() == list(range(6, 27))  # ascending token index
+    cut = sorted(p.best.tolist(), reverse=True)
+    assert p.best[p.merged].min() >= cut[7] and p.best[~p.merged].max() <= cut[7]
+
+
+def test_ref_round_trip_of_a_cell_constant_image():
+    """An image that is constant per 2 x 2 cell: every source's best match is a destination with its own value (score
+    1), so merge -> unmerge gives the image back exactly (small integers: the sums and the means are exact)."""
+    g = torch.Generator().manual_seed(3)
+    cells = torch.randint(-8, 9, (4, 4, 8), generator=g).to(F64)
+    x = cells.repeat_interleave(2, 0).repeat_interleave(2, 1).reshape(64, 8)
+    p = tome_ref(x, 8, 8, 32)
+    assert torch.equal(p.unmerge_add(p.merge(x)), x)
+    assert torch.allclose(p.best, torch.ones(48, dtype=F64), atol=1e-14)
+
+
+# ------------------------------------------------------------------ host logic
+def test_ratio_to_r_and_sizes():
+    from video_style_transfer_amd import kernels as K
+    from video_style_transfer_amd._lib import VstError
+    assert K.tome_sizes(32, 32, 2, 2, 0.5) == (1024, 256, 768, 512)
+    assert K.tome_sizes(32, 32, 2, 2, 0.75) == (1024, 256, 768, 768)
+    assert K.tome_sizes(32, 32, 2, 2, 0.9) == (1024, 256, 768, 768)       # clamps to Ns
+    assert K.tome_sizes(5, 7, 2, 2, 0.25) == (35, 6, 29, 8)
+    assert K.tome_sizes(4, 4, 2, 2, 0.0)[3] == 0
+    assert K.tome_sizes(16, 16, 2, 2, 1.0 / 256)[3] == 1
+    assert K.tome_plan_ints(1024) == 6 * 1024 + 4
+    for bad in ((4, 4, 5, 2, 0.5), (4, 4, 2, 2, 1.5), (4, 4, 2, 2, float("nan")), (0, 4, 2, 2, 0.5)):
+        with pytest.raises(VstError):
+            K.tome_sizes(*bad)
+
+
+def test_active_blocks_per_max_downsample():
+    """SDXL at a 64 x 64 latent: spatial transformer blocks at 32 x 32 (down-sampling 2) and 16 x 16 (4)."""
+    from video_style_transfer_amd.config import UNetMotionConfig
+    from video_style_transfer_amd.token_merge import TokenMerging, active_levels, downsample_of, spatial_levels
+    from video_style_transfer_amd.unet_motion import UNetMotionModel
+    with torch.device("meta"):
+        model = UNetMotionModel(UNetMotionConfig.sdxl())
+    levels = spatial_levels(model, 64, 64)
+    assert levels == [((32, 32), 640), ((16, 16), 1280), ((16, 16), 1280)]
+    hw = [l for l, _ in levels]
+    assert [downsample_of(64 * 64, H * W) for H, W in hw] == [2, 4, 4]
+    assert active_levels(TokenMerging(max_downsample=1), (64, 64), hw) == [False, False, False]
+    assert active_levels(TokenMerging(max_downsample=2), (64, 64), hw) == [True, False, False]
+    assert active_levels(TokenMerging(max_downsample=4), (64, 64), hw) == [True, True, True]
+    assert active_levels(TokenMerging(max_downsample=8), (64, 64), hw) == [True, True, True]
+    assert active_levels(TokenMerging(ratio=0.0, max_downsample=4), (64, 64), hw) == [False] * 3
+    assert active_levels(TokenMerging(merge_attn=False, max_downsample=4), (64, 64), hw) == [False] * 3
+    assert active_levels(TokenMerging(merge_attn=False, merge_mlp=True), (64, 64), hw) == [True, False, False]
+    assert active_levels(None, (64, 64), hw) == [False] * 3
+    assert downsample_of(35 * 35, 18 * 18) == 2  # odd latents round up, as tomesd does
+
+
+def test_defaults_mirror_tomesd_and_surface():
+    import dataclasses
+    import inspect
+    from video_style_transfer_amd.pipeline import AnimateDiffDenoiser
+    from video_style_transfer_amd.token_merge import TokenMerging, as_token_merging
+    from video_style_transfer_amd.unet_motion import FwdCtx, UNetMotionModel
+    tm = TokenMerging()
+    assert (tm.ratio, tm.max_downsample, tm.sx, tm.sy, tm.use_rand, tm.merge_attn, tm.merge_crossattn,
+            tm.merge_mlp) == (0.5, 2, 2, 2, True, True, False, False)
+    assert "token_merging" in [f.name for f in dataclasses.fields(FwdCtx)]
+    assert "token_merging" in inspect.signature(AnimateDiffDenoiser.__init__).parameters
+    assert "token_merging" in inspect.signature(UNetMotionModel.forward).parameters
+    assert hasattr(UNetMotionModel, "enable_token_merging") and hasattr(UNetMotionModel, "disable_token_merging")
+    assert as_token_merging(None) is None and as_token_merging(tm) is tm
+    assert as_token_merging(0.25).ratio == 0.25 and as_token_merging(dict(ratio=0.3, merge_mlp=True)).merge_mlp
+
+
+def test_refusals():
+    from video_style_transfer_amd._lib import VstError
+    from video_style_transfer_amd.attention_processor import AttnProcessor2_0
+    from video_style_transfer_amd.config import UNetMotionConfig
+    from video_style_transfer_amd.token_merge import TokenMerging, as_token_merging, check_token_merging
+    from video_style_transfer_amd.unet_motion import UNetMotionModel
+    with pytest.raises(VstError, match="merge_crossattn"):
+        TokenMerging(merge_crossattn=True)
+    for kw in (dict(ratio=-0.1), dict(ratio=1.5), dict(ratio=float("nan")), dict(ratio="x"), dict(max_downsample=3),
+               dict(sx=0), dict(sy=2.0)):
+        with pytest.raises(VstError, match="token_merging"):
+            TokenMerging(**kw)
+    with pytest.raises(VstError, match="token_merging"):
+        as_token_merging("half")
+    with torch.device("meta"):
+        model = UNetMotionModel(UNetMotionConfig.tiny())
+    model.requires_grad_(False)
+    tm = TokenMerging(max_downsample=4)
+    check_token_merging(model, tm, (16, 16))              # fine
+    check_token_merging(model, None, (16, 16))
+    with pytest.raises(VstError, match="tokens"):         # 128 x 128 tokens at the first level
+        check_token_merging(model, tm, (256, 256))
+    # the training path
+    p = next(model.parameters())
+    p.requires_grad_(True)
+    with pytest.raises(VstError, match="inference only"):
+        check_token_merging(model, tm, (16, 16))
+    with torch.no_grad():
+        check_token_merging(model, tm, (16, 16))
+    p.requires_grad_(False)
+    # another processor on a merged attn1
+    blk = model.down_blocks[1].attentions[0].transformer_blocks[0]
+    keep = blk.attn1.processor
+    blk.attn1.set_processor(AttnProcessor2_0())
+    with pytest.raises(VstError, match="AnimateDiffAttnProcessor2_0"):
+        check_token_merging(model, tm, (16, 16))
+    check_token_merging(model, TokenMerging(merge_attn=False, merge_mlp=True), (16, 16))
+    blk.attn1.set_processor(keep)
+    # the layers are numbered in module order
+    ids = [m.__dict__["_vst_tome_layer"] for m in model.modules() if "_vst_tome_layer" in m.__dict__]
+    assert ids == list(range(len(ids))) and len(ids) == 2 * 1 + 2 * 2 + 2 + 3 * 2 + 3 * 1
+
+
+def test_destination_draw_on_the_host():
+    from video_style_transfer_amd.token_merge import destination_offsets, destination_tokens
+    o = destination_offsets(8, 10, 2, 2, seed=7, step=3, layer=5)
+    assert o.shape == (4, 5) and int(o.min()) >= 0 and int(o.max()) <= 3
+    assert torch.equal(o, destination_offsets(8, 10, 2, 2, seed=7, step=3, layer=5))
+    assert not torch.equal(o, destination_offsets(8, 10, 2, 2, seed=7, step=4, layer=5))
+    assert not torch.equal(o, destination_offsets(8, 10, 2, 2, seed=7, step=3, layer=6))
+    assert not torch.equal(o, destination_offsets(8, 10, 2, 2, seed=8, step=3, layer=5))
+    assert int(destination_offsets(8, 10, 2, 2, None).abs().max()) == 0
+    tok = destination_tokens(8, 10, 2, 2, o)
+    y, x = tok // 10, tok % 10
+    assert torch.equal(y // 2, torch.arange(4).repeat_interleave(5)) and torch.equal(x // 2, torch.arange(5).repeat(4))
+    assert tome_ref(torch.ones(80, 2), 8, 10, 0, offsets=o).dst_tok.tolist() == tok.tolist()
+
+
+def test_abi_lists_the_new_symbols():
+    from video_style_transfer_amd import _lib
+    sig = _lib.SIGNATURES
+    for name, nargs in (("vst_tome_plan_bytes", 3), ("vst_tome_match", 15), ("vst_tome_merge", 13),
+                        ("vst_tome_unmerge_add", 12)):
+        assert name in sig and len(sig[name][1]) == nargs, name
+    import ctypes
+    assert sig["vst_tome_plan_bytes"][0] is ctypes.c_size_t
+    lib = _lib.load()
+    assert lib.vst_tome_plan_bytes(2, 1024, 512) == 2 * (6 * 1024 + 4) * 4
+    assert lib.vst_tome_plan_bytes(0, 1024, 0) == 0
+    # refused before any launch (no device is touched): sizes past the kernels' plan, bad arguments
+    assert lib.vst_tome_match(None, 64, 1, 4, 4, 64, 2, 2, 2, None, None, 0, None, None, None) == 1
+    assert lib.vst_tome_match(None, 64, 1, 128, 64, 64, 2, 2, 2, None, None, 0, None, None, None) == 3
+    assert lib.vst_tome_match(None, 72, 1, 4, 4, 72, 2, 2, 2, None, None, 0, None, None, None) == 3
+    assert lib.vst_tome_match(None, 1344, 1, 4, 4, 1344, 2, 2, 2, None, None, 0, None, None, None) == 3
+    assert lib.vst_tome_merge(None, 64, None, 1, 4, 4, 64, 2, 2, 13, None, 64, None) == 1   # r > Ns
+    assert lib.vst_tome_unmerge_add(None, 64, None, 1, 16, 16, 64, None, 0, None, 64, None) == 1

@@ -1520,6 +1520,133 @@ def free_init_mix(x, init, filt, scale, *, noise=None, seed=None, it=None, strea
     return out
 
 
+# ---- token merging (token_merge.TokenMerging) ----
+TOME_MAX_TOKENS = 4096  # the most tokens per image vst_tome_match takes
+TOME_MAX_CHANNELS = 1280
+
+
+def tome_sizes(H: int, W: int, sy: int, sx: int, ratio: float):
+    """(N, Nd, Ns, r) of an H x W image cut into sy x sx cells: the tokens, the destinations (whole cells), the sources
+    and the merged sources r = min(Ns, int(ratio * N))."""
+    H, W, sy, sx = int(H), int(W), int(sy), int(sx)
+    if min(H, W, sy, sx) < 1 or sy > H or sx > W:
+        raise _lib.VstError(f"token merging: cells of {sy} x {sx} on a {H} x {W} image")
+    ratio = float(ratio)
+    if not 0.0 <= ratio <= 1.0:  # also refuses NaN
+        raise _lib.VstError(f"token merging: ratio {ratio} outside [0, 1]")
+    N = H * W
+    Nd = (H // sy) * (W // sx)
+    return N, Nd, N - Nd, min(N - Nd, int(ratio * N))
+
+
+def tome_plan_ints(N: int) -> int:
+    """int32 per image of a plan (the formula of include/vst.h)."""
+    return 6 * int(N) + 4
+
+
+def tome_plan(nimg: int, N: int, device):
+    """A plan buffer for nimg images of N tokens (int32 [nimg, 6 N + 4]), zero-filled so that a merge before any match
+    reads valid rows."""
+    nbytes = int(_lib.load().vst_tome_plan_bytes(int(nimg), int(N), 0))
+    if nbytes != nimg * tome_plan_ints(N) * 4:
+        raise _lib.VstError(f"tome_plan: {nimg} images of {N} tokens")
+    return torch.zeros((nimg, tome_plan_ints(N)), dtype=I32, device=device)
+
+
+def _tome_operands(fn, x, nimg, H, W, sy, sx, r, plan, name="x", rows=None):
+    """The operands the three token-merging entries share: a bf16 view of nimg * (rows or H * W) rows whose width is a
+    multiple of 64 up to 1280, 16-byte aligned with a row stride that is a multiple of 8, and the plan of tome_plan."""
+    nimg, H, W, sy, sx, r = (int(v) for v in (nimg, H, W, sy, sx, r))
+    if min(nimg, H, W, sy, sx) < 1 or sy > H or sx > W:
+        _fail(fn, "nimg, H, W, sy, sx", f"= {nimg}, {H}, {W}, {sy}, {sx}: expected positive sizes and cells inside the "
+                                        f"image")
+    N = H * W
+    Ns = N - (H // sy) * (W // sx)
+    if not 0 <= r <= Ns:
+        _fail(fn, "r", f"= {r}: outside [0, Ns = {Ns}]")
+    _tome_view(fn, x, nimg * (N if rows is None else rows), name)
+    if N > TOME_MAX_TOKENS:
+        _fail(fn, name, f"{N} tokens per image: at most {TOME_MAX_TOKENS}")
+    _block(plan, I32, "plan", fn, shape=(nimg, tome_plan_ints(N)))
+    if plan.data_ptr() % 16:
+        _fail(fn, "plan", "needs a 16-byte aligned base")
+    return N, Ns
+
+
+def _tome_view(fn, t, rows, name, C=None):
+    _view(t, BF16, name, fn, rows=rows)
+    c = t.shape[1]
+    if c == 0 or c % 64 or c > TOME_MAX_CHANNELS or (C is not None and c != C):
+        _fail(fn, name, f"{c} columns: expected {'a multiple of 64' if C is None else C}, at most {TOME_MAX_CHANNELS}")
+    if _ld(t) % 8 or t.data_ptr() % 16:
+        _fail(fn, name, f"needs a row stride that is a multiple of 8 and a 16-byte aligned base, got stride "
+                        f"{t.stride()}")
+    return c
+
+
+def tome_match(x, nimg, H, W, r, plan, *, sy=2, sx=2, seed=None, step_idx=None, layer=0, best=None):
+    """The bipartite matching of token merging (vst_tome_match): x [nimg*H*W, C] bf16 view, the metric; writes the plan
+    (tome_plan) and returns best, fp32 [nimg, Ns], every source's largest cosine score.  seed (int64 [1]) and step_idx
+    (int32 [1]), both or neither: the destination of every cell is drawn from the Philox counters at (seed, step,
+    layer, cell), read on the device; neither: the cell's top-left token."""
+    fn = "tome_match"
+    N, Ns = _tome_operands(fn, x, nimg, H, W, sy, sx, r, plan)
+    if (seed is None) != (step_idx is None):
+        _fail(fn, "seed, step_idx", "go together")
+    if seed is not None:
+        _block(seed, torch.int64, "seed", fn, (1,))
+        _step_counter(step_idx, fn)
+    if not 0 <= int(layer) < 1 << 16:
+        _fail(fn, "layer", f"= {layer}: outside [0, 65535]")
+    if best is None:
+        best = torch.empty((nimg, Ns), dtype=F32, device=x.device)
+    _block(best, F32, "best", fn, shape=(nimg, Ns))
+    C = x.shape[1]
+    Nd = N - Ns
+    with _Rec("tome_match", 2.0 * nimg * Ns * Nd * C, 2.0 * nimg * N * C * 2, lambda: "tome_score_kernel",
+              (nimg, N, C, r)):
+        _lib.call("vst_tome_match", _p(x), _ld(x), int(nimg), int(H), int(W), C, int(sy), int(sx), int(r), _p(seed),
+                  _p(step_idx), int(layer), _p(plan), _p(best), _stream())
+    return best
+
+
+def tome_merge(x, nimg, H, W, r, plan, *, sy=2, sx=2, out=None):
+    """x [nimg*N, C] -> [nimg*(N - r), C]: every merged row is the mean of its members (vst_tome_merge), in fp32 in
+    ascending token order; a row with one member is copied."""
+    fn = "tome_merge"
+    N, _ = _tome_operands(fn, x, nimg, H, W, sy, sx, r, plan)
+    C = x.shape[1]
+    out = _new(out, (nimg * (N - r), C), x, "out", fn)
+    _tome_view(fn, out, nimg * (N - r), "out", C)
+    with _Rec("tome_merge", 1.0 * nimg * N * C, 2.0 * nimg * (2 * N - r) * C, lambda: "tome_merge_kernel",
+              (nimg, N, C, r)):
+        _lib.call("vst_tome_merge", _p(x), _ld(x), _p(plan), int(nimg), int(H), int(W), C, int(sy), int(sx), int(r),
+                  _p(out), _ld(out), _stream())
+    return out
+
+
+def tome_unmerge_add(o, nimg, N, r, plan, *, residual=None, out=None):
+    """o [nimg*(N - r), C] -> [nimg*N, C]: out[p] = residual[p] + o[slot[p]] (vst_tome_unmerge_add), or o[slot[p]] bit
+    for bit without a residual; out may be the residual."""
+    fn = "tome_unmerge_add"
+    nimg, N, r = int(nimg), int(N), int(r)
+    if nimg < 1 or N < 1 or not 0 <= r < N or N > TOME_MAX_TOKENS:
+        _fail(fn, "nimg, N, r", f"= {nimg}, {N}, {r}: expected positive sizes, N <= {TOME_MAX_TOKENS} and 0 <= r < N")
+    C = _tome_view(fn, o, nimg * (N - r), "o")
+    _block(plan, I32, "plan", fn, shape=(nimg, tome_plan_ints(N)))
+    if plan.data_ptr() % 16:
+        _fail(fn, "plan", "needs a 16-byte aligned base")
+    if residual is not None:
+        _tome_view(fn, residual, nimg * N, "residual", C)
+    out = _new(out, (nimg * N, C), o, "out", fn)
+    _tome_view(fn, out, nimg * N, "out", C)
+    with _Rec("tome_unmerge_add", 1.0 * nimg * N * C, 2.0 * nimg * N * C * (2 if residual is None else 3),
+              lambda: "tome_unmerge_kernel", (nimg, N, C, r)):
+        _lib.call("vst_tome_unmerge_add", _p(o), _ld(o), _p(plan), nimg, N, r, C, _p(residual),
+                  0 if residual is None else _ld(residual), _p(out), _ld(out), _stream())
+    return out
+
+
 # ---- ceiling probes (bench.py: measured peaks next to the vendor figures) ----
 def probe_mfma_tflops(device, grid=1024, iters=20000, reps=3):
     """Best-of-`reps` bf16 MFMA rate of vst_probe_mfma (16 independent 16x16x32 chains per wave)."""

@@ -19,6 +19,8 @@ still replays unchanged.
 With free_init= a call runs the loop num_iters times; between two passes vst_free_init_mix re-noises the
 result with the run's initial noise, keeps its low spatio-temporal frequencies and takes the high ones from fresh
 counter-based noise.  The mix runs between passes, outside the step, so the captured step replays untouched.
+With token_merging= the spatial transformer blocks merge tokens around attn1 (and the feed-forward); the
+plans live in static buffers and the destination draw reads the device seed and step counter, so the step still replays.
 """
 from __future__ import annotations
 
@@ -34,6 +36,7 @@ from .free_init import FreeInit, as_free_init, check_free_init_arg, check_free_i
 from .freeu import FreeU, as_freeu, check_freeu_arg
 from .ip_adapter import ImagePrompt, check_forward, refresh_image_kv
 from .lora_gate import LoraGate
+from .token_merge import TokenMerging, as_token_merging, check_token_merging
 from .scheduler import (SAMPLERS, STOCHASTIC_SAMPLERS, EulerDiscreteScheduler, check_eta, sampler_coefficients,
                         start_index)
 from .unet_motion import TemporalContext, UNetMotionModel, as_cross_frame, check_clip_length, check_cross_frame
@@ -73,7 +76,8 @@ class AnimateDiffDenoiser:
                  scheduler: Optional[EulerDiscreteScheduler] = None, use_graph: bool = True, shard=None,
                  num_clips: int = 1, context_length: Optional[int] = None, context_stride: int = 4,
                  context_weighting: str = "pyramid", cross_frame=None, sampler: str = "euler",
-                 guidance_rescale: float = 0.0, eta: float = 1.0, freeu=None, free_init=None):
+                 guidance_rescale: float = 0.0, eta: float = 1.0, freeu=None, free_init=None,
+                 token_merging=None):
         """`num_clips` clips are denoised together (the reference loop is one clip, B=1).
         `shard` (frame_shard.FrameShard): this process denoises frames [f0, f0 + F/P) of every clip and
         exchanges with the other ranks inside every motion module.
@@ -101,7 +105,11 @@ class AnimateDiffDenoiser:
         `free_init` (a free_init.FreeInit, a dict of its fields or its tuple): FreeInit, diffusers'
         enable_free_init.  A call (`__call__`) then runs the whole loop num_iters times, with the frequency mix of
         kernels.free_init_mix between two passes.  It transforms whole clips, so a frame shard of more than one rank
-        is refused, and so is a source run; num_iters 1 or None is the plain run, launch for launch."""
+        is refused, and so is a source run; num_iters 1 or None is the plain run, launch for launch.
+        `token_merging` (a token_merge.TokenMerging, a dict of its fields or a ratio): token merging in
+        the spatial transformer blocks, tomesd's apply_patch.  None takes what unet.enable_token_merging set, if
+        anything.  With use_rand the destination pattern is drawn from the noise seed (set_noise_seed, or the `seed` of
+        a call) and the device step counter, so it changes per step under replay; ratio 0 is the plain step."""
         self.guidance_rescale = check_sampler(sampler, guidance_scale, guidance_rescale, shard, eta, scheduler)
         check_freeu_arg(freeu)
         check_free_init_arg(free_init)
@@ -169,6 +177,11 @@ class AnimateDiffDenoiser:
             if self.guidance_rescale > 0.0:
                 self.factor = torch.ones(num_clips, dtype=torch.float32, device=dev)
                 self.rescale_ws = K.cfg_rescale_workspace(self.lat.shape, dev)
+        # token merging: refused here, before anything is captured; its destination draw reads the
+        # sampler's noise seed where there is one, else a seed of its own, and this denoiser's step counter
+        self.token_merging = self.tm_seed = None
+        self._set_token_merging(getattr(unet, "token_merging", None) if token_merging is None
+                                else as_token_merging(token_merging))
         # FreeInit: the latents the run was entered with, the mask in DFT order, the seed and the
         # counter of the fresh noise and the spectrum workspace; static device buffers, allocated when it is turned on
         self.free_init = None
@@ -204,7 +217,8 @@ class AnimateDiffDenoiser:
         emb = self.unet.embed(self.timesteps, self.pooled, self.time_ids, B, step_idx=self.step_idx)
         noise = self.unet.forward_tokens(self.x, B, self.F, self.h, self.w, emb, self.enc, shard=self.shard,
                                          temporal_context=self.context, cross_frame=self.cross_frame,
-                                         lora_gate=self.lora_gate, freeu=self.freeu, image_prompt=self.image_prompt)
+                                         lora_gate=self.lora_gate, freeu=self.freeu, image_prompt=self.image_prompt,
+                                         token_merging=self.token_merging)
         if self.table_step:
             if self.factor is not None:
                 K.cfg_rescale_factor(noise, self.lat.shape, guidance=self.guidance, phi=self.guidance_rescale,
@@ -400,6 +414,29 @@ class AnimateDiffDenoiser:
             self.freeu = None
             self.graph = None
 
+    def _set_token_merging(self, tm: Optional[TokenMerging]):
+        check_token_merging(self.unet, tm, (self.h, self.w))
+        if tm is not None and tm.use_rand:
+            if self.tm_seed is None:
+                self.tm_seed = self.noise_seed if self.noise_seed is not None else torch.zeros(
+                    1, dtype=torch.int64, device=self.device)
+            tm.bind(self.tm_seed, self.step_idx)
+        self.token_merging = tm
+        self.graph = None
+
+    def enable_token_merging(self, ratio: float = 0.5, max_downsample: int = 2, sx: int = 2, sy: int = 2,
+                             use_rand: bool = True, merge_attn: bool = True, merge_crossattn: bool = False,
+                             merge_mlp: bool = False):
+        """tomesd.apply_patch's arguments for the steps that follow (token_merge.TokenMerging).  Drops a
+        captured step: the merged blocks run other launches."""
+        self._set_token_merging(TokenMerging(ratio, max_downsample, sx, sy, use_rand, merge_attn, merge_crossattn,
+                                             merge_mlp))
+
+    def disable_token_merging(self):
+        """Back to the plain step (drops a captured step with merged blocks)."""
+        if self.token_merging is not None:
+            self._set_token_merging(None)
+
     def _set_free_init(self, fi: FreeInit):
         check_free_init_run(fi, self.shard)
         F, h, w = self.lat.shape[2:]
@@ -540,6 +577,9 @@ class AnimateDiffDenoiser:
         check_free_init_run(fi, self.shard, source is not None)
         if self.noise_seed is not None:
             self.set_noise_seed(seed)
+        elif self.tm_seed is not None:
+            v = int(seed) & (2 ** 64 - 1)
+            self.tm_seed.fill_(v - 2 ** 64 if v >= 2 ** 63 else v)  # the same 64 bits as an int64
         if content_scale is not None or style_scale is not None:
             self.set_lora_gates(1.0 if content_scale is None else content_scale,
                                 1.0 if style_scale is None else style_scale)

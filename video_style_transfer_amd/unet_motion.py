@@ -29,10 +29,11 @@ import torch
 from torch import nn
 
 from . import kernels as K
-from .attention_processor import Attention, input_lora_ops
+from .attention_processor import AnimateDiffAttnProcessor2_0, Attention, input_lora_ops
 from .config import UNetMotionConfig
 from .freeu import FreeU, as_freeu
 from .lora_linear import LoRACompatibleLinear, build_ops, lora_in_gemm, run_ops
+from .token_merge import TokenMerging, as_token_merging, check_token_merging
 from .weights import sinusoid_table
 
 BF16 = torch.bfloat16
@@ -270,6 +271,9 @@ class FwdCtx:
     lora_gate: Optional[object] = None  # lora_gate.LoraGate ([B * F] rows): per-frame content / style strength
     freeu: Optional[FreeU] = None       # backbone scale + skip filter before the skip concats of up stages 0 and 1
     image_prompt: Optional[object] = None  # ip_adapter.ImagePrompt ([B * F] rows): image tokens of the attn2 layers
+    token_merging: Optional[TokenMerging] = None  # merge tokens around attn1 / the FF of the spatial blocks (§22)
+    latent_hw: Optional[tuple] = None   # the latent's (h, w): a block's down-sampling level is measured against it
+    spatial_hw: Optional[tuple] = None  # the (H, W) of the tokens of the Transformer2DModel being run (the cells' grid)
 
 
 # --------------------------------------------------------------------------------------- blocks
@@ -330,7 +334,8 @@ class BasicTransformerBlock(nn.Module):
             self.pos_embed = _SinusoidalPE(dim, max_seq_length)
 
     def run(self, x, nimg, N, ctx: FwdCtx):
-        """x: [nimg*N, C] -> same."""
+        """x: [nimg*N, C] -> same.  A spatial block merges tokens (ctx.token_merging) only where ctx.spatial_hw gives
+        the (H, W) of its N tokens: the cells are cut on that grid."""
         C = x.shape[1]
         if self.temporal:
             pe = f32(self.pos_embed.pe).view(-1, C)
@@ -353,19 +358,48 @@ class BasicTransformerBlock(nn.Module):
             x = self.attn2(n.view(nimg, N, C), num_frames=ctx.F, _vst_residual=x).view(-1, C)
         else:
             scale = ctx.cross_kwargs.get("scale", 1.0)
-            n, u = self.norm1.run_lora(x, input_lora_ops(self.attn1, True, scale))
             cf = ctx.cross_frame
             kw = dict(_vst_cross_frame=(cf, ctx.F)) if cf is not None and cf.active(ctx.F) else {}
             gkw = dict(_vst_lora_gate=ctx.lora_gate) if ctx.lora_gate is not None else {}
-            x = self.attn1(n.view(nimg, N, C), _vst_residual=x, _vst_lora_u=u, **kw, **gkw,
-                           **ctx.cross_kwargs).view(-1, C)
+            tm, plan = self._token_merging(x, nimg, N, ctx)
+            if plan is not None and tm.merge_attn:
+                # attn1 on the merged rows (no fused residual, the LoRA down-projection inside the GEMM); every token
+                # then takes the row it went to, on top of the block's residual
+                m = tm.merge(plan, self.norm1.run(x))
+                o = self.attn1(m.view(nimg, N - plan.r, C), _vst_residual=None, _vst_lora_u=None, **kw, **gkw,
+                               **ctx.cross_kwargs).view(-1, C)
+                x = tm.unmerge_add(plan, o, x)
+            else:
+                n, u = self.norm1.run_lora(x, input_lora_ops(self.attn1, True, scale))
+                x = self.attn1(n.view(nimg, N, C), _vst_residual=x, _vst_lora_u=u, **kw, **gkw,
+                               **ctx.cross_kwargs).view(-1, C)
             n, u = self.norm2.run_lora(x, input_lora_ops(self.attn2, False, scale))
             if ctx.image_prompt is not None:
                 gkw = dict(gkw, _vst_image_prompt=ctx.image_prompt)
             x = self.attn2(n.view(nimg, N, C), encoder_hidden_states=ctx.enc, _vst_residual=x, _vst_lora_u=u, **gkw,
                            **ctx.cross_kwargs).view(-1, C)
+            if plan is not None and tm.merge_mlp:
+                m = tm.merge(plan, self.norm3.run(x))
+                return tm.unmerge_add(plan, self.ff.run(m, residual=None), x)
         n = self.norm3.run(x)
         return self.ff.run(n, residual=x)
+
+    def _token_merging(self, x, nimg, N, ctx: FwdCtx):
+        """(the option, this block's plan computed from its input x), or (None, None) where the block runs as without
+        the option: off, ratio 0, no tokens to merge, or a level above max_downsample."""
+        tm, hw = ctx.token_merging, ctx.spatial_hw
+        if tm is None or hw is None or hw[0] * hw[1] != N or not tm.enabled:
+            return None, None
+        H, W = hw
+        lat = ctx.latent_hw or hw
+        if not tm.active(lat[0] * lat[1], N) or tm.sizes(H, W)[3] == 0:
+            return None, None
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise K._lib.VstError("token_merging: inference only; the training path (autograd) has no merged backward")
+        if tm.merge_attn and not isinstance(self.attn1.processor, AnimateDiffAttnProcessor2_0):
+            raise K._lib.VstError(f"token_merging: attn1 has a {type(self.attn1.processor).__name__}; the merged "
+                                  f"attention runs through AnimateDiffAttnProcessor2_0")
+        return tm, tm.match(self.__dict__.get("_vst_tome_layer", 0), x, nimg, H, W)
 
 
 class _SinusoidalPE(nn.Module):
@@ -388,6 +422,8 @@ class Transformer2DModel(nn.Module):
     def run(self, x, nimg, H, W, ctx):
         h = self.norm.run(x, nimg, H * W)
         h = self.proj_in.run(h)
+        if ctx.token_merging is not None:
+            ctx = dataclasses.replace(ctx, spatial_hw=(H, W))
         for blk in self.transformer_blocks:
             h = blk.run(h, nimg, H * W, ctx)
         return self.proj_out.run(h, residual=x)
@@ -662,6 +698,7 @@ class UNetMotionModel(nn.Module):
         self.conv_norm_out = GroupNorm(cfg.norm_num_groups, ch[0], eps=cfg.norm_eps)
         self.conv_out = Conv3x3(ch[0], cfg.out_channels)
         self.freeu = None  # enable_freeu: the default of forward()
+        self.token_merging = None  # enable_token_merging: the default of forward()
 
     # ---- diffusers surface ----------------------------------------------------------------
     @property
@@ -694,6 +731,17 @@ class UNetMotionModel(nn.Module):
 
     def disable_freeu(self):
         self.freeu = None
+
+    def enable_token_merging(self, ratio: float = 0.5, max_downsample: int = 2, sx: int = 2, sy: int = 2,
+                             use_rand: bool = True, merge_attn: bool = True, merge_crossattn: bool = False,
+                             merge_mlp: bool = False):
+        """Token merging (tomesd.apply_patch's arguments; token_merge.TokenMerging) for every later
+        forward() that is given no `token_merging=`.  Inference only."""
+        self.token_merging = TokenMerging(ratio, max_downsample, sx, sy, use_rand, merge_attn, merge_crossattn,
+                                          merge_mlp)
+
+    def disable_token_merging(self):
+        self.token_merging = None
 
     def set_ip_adapter_scale(self, scale):
         """The weight of the image term of the IP-Adapter layers (ip_adapter.load_ip_adapter): a float, or
@@ -736,7 +784,8 @@ class UNetMotionModel(nn.Module):
 
     # ---- core (NHWC tokens) -----------------------------------------------------------------
     def forward_tokens(self, x, B, F, h, w, emb_silu, enc, cross_kwargs=None, shard=None, fusion_world=None,
-                       temporal_context=None, cross_frame=None, lora_gate=None, freeu=None, image_prompt=None):
+                       temporal_context=None, cross_frame=None, lora_gate=None, freeu=None, image_prompt=None,
+                       token_merging=None):
         """x: [B*F*h*w, in_channels] bf16 -> noise prediction [B*F*h*w, out_channels] bf16.
         With `shard` (frame_shard.FrameShard), F is this rank's frames of each clip.  `fusion_world` P (default: the
         shard's world size, else 1): take the shape-dependent fusion decisions a P-way frame-sharded rank takes
@@ -748,9 +797,13 @@ class UNetMotionModel(nn.Module):
         its (s1, s2, b1, b2)): FreeU in the first two up blocks; None runs today's launches.  Here
         None means off: the enable_freeu default is applied by forward().  `image_prompt` (ip_adapter.ImagePrompt with
         B * F rows): the image tokens of the IP-Adapter attn2 layers (load_ip_adapter); required when
-        they are installed, refused when they are not."""
+        they are installed, refused when they are not.  `token_merging` (token_merge.TokenMerging, a dict of its
+        fields or a ratio): the spatial blocks up to its max_downsample merge tokens around attn1 (and the
+        feed-forward); None, as for freeu, means off here."""
         from .ip_adapter import check_forward  # (local import: ip_adapter imports the attention processors)
         check_forward(self, image_prompt, B * F, lora_gate)
+        token_merging = as_token_merging(token_merging)
+        check_token_merging(self, token_merging, (h, w), x)
         freeu = as_freeu(freeu, x.device)
         cross_frame = as_cross_frame(cross_frame)
         check_cross_frame(self, F * (shard.world if shard is not None else 1), cross_frame, shard, (h, w))
@@ -764,7 +817,7 @@ class UNetMotionModel(nn.Module):
         # no split-K: a row's bits do not depend on the launch's row count (frame shards)
         with K.row_invariant(), K.fusion_world(fusion_world):
             ctx = FwdCtx(B, F, emb_silu, enc, cross_kwargs or {}, shard, self.batched_temb(emb_silu),
-                         temporal_context, cross_frame, lora_gate, freeu, image_prompt)
+                         temporal_context, cross_frame, lora_gate, freeu, image_prompt, token_merging, (h, w))
             nimg = B * F
             H, W = h, w
             x = self.conv_in.run(x, nimg, H, W)
@@ -781,14 +834,15 @@ class UNetMotionModel(nn.Module):
     def forward(self, sample, timestep, encoder_hidden_states, timestep_cond=None, attention_mask=None,
                 cross_attention_kwargs=None, added_cond_kwargs=None, return_dict=True, frame_shard=None,
                 fusion_world=None, temporal_context=None, cross_frame=None, lora_gate=None, freeu=None,
-                image_prompt=None, **kwargs):
+                image_prompt=None, token_merging=None, **kwargs):
         """diffusers UNetMotionModel.forward signature (inference_animatediff.py:110-121).  With
         `frame_shard` (frame_shard.FrameShard) `sample` holds this rank's frames of each clip; `fusion_world`: see
         forward_tokens; `temporal_context` (TemporalContext): the motion modules attend inside sliding windows when the
         clip is longer than its length; `cross_frame` (CrossFrameAttention or its sources, e.g. ("first",)): attn1 of the
         spatial transformer blocks also attends to the source frames of the same clip; `lora_gate`: see
         forward_tokens; `freeu` (FreeU or (s1, s2, b1, b2)): FreeU for this call, default what enable_freeu set;
-        `image_prompt` (ip_adapter.ImagePrompt): see forward_tokens."""
+        `image_prompt` (ip_adapter.ImagePrompt): see forward_tokens; `token_merging` (TokenMerging, a dict of its fields
+        or a ratio): token merging for this call, default what enable_token_merging set."""
         if not sample.is_cuda:
             raise K._lib.VstError("UNetMotionModel: sample is on CPU; the HIP path has no CPU fallback")
         B, Cin, F, h, w = sample.shape
@@ -798,6 +852,8 @@ class UNetMotionModel(nn.Module):
         check_cross_frame(self, F * (frame_shard.world if frame_shard is not None else 1), cross_frame,
                           frame_shard, (h, w))
         freeu = as_freeu(self.freeu if freeu is None else freeu, sample.device)  # bad values: before any launch
+        token_merging = as_token_merging(self.token_merging if token_merging is None else token_merging)
+        check_token_merging(self, token_merging, (h, w), sample)
         if self.config.motion_modules:
             check_clip_length(F * (frame_shard.world if frame_shard is not None else 1),
                               self.config.motion_max_seq_length, temporal_context)
@@ -816,6 +872,6 @@ class UNetMotionModel(nn.Module):
         y = self.forward_tokens(x, B, F, h, w, emb_silu, enc, cross_attention_kwargs, shard=frame_shard,
                                 fusion_world=fusion_world, temporal_context=temporal_context,
                                 cross_frame=cross_frame, lora_gate=lora_gate,
-                                freeu=freeu, image_prompt=image_prompt)
+                                freeu=freeu, image_prompt=image_prompt, token_merging=token_merging)
         out = y.view(B, F, h, w, -1).permute(0, 4, 1, 2, 3).contiguous().to(sample.dtype)
         return UNetMotionOutput(out) if return_dict else (out,)
