@@ -134,8 +134,11 @@ def test_option_refuses_a_level_below_two_tokens():
     """The tiny UNet halves the latent once per down block: a 2 x 1 latent leaves its deepest level one token."""
     from video_style_transfer_amd import _lib
     from video_style_transfer_amd.config import UNetMotionConfig
-    from video_style_transfer_amd.unet_motion import (CrossFrameAttention, UNetMotionModel, check_cross_frame,
-                                                      spatial_attention_tokens)
+    from video_style_transfer_amd.token_merge import spatial_levels
+    from video_style_transfer_amd.unet_motion import CrossFrameAttention, UNetMotionModel, check_cross_frame
+
+    def spatial_attention_tokens(model, h, w):
+        return [H * W for (H, W), _ in spatial_levels(model, h, w)]
     model = UNetMotionModel(UNetMotionConfig.tiny())
     tok = spatial_attention_tokens(model, 16, 16)
     assert max(tok) <= 256 and min(tok) >= 2 and min(tok) < max(tok)

@@ -238,7 +238,7 @@ def test_status_codes_before_any_launch(cuda, K, cases):
 def test_processor_fused_text_path_plus_image_add(cuda, K):
     from test_gemm_xattn_gpu import check
     from video_style_transfer_amd import attention_processor as AP
-    from video_style_transfer_amd.attention_processor import Attention
+    from video_style_transfer_amd.attention_processor import AttnCall, Attention
     from video_style_transfer_amd.ip_adapter import IPAdapterAttnProcessor2_0, ImagePrompt
     from video_style_transfer_amd.utils import attach_unziplora_layers
     torch.manual_seed(3)
@@ -261,15 +261,15 @@ def test_processor_fused_text_path_plus_image_add(cuda, K):
     enc = torch.randn(2, 77, 2048, device=cuda).to(BF16)
     tokens = torch.randn(2, 4, 2048, device=cuda).to(BF16)
     prompt = ImagePrompt(tokens, 2)
-    proc(attn, x, encoder_hidden_states=enc, _vst_image_prompt=prompt)   # projects the text K/V and folds the keys
-    o_fused, kinds = profiled(K, lambda: proc(attn, x, encoder_hidden_states=enc, _vst_image_prompt=prompt))
+    proc(attn, x, encoder_hidden_states=enc, _vst=AttnCall(image_prompt=prompt))   # projects the text K/V and folds the keys
+    o_fused, kinds = profiled(K, lambda: proc(attn, x, encoder_hidden_states=enc, _vst=AttnCall(image_prompt=prompt)))
     i = kinds.index("gemm_xattn")
     assert kinds[i + 1] == "ip_attention_add" and kinds.count("ip_attention_add") == 1, kinds
     assert "spatial_attention" not in kinds
     orig = AP._cross_fusable
     AP._cross_fusable = lambda *a, **k: False
     try:
-        o_two, kinds2 = profiled(K, lambda: proc(attn, x, encoder_hidden_states=enc, _vst_image_prompt=prompt))
+        o_two, kinds2 = profiled(K, lambda: proc(attn, x, encoder_hidden_states=enc, _vst=AttnCall(image_prompt=prompt)))
     finally:
         AP._cross_fusable = orig
     assert "gemm_xattn" not in kinds2 and kinds2[kinds2.index("spatial_attention") + 1] == "ip_attention_add"
@@ -285,7 +285,7 @@ def test_processor_fused_text_path_plus_image_add(cuda, K):
     plain = AP.AnimateDiffAttnProcessor2_0()(attn, x, encoder_hidden_states=enc)
     assert rel(o_fused, plain) > 2e-2
     proc.scale = 0.0
-    o_zero, kinds0 = profiled(K, lambda: proc(attn, x, encoder_hidden_states=enc, _vst_image_prompt=prompt))
+    o_zero, kinds0 = profiled(K, lambda: proc(attn, x, encoder_hidden_states=enc, _vst=AttnCall(image_prompt=prompt)))
     assert "ip_attention_add" not in kinds0 and torch.equal(bits(o_zero), bits(plain))
 
 

@@ -434,7 +434,7 @@ def test_processor_per_frame_gates_equal_uniform_runs(cuda, K, cross):
     in-GEMM gate for to_out; attn2 the fused gated cross-attention launch, with per-frame text K/V.  Run as the
     UNet runs it, under K.row_invariant (a row's bits do not depend on the launch's row count: the gated text K/V
     are projected for 6 x 77 rows, the plain ones for 2 x 77)."""
-    from video_style_transfer_amd.attention_processor import AnimateDiffAttnProcessor2_0
+    from video_style_transfer_amd.attention_processor import AnimateDiffAttnProcessor2_0, AttnCall
     from video_style_transfer_amd.lora_gate import LoraGate
     attn = _attention(cuda, 128 if cross else None, 5 + cross)
     proc = AnimateDiffAttnProcessor2_0()
@@ -446,7 +446,7 @@ def test_processor_per_frame_gates_equal_uniform_runs(cuda, K, cross):
     gate = LoraGate(6, cuda).set(pairs[:, 0], pairs[:, 1])
     K.profile_launches(True)
     with K.row_invariant():
-        out = proc(attn, x, encoder_hidden_states=enc, _vst_residual=res, _vst_lora_gate=gate)
+        out = proc(attn, x, encoder_hidden_states=enc, _vst=AttnCall(residual=res, lora_gate=gate))
     rec = K.collect_launches()
     K.profile_launches(False)
     syms = [r[1] for r in rec]
@@ -456,15 +456,15 @@ def test_processor_per_frame_gates_equal_uniform_runs(cuda, K, cross):
     else:
         assert "lora_gate" in [r[0] for r in rec], rec
     with K.row_invariant():
-        plain = proc(attn, x, encoder_hidden_states=enc, _vst_residual=res)
+        plain = proc(attn, x, encoder_hidden_states=enc, _vst=AttnCall(residual=res))
         assert not torch.equal(out, plain) and torch.equal(out[0], plain[0])  # frame 0 has gates (1, 1)
         for f in range(6):
             uni = LoraGate(6, cuda).set(float(pairs[f, 0]), float(pairs[f, 1]))
-            ref = proc(attn, x, encoder_hidden_states=enc, _vst_residual=res, _vst_lora_gate=uni)
+            ref = proc(attn, x, encoder_hidden_states=enc, _vst=AttnCall(residual=res, lora_gate=uni))
             assert torch.equal(out[f], ref[f]), f
     from video_style_transfer_amd._lib import VstError
     with pytest.raises(VstError):
-        proc(attn, x, encoder_hidden_states=enc, _vst_residual=res, _vst_lora_gate=LoraGate(4, cuda))
+        proc(attn, x, encoder_hidden_states=enc, _vst=AttnCall(residual=res, lora_gate=LoraGate(4, cuda)))
 
 
 def test_text_kv_reprojects_in_place_when_gates_change(cuda, K):

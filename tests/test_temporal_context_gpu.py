@@ -195,7 +195,7 @@ def test_windowed_motion_module_vs_fp32(cuda, K, C):
     UNWINDOWED module's error against oracle.unet.motion_module at F = 16 on the same weights (existing code)."""
     from oracle import unet as OU
     from test_temporal_context import motion_params, windowed_motion_module
-    from video_style_transfer_amd.unet_motion import FwdCtx, TemporalContext
+    from video_style_transfer_amd.unet_motion import ForwardOptions, FwdCtx, TemporalContext
     B, Fr, H, W = 2, 20, 4, 4
     P = motion_params(C, seed=C)
     mm = _device_motion_module(P, C, cuda)
@@ -205,12 +205,13 @@ def test_windowed_motion_module_vs_fp32(cuda, K, C):
 
     out16 = mm.run(_tokens(x16).to(cuda, BF16), B * 16, H, W, FwdCtx(B, 16, None, None, {}))
     e16 = rel(out16, _tokens(OU.motion_module(P, "mm", x16, 16)))
-    out = mm.run(_tokens(x).to(cuda, BF16), B * Fr, H, W, FwdCtx(B, Fr, None, None, {}, temporal_context=tc))
+    windowed = ForwardOptions(temporal_context=tc)
+    out = mm.run(_tokens(x).to(cuda, BF16), B * Fr, H, W, FwdCtx(B, Fr, None, None, {}, opts=windowed))
     e_win = rel(out, _tokens(windowed_motion_module(P, "mm", x, Fr, 16, 4, "pyramid")))
     print(f"[context] motion module C={C}: windowed F=20 rel_l2={e_win:.3e}, unwindowed F=16 rel_l2={e16:.3e}")
     assert e_win <= 1.25 * e16 + 2e-3, (e_win, e16)
     # an inactive context (F <= length) launches exactly what no context launches
-    same = mm.run(_tokens(x16).to(cuda, BF16), B * 16, H, W, FwdCtx(B, 16, None, None, {}, temporal_context=tc))
+    same = mm.run(_tokens(x16).to(cuda, BF16), B * 16, H, W, FwdCtx(B, 16, None, None, {}, opts=windowed))
     assert torch.equal(same, out16)
 
 

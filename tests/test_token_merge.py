@@ -187,11 +187,12 @@ def test_defaults_mirror_tomesd_and_surface():
     import inspect
     from video_style_transfer_amd.pipeline import AnimateDiffDenoiser
     from video_style_transfer_amd.token_merge import TokenMerging, as_token_merging
-    from video_style_transfer_amd.unet_motion import FwdCtx, UNetMotionModel
+    from video_style_transfer_amd.unet_motion import ForwardOptions, FwdCtx, UNetMotionModel
     tm = TokenMerging()
     assert (tm.ratio, tm.max_downsample, tm.sx, tm.sy, tm.use_rand, tm.merge_attn, tm.merge_crossattn,
             tm.merge_mlp) == (0.5, 2, 2, 2, True, True, False, False)
-    assert "token_merging" in [f.name for f in dataclasses.fields(FwdCtx)]
+    assert "token_merging" in [f.name for f in dataclasses.fields(ForwardOptions)]   # carried by FwdCtx.opts
+    assert isinstance(FwdCtx(1, 1, None, None, {}).opts, ForwardOptions)
     assert "token_merging" in inspect.signature(AnimateDiffDenoiser.__init__).parameters
     assert "token_merging" in inspect.signature(UNetMotionModel.forward).parameters
     assert hasattr(UNetMotionModel, "enable_token_merging") and hasattr(UNetMotionModel, "disable_token_merging")

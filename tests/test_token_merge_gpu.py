@@ -391,9 +391,10 @@ def rel(a, b):
 
 
 def run_block(K, cuda, blk, x, enc, H, W, Fr, tm, gate=None, cross_frame=None):
-    from video_style_transfer_amd.unet_motion import FwdCtx
+    from video_style_transfer_amd.unet_motion import ForwardOptions, FwdCtx
     nimg, N, C = x.shape
-    ctx = FwdCtx(nimg // Fr, Fr, None, enc.to(cuda), {}, cross_frame=cross_frame, lora_gate=gate, token_merging=tm,
+    ctx = FwdCtx(nimg // Fr, Fr, None, enc.to(cuda), {},
+                 opts=ForwardOptions(cross_frame=cross_frame, lora_gate=gate, token_merging=tm),
                  latent_hw=(2 * H, 2 * W), spatial_hw=(H, W))
     with K.row_invariant():
         out = blk.run(x.reshape(nimg * N, C).to(cuda), nimg, N, ctx)
@@ -462,11 +463,11 @@ def test_block_refuses_another_processor_and_autograd(cuda, K, block):
         with pytest.raises(K._lib.VstError, match="AnimateDiffAttnProcessor2_0"):
             run_block(K, cuda, blk, x, enc, 8, 8, 2, TokenMerging())
         blk.attn1.set_processor(keep)
-        from video_style_transfer_amd.unet_motion import FwdCtx
+        from video_style_transfer_amd.unet_motion import ForwardOptions, FwdCtx
         xg = x.reshape(128, 640).to(cuda).requires_grad_(True)
         with pytest.raises(K._lib.VstError, match="inference only"):
-            blk.run(xg, 2, 64, FwdCtx(1, 2, None, enc.to(cuda), {}, token_merging=TokenMerging(), latent_hw=(16, 16),
-                                      spatial_hw=(8, 8)))
+            blk.run(xg, 2, 64, FwdCtx(1, 2, None, enc.to(cuda), {}, opts=ForwardOptions(token_merging=TokenMerging()),
+                                      latent_hw=(16, 16), spatial_hw=(8, 8)))
         assert K.collect_launches() == []
     finally:
         blk.attn1.set_processor(keep)

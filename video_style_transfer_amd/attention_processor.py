@@ -14,13 +14,15 @@
   (inference_animatediff.py:211-215): frame-axis self-attention -> vst_temporal_attention.
 
 Hidden-state layout.  Spatial: (B*F, H*W, C).  Motion: the reference/diffusers permute to
-(B*H*W, F, C); our blocks keep (B*F, H*W, C) and pass `num_frames=F`, the kernel reads the frame
-axis with stride H*W.  Both layouts are accepted by AttnProcessor2_0 (without `num_frames` the
-input is taken as (batch, seq=F, C), the diffusers layout).
+(B*H*W, F, C); our blocks keep (B*F, H*W, C) and pass the frame count (`AttnCall.frames`; a caller
+without an AttnCall passes `num_frames=F`), the kernel reads the frame axis with stride H*W.  Both
+layouts are accepted by AttnProcessor2_0 (given neither, the input is taken as (batch, seq=F, C),
+the diffusers layout).
 """
 from __future__ import annotations
 
 import os
+from dataclasses import dataclass
 from typing import Optional
 
 import torch
@@ -30,6 +32,22 @@ from torch import nn
 from . import kernels as K
 from .lora_linear import LoRACompatibleLinear, build_ops, gate_operands, run_ops
 
+
+@dataclass
+class AttnCall:
+    """What the UNet's blocks hand a processor beside diffusers' arguments, as the one keyword `_vst` (DESIGN.md
+    §23).  A processor called without it is being called the diffusers way: ip_adapter's then finds the image tokens
+    at the end of encoder_hidden_states, AttnProcessor2_0 takes the (B*HW, F, C) layout unless given `num_frames`."""
+    residual: Optional[torch.Tensor] = None  # the block's residual, added in to_out's epilogue
+    lora_u: Optional[torch.Tensor] = None    # x @ Acat^T of the q(/k/v) ops, from K.layer_norm_lora
+    frames: Optional[int] = None             # frames per clip, where the attention reads the frame axis
+    cross_frame: Optional[object] = None     # attn1 only: an active unet_motion.CrossFrameAttention (needs `frames`)
+    lora_gate: Optional[object] = None       # lora_gate.LoraGate, one row per image of the batch
+    image_prompt: Optional[object] = None    # attn2 only: ip_adapter.ImagePrompt
+    context: Optional[tuple] = None          # motion modules: (TemporalContext, fp32 PE table); the input carries no PE
+
+
+_NO_CALL = AttnCall()
 
 class Attention(nn.Module):
     def __init__(self, query_dim: int, cross_attention_dim: Optional[int] = None, heads: int = 8,
@@ -97,12 +115,9 @@ class AnimateDiffAttnProcessor2_0:
             raise ImportError("AnimateDiffAttnProcessor2_0 requires PyTorch 2.0+.")
 
     def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None, scale=1.0,
-                 **kwargs):
-        fused_residual = kwargs.pop("_vst_residual", None)
-        lora_u = kwargs.pop("_vst_lora_u", None)  # x @ Acat^T of the q(/k/v) ops, from K.layer_norm_lora
-        cross_frame = kwargs.pop("_vst_cross_frame", None)  # attn1 only: (CrossFrameAttention, frames per clip)
-        gate = kwargs.pop("_vst_lora_gate", None)  # lora_gate.LoraGate, one row per image of the batch
-        image_prompt = kwargs.pop("_vst_image_prompt", None)  # attn2 only: ip_adapter.ImagePrompt
+                 _vst: Optional[AttnCall] = None, **kwargs):
+        call = _vst if _vst is not None else _NO_CALL
+        lora_u, cf, gate = call.lora_u, call.cross_frame, call.lora_gate
         if gate is not None and gate.rows != hidden_states.shape[0]:
             raise K._lib.VstError(f"LoRA gate: {gate.rows} rows for a batch of {hidden_states.shape[0]} images")
         if attn.spatial_norm is not None or attn.group_norm is not None or attn.norm_cross:
@@ -119,12 +134,12 @@ class AnimateDiffAttnProcessor2_0:
         hd = inner // heads
         x = hidden_states.reshape(batch * N, C)
         if encoder_hidden_states is None:
-            if cross_frame is not None and hd != 64:
+            if cf is not None and hd != 64:
                 raise K._lib.VstError("cross_frame: the cross-frame attention kernel is specialised for head_dim 64")
             qkv = run_ops(x, build_ops([attn.to_q, attn.to_k, attn.to_v], s), u=lora_u, gate=gate)
-            if cross_frame is not None:
+            if cf is not None:
                 # the frame's own tokens plus those of the source frames of the same clip, read in place
-                cf, Fr = cross_frame
+                Fr = call.frames
                 if cf.adain is not None:
                     # StyleAligned: q | k (| v) normalised per column to the anchor frame's statistics, in place
                     K.frame_adain(qkv[:, :cf.adain_blocks * inner], batch // Fr, Fr, N, cf.anchor)
@@ -156,8 +171,8 @@ class AnimateDiffAttnProcessor2_0:
                 q = run_ops(x, q_ops, u=lora_u, gate=gate)
                 o = K.spatial_attention(q, kv[:, :inner], kv[:, inner:], batch, heads, N, L, kv_div,
                                         scale=hd ** -0.5)
-            o = self._image_attention(attn, x, o, q_ops, batch, N, image_prompt, gate)
-        res2d = None if fused_residual is None else fused_residual.reshape(batch * N, -1)
+            o = self._image_attention(attn, x, o, q_ops, batch, N, call.image_prompt, gate)
+        res2d = None if call.residual is None else call.residual.reshape(batch * N, -1)
         out = run_ops(o, build_ops([attn.to_out[0]], s), residual=res2d, gate=gate)
         out = out.view(batch, N, -1)
         if input_ndim == 4:
@@ -271,7 +286,7 @@ def _context_table(attn, ops, pe, length):
     """fp32 [length, 3C] = pe[:length] @ Wqkv^T (LoRA factors included, bias not): what the positional term adds to
     q/k/v by linearity, so the windowed kernel adds it per window position behind ONE projection per frame.  Cached on
     the module against the fused operand it was made from, like _tattn_operands."""
-    c = attn.__dict__.get("_vst_context_table")
+    c = attn.__dict__.get("_vst_window_pos")
     if c is None or c[0] is not ops or c[1] != length or c[2] != pe.data_ptr():
         with torch.no_grad():
             w = ops.w.float()
@@ -280,7 +295,7 @@ def _context_table(attn, ops, pe, length):
             if ops.a is not None:
                 t = t + (p @ ops.a.float().t()) @ w[:, ops.k1:].t()
         c = (ops, length, pe.data_ptr(), t.contiguous())
-        attn.__dict__["_vst_context_table"] = c
+        attn.__dict__["_vst_window_pos"] = c
     return c[3]
 
 
@@ -288,9 +303,9 @@ class AttnProcessor2_0:
     """Default (motion-module) processor: self-attention along the frame axis."""
 
     def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None,
-                 num_frames: Optional[int] = None, **kwargs):
-        fused_residual = kwargs.pop("_vst_residual", None)
-        context = kwargs.pop("_vst_context", None)  # (TemporalContext, fp32 PE table): hidden_states carry no PE
+                 num_frames: Optional[int] = None, _vst: Optional[AttnCall] = None, **kwargs):
+        call = _vst if _vst is not None else AttnCall(frames=num_frames)
+        num_frames, context = call.frames, call.context
         if encoder_hidden_states is not None or attention_mask is not None:
             raise NotImplementedError("motion-module attention is self-attention without mask")
         batch, N, C = hidden_states.shape
@@ -325,6 +340,6 @@ class AttnProcessor2_0:
             qkv = run_ops(x, ops)
             o = K.temporal_attention(qkv[:, :inner], qkv[:, inner:2 * inner], qkv[:, 2 * inner:], nclip, Fr, HW,
                                      heads, D)
-        res2d = None if fused_residual is None else fused_residual.reshape(batch * N, -1)
+        res2d = None if call.residual is None else call.residual.reshape(batch * N, -1)
         out = run_ops(o, build_ops([attn.to_out[0]], 1.0), residual=res2d).view(batch, N, -1)
         return _finish(attn, out, hidden_states)

@@ -26,7 +26,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import kernels as K
-from .attention_processor import AnimateDiffAttnProcessor2_0, Attention
+from .attention_processor import AnimateDiffAttnProcessor2_0, AttnCall, Attention
 from .lora_linear import build_ops, run_ops
 
 BF16 = torch.bfloat16
@@ -144,8 +144,9 @@ class ImagePrompt:
 class IPAdapterAttnProcessor2_0(nn.Module, AnimateDiffAttnProcessor2_0):
     """unzip_attention_processor.py:1693-1822 on the kernels: AnimateDiffAttnProcessor2_0's attn2 (text K/V cached per
     clip, q + cross-attention in one launch where it fits) plus vst_ip_attention_add for the image tokens.
-    Called by the UNet it takes the tokens from `_vst_image_prompt` (ImagePrompt) and plain text states; called
-    directly, as the reference is, the last num_tokens rows of encoder_hidden_states are the image tokens (:1767-1771).
+    Called by the UNet (with an AttnCall) it takes the tokens from its `image_prompt` (ImagePrompt) and plain text
+    states; called without one, as the reference is, the last num_tokens rows of encoder_hidden_states are the image
+    tokens (:1767-1771).
     `scale` is the layer's weight of the image term (unet.set_ip_adapter_scale); 0 launches nothing."""
 
     def __init__(self, hidden_size, cross_attention_dim=None, num_tokens=4, scale=1.0):
@@ -161,16 +162,16 @@ class IPAdapterAttnProcessor2_0(nn.Module, AnimateDiffAttnProcessor2_0):
         self.to_v_ip = nn.Linear(cross_attention_dim or hidden_size, hidden_size, bias=False)
 
     def forward(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None, scale=1.0,
-                **kwargs):
+                _vst: Optional[AttnCall] = None, **kwargs):
         if encoder_hidden_states is None:
             raise _err("image_prompt: IPAdapterAttnProcessor2_0 is a cross-attention (attn2) processor")
-        if "_vst_image_prompt" not in kwargs:
-            encoder_hidden_states, kwargs["_vst_image_prompt"] = self._split(encoder_hidden_states,
-                                                                            hidden_states.shape[0])
-        elif kwargs["_vst_image_prompt"] is None:
+        if _vst is None:
+            encoder_hidden_states, prompt = self._split(encoder_hidden_states, hidden_states.shape[0])
+            _vst = AttnCall(image_prompt=prompt)
+        elif _vst.image_prompt is None:
             raise _err("image_prompt: IP-Adapter processors are installed and no image prompt was given")
         return AnimateDiffAttnProcessor2_0.__call__(self, attn, hidden_states, encoder_hidden_states, attention_mask,
-                                                    temb, scale, **kwargs)
+                                                    temb, scale, _vst, **kwargs)
 
     def _split(self, enc, batch):
         """(text states, ImagePrompt) of concatenated states [be, L + num_tokens, D], kept per tensor object: the
@@ -228,8 +229,7 @@ class IPAdapterAttnProcessor2_0(nn.Module, AnimateDiffAttnProcessor2_0):
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
             # (no backward pass of vst_ip_attention_add, and the fold is made outside autograd)
             raise NotImplementedError("image_prompt: the IP-Adapter path is inference only")
-        if gate is not None:
-            raise _err("image_prompt: not together with a lora_gate (the folded keys would differ per frame)")
+        refuse_lora_gate(image_prompt, gate)
         if image_prompt is None:
             raise _err("image_prompt: IP-Adapter processors are installed and no image prompt was given")
         heads = attn.heads
@@ -259,8 +259,15 @@ def ip_processors(model) -> list:
             if isinstance(m, Attention) and isinstance(m.processor, IPAdapterAttnProcessor2_0)]
 
 
+def refuse_lora_gate(image_prompt, lora_gate):
+    """The one rule between two options: an image prompt and a LoRA gate do not go together.  Stated here only
+    (ForwardOptions.resolve through check_forward, the denoiser's two setters, a direct processor call)."""
+    if image_prompt is not None and lora_gate is not None:
+        raise _err("image_prompt: not together with a lora_gate (the folded keys would differ per frame)")
+
+
 def check_forward(model, image_prompt, rows: int, lora_gate=None):
-    """Refuse, before any launch, an image prompt the model cannot honour (UNetMotionModel.forward_tokens)."""
+    """Refuse, before any launch, an image prompt the model cannot honour (ForwardOptions.resolve)."""
     layers = ip_processors(model)
     if image_prompt is None:
         if layers:
@@ -268,8 +275,7 @@ def check_forward(model, image_prompt, rows: int, lora_gate=None):
         return
     if not layers:
         raise _err("image_prompt: the model has no IP-Adapter processors (load_ip_adapter)")
-    if lora_gate is not None:
-        raise _err("image_prompt: not together with a lora_gate (the folded keys would differ per frame)")
+    refuse_lora_gate(image_prompt, lora_gate)
     check_image_prompt(image_prompt, rows)
     for n, m in layers:
         if m.processor.num_tokens != image_prompt.num_tokens:

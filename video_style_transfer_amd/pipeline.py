@@ -34,7 +34,7 @@ from . import kernels as K
 from .attention_processor import refresh_text_kv
 from .free_init import FreeInit, as_free_init, check_free_init_arg, check_free_init_run, dft_order, freq_filter
 from .freeu import FreeU, as_freeu, check_freeu_arg
-from .ip_adapter import ImagePrompt, check_forward, refresh_image_kv
+from .ip_adapter import ImagePrompt, check_forward, refresh_image_kv, refuse_lora_gate
 from .lora_gate import LoraGate
 from .token_merge import TokenMerging, as_token_merging, check_token_merging
 from .scheduler import (SAMPLERS, STOCHASTIC_SAMPLERS, EulerDiscreteScheduler, check_eta, sampler_coefficients,
@@ -211,14 +211,18 @@ class AnimateDiffDenoiser:
         self.time_ids = tid.unsqueeze(0).repeat(self.ncopy * n, 1).to(dev).contiguous()
         self.graph = None
 
+    def _options(self) -> dict:
+        """The per-call options as they stand now, by ForwardOptions' field names: the one place that maps this
+        object's attributes to them.  The forward resolves (and so checks) them, once per call."""
+        return dict(temporal_context=self.context, cross_frame=self.cross_frame, lora_gate=self.lora_gate,
+                    freeu=self.freeu, image_prompt=self.image_prompt, token_merging=self.token_merging)
+
     def _step(self):
         B = self.ncopy * self.nclips
         K.pack_latents(self.lat, self.x, sigmas=self.sigmas, step_idx=self.step_idx, ncopy=self.ncopy)
         emb = self.unet.embed(self.timesteps, self.pooled, self.time_ids, B, step_idx=self.step_idx)
         noise = self.unet.forward_tokens(self.x, B, self.F, self.h, self.w, emb, self.enc, shard=self.shard,
-                                         temporal_context=self.context, cross_frame=self.cross_frame,
-                                         lora_gate=self.lora_gate, freeu=self.freeu, image_prompt=self.image_prompt,
-                                         token_merging=self.token_merging)
+                                         **self._options())
         if self.table_step:
             if self.factor is not None:
                 K.cfg_rescale_factor(noise, self.lat.shape, guidance=self.guidance, phi=self.guidance_rescale,
@@ -318,9 +322,7 @@ class AnimateDiffDenoiser:
         The first call drops a captured step (the gated step runs other kernels); later calls rewrite the gate
         tables in place, re-project the text K/V of every attn2 into their buffers, and keep it, so a schedule can
         be driven from the host: run_steps(k), set_lora_gates(...), run_steps()."""
-        if self.image_prompt is not None:
-            raise K._lib.VstError("image_prompt: not together with a lora_gate (the folded keys would differ per "
-                                  "frame)")
+        refuse_lora_gate(self.image_prompt, True)  # (True: the gate this call would make)
         c = self._gate_rows(content, "content")
         s = self._gate_rows(style, "style")
         if self.lora_gate is None:
@@ -358,9 +360,7 @@ class AnimateDiffDenoiser:
         the image keys of every layer into their buffers and keep it.  Not together with set_lora_gates."""
         if (image_embeds is None) == (tokens is None):
             raise ValueError("set_image_prompt: give image_embeds or tokens (one of them)")
-        if self.lora_gate is not None:
-            raise K._lib.VstError("image_prompt: not together with a lora_gate (the folded keys would differ per "
-                                  "frame)")
+        refuse_lora_gate(True, self.lora_gate)  # (True: the prompt this call would make)
         cond = self._image_tokens(image_embeds, tokens, "set_image_prompt")
         if self.cfg:
             if negative_tokens is None and negative_image_embeds is None:

@@ -29,11 +29,11 @@ import torch
 from torch import nn
 
 from . import kernels as K
-from .attention_processor import AnimateDiffAttnProcessor2_0, Attention, input_lora_ops
+from .attention_processor import AnimateDiffAttnProcessor2_0, AttnCall, Attention, input_lora_ops
 from .config import UNetMotionConfig
 from .freeu import FreeU, as_freeu
 from .lora_linear import LoRACompatibleLinear, build_ops, lora_in_gemm, run_ops
-from .token_merge import TokenMerging, as_token_merging, check_token_merging
+from .token_merge import TokenMerging, as_token_merging, check_token_merging, spatial_levels
 from .weights import sinusoid_table
 
 BF16 = torch.bfloat16
@@ -208,23 +208,6 @@ def as_cross_frame(cf) -> Optional[CrossFrameAttention]:
     return cf if cf is None or isinstance(cf, CrossFrameAttention) else CrossFrameAttention(cf)
 
 
-def spatial_attention_tokens(model, h: int, w: int) -> list:
-    """Tokens per frame (H * W) at every level of `model` that has spatial transformer blocks, for an h x w latent."""
-    out = []
-    for blk in model.down_blocks:
-        if blk.attentions is not None:
-            out.append(h * w)
-        if blk.downsamplers is not None:
-            h, w = (h + 1) // 2, (w + 1) // 2
-    out.append(h * w)  # the mid block
-    for blk in model.up_blocks:
-        if blk.attentions is not None:
-            out.append(h * w)
-        if blk.upsamplers is not None:
-            h, w = 2 * h, 2 * w
-    return out
-
-
 def check_cross_frame(model, F: int, cf: Optional[CrossFrameAttention], shard=None, hw=None):
     """Refuse, before any launch, a cross_frame option the spatial self-attention cannot honour on a clip of F
     frames (all ranks' frames together).  `hw`: the latent's (h, w), where the caller knows it; the AdaIN's unbiased
@@ -238,7 +221,8 @@ def check_cross_frame(model, F: int, cf: Optional[CrossFrameAttention], shard=No
                               f"{cf.sources} name none (\"first\" or a frame index)")
     if not cf.active(F):
         return
-    if cf.adain is not None and hw is not None and min(spatial_attention_tokens(model, *hw)) < 2:
+    # (the fewest tokens are at the deepest level of the down path; the up path's levels are never smaller)
+    if cf.adain is not None and hw is not None and min(H * W for (H, W), _ in spatial_levels(model, *hw)) < 2:
         raise K._lib.VstError(f"cross_frame: adain={cf.adain!r} takes a variance over each frame's tokens, and a "
                               f"{hw[0]} x {hw[1]} latent leaves a level of this model fewer than 2 per frame")
     if shard is not None and shard.world > 1:
@@ -247,14 +231,65 @@ def check_cross_frame(model, F: int, cf: Optional[CrossFrameAttention], shard=No
     for s in cf.sources:
         if isinstance(s, int) and s >= F:
             raise K._lib.VstError(f"cross_frame: source frame {s} >= F = {F}")
-    bad = model.__dict__.get("_vst_cross_frame_bad")
+    bad = model.__dict__.get("_vst_xframe_bad_heads")
     if bad is None:  # head sizes are fixed at construction: scanned once per model
         bad = [n for n, m in model.named_modules()
                if isinstance(m, BasicTransformerBlock) and not m.temporal and m.attn1.dim_head != 64]
-        model.__dict__["_vst_cross_frame_bad"] = bad
+        model.__dict__["_vst_xframe_bad_heads"] = bad
     if bad:
         raise K._lib.VstError(f"cross_frame: the cross-frame attention kernel is specialised for head_dim 64; "
                               f"{bad[0]}.attn1 has another")
+
+
+@dataclass(frozen=True)
+class ForwardOptions:
+    """The per-call options of the UNet forward, normalised and checked.  `resolve` is the way to one
+    for a model call: holding an instance means the checks have run, so nothing below looks again.  (Built directly,
+    from the option objects themselves, only to run a block on its own.)  None: the option is off, the plain launches.
+    `temporal_context`: the motion modules attend inside sliding windows when the clip is longer than its length.
+    `cross_frame` (given as a CrossFrameAttention or its sources, e.g. ("first",)): attn1 of the spatial transformer
+    blocks also attends to the source frames of the same clip.  `lora_gate` (lora_gate.LoraGate with B * F rows, one
+    per (batch element, frame) in row order; under a shard this rank's frames): the content / style strength of the
+    UnZipLoRA delta of the spatial transformer blocks' projections, per row; the motion modules are not gated.
+    `freeu` (given as a freeu.FreeU or its (s1, s2, b1, b2)): FreeU in the first two up blocks (§17).  `image_prompt`
+    (ip_adapter.ImagePrompt with B * F rows): the image tokens of the IP-Adapter attn2 layers (load_ip_adapter, §20);
+    required when they are installed, refused when they are not.  `token_merging` (given as a TokenMerging, a dict of
+    its fields or a ratio; §22): the spatial blocks up to its max_downsample merge tokens around attn1 (and the
+    feed-forward)."""
+    temporal_context: Optional[TemporalContext] = None
+    cross_frame: Optional[CrossFrameAttention] = None
+    lora_gate: Optional[object] = None
+    freeu: Optional[FreeU] = None
+    image_prompt: Optional[object] = None
+    token_merging: Optional[TokenMerging] = None
+
+    @classmethod
+    def resolve(cls, model, B: int, F: int, hw, shard=None, x=None, *, use_model_defaults: bool, **given):
+        """The options `given` (by field name, in the forms forward() takes) for a call of `model` on B clips of F
+        frames (this rank's, under `shard`) of an hw = (h, w) latent; `x`: the call's input, for its device and
+        whether it asks for gradients.  `use_model_defaults`: freeu / token_merging not given are what enable_freeu /
+        enable_token_merging set (forward()); else None means off (forward_tokens()).
+        Every refusal is raised here, before any launch, each check once and in this order: the image prompt against
+        the model (and against a lora_gate), cross_frame, the freeu values, token_merging, the clip length against
+        the motion modules' positions, the lora_gate's rows."""
+        from .ip_adapter import check_forward  # (local import: ip_adapter imports the attention processors)
+        o = cls(**given)  # (an option that does not exist is a TypeError here)
+        F_clip = F * (shard.world if shard is not None else 1)
+        check_forward(model, o.image_prompt, B * F, o.lora_gate)
+        cross_frame = as_cross_frame(o.cross_frame)
+        check_cross_frame(model, F_clip, cross_frame, shard, hw)
+        freeu, token_merging = o.freeu, o.token_merging
+        if use_model_defaults:
+            freeu = model.freeu if freeu is None else freeu
+            token_merging = model.token_merging if token_merging is None else token_merging
+        freeu = as_freeu(freeu, x.device if x is not None else model.conv_in.weight.device)
+        token_merging = as_token_merging(token_merging)
+        check_token_merging(model, token_merging, hw, x)
+        if model.config.motion_modules:
+            check_clip_length(F_clip, model.config.motion_max_seq_length, o.temporal_context)
+        if o.lora_gate is not None and o.lora_gate.rows != B * F:
+            raise K._lib.VstError(f"lora_gate: {o.lora_gate.rows} rows, expected B * F = {B * F}")
+        return dataclasses.replace(o, cross_frame=cross_frame, freeu=freeu, token_merging=token_merging)
 
 
 @dataclass
@@ -264,14 +299,9 @@ class FwdCtx:
     emb_silu: torch.Tensor  # [B, T] bf16, SiLU(time + add embedding)
     enc: Optional[torch.Tensor]  # [B, L, D] bf16 text states
     cross_kwargs: dict
+    opts: ForwardOptions = ForwardOptions()
     shard: Optional[object] = None  # frame_shard.FrameShard when the clip's frames span ranks (F is per rank)
     temb: Optional[dict] = None     # ResnetBlock2D -> fp32 [B, Cout] view of the batched time_emb_proj output
-    temporal_context: Optional[TemporalContext] = None  # motion attention inside sliding windows when F > length
-    cross_frame: Optional[CrossFrameAttention] = None   # spatial attn1 also attends to source frames when F > 1
-    lora_gate: Optional[object] = None  # lora_gate.LoraGate ([B * F] rows): per-frame content / style strength
-    freeu: Optional[FreeU] = None       # backbone scale + skip filter before the skip concats of up stages 0 and 1
-    image_prompt: Optional[object] = None  # ip_adapter.ImagePrompt ([B * F] rows): image tokens of the attn2 layers
-    token_merging: Optional[TokenMerging] = None  # merge tokens around attn1 / the FF of the spatial blocks (§22)
     latent_hw: Optional[tuple] = None   # the latent's (h, w): a block's down-sampling level is measured against it
     spatial_hw: Optional[tuple] = None  # the (H, W) of the tokens of the Transformer2DModel being run (the cells' grid)
 
@@ -334,50 +364,42 @@ class BasicTransformerBlock(nn.Module):
             self.pos_embed = _SinusoidalPE(dim, max_seq_length)
 
     def run(self, x, nimg, N, ctx: FwdCtx):
-        """x: [nimg*N, C] -> same.  A spatial block merges tokens (ctx.token_merging) only where ctx.spatial_hw gives
-        the (H, W) of its N tokens: the cells are cut on that grid."""
+        """x: [nimg*N, C] -> same.  A spatial block merges tokens (ctx.opts.token_merging) only where ctx.spatial_hw
+        gives the (H, W) of its N tokens: the cells are cut on that grid."""
         C = x.shape[1]
+        opts = ctx.opts
         if self.temporal:
             pe = f32(self.pos_embed.pe).view(-1, C)
-            tc = ctx.temporal_context
-            check_clip_length(ctx.F, pe.shape[0], tc)
+            tc = opts.temporal_context
             if tc is not None and tc.active(ctx.F):
                 # LayerNorm WITHOUT the positional term: the windowed kernel adds pe[position in window] . Wqkv^T per
                 # window behind one projection per frame; the fused q/k/v GEMM steps aside
-                kw = dict(num_frames=ctx.F, _vst_context=(tc, pe))
-                n = self.norm1.run(x)
-                x = self.attn1(n.view(nimg, N, C), _vst_residual=x, **kw).view(-1, C)
-                n = self.norm2.run(x)
-                x = self.attn2(n.view(nimg, N, C), _vst_residual=x, **kw).view(-1, C)
-                n = self.norm3.run(x)
-                return self.ff.run(n, residual=x)
-            kw = dict(pe=pe, pe_div=N, pe_mod=ctx.F)
-            n = self.norm1.run(x, **kw)
-            x = self.attn1(n.view(nimg, N, C), num_frames=ctx.F, _vst_residual=x).view(-1, C)
-            n = self.norm2.run(x, **kw)
-            x = self.attn2(n.view(nimg, N, C), num_frames=ctx.F, _vst_residual=x).view(-1, C)
+                pe_kw, context = {}, (tc, pe)
+            else:
+                pe_kw, context = dict(pe=pe, pe_div=N, pe_mod=ctx.F), None
+            for norm, attn in ((self.norm1, self.attn1), (self.norm2, self.attn2)):
+                n = norm.run(x, **pe_kw)
+                x = attn(n.view(nimg, N, C), _vst=AttnCall(residual=x, frames=ctx.F, context=context)).view(-1, C)
         else:
             scale = ctx.cross_kwargs.get("scale", 1.0)
-            cf = ctx.cross_frame
-            kw = dict(_vst_cross_frame=(cf, ctx.F)) if cf is not None and cf.active(ctx.F) else {}
-            gkw = dict(_vst_lora_gate=ctx.lora_gate) if ctx.lora_gate is not None else {}
+            gate = opts.lora_gate
+            cf = opts.cross_frame if opts.cross_frame is not None and opts.cross_frame.active(ctx.F) else None
+            frames = ctx.F if cf is not None else None
             tm, plan = self._token_merging(x, nimg, N, ctx)
             if plan is not None and tm.merge_attn:
                 # attn1 on the merged rows (no fused residual, the LoRA down-projection inside the GEMM); every token
                 # then takes the row it went to, on top of the block's residual
                 m = tm.merge(plan, self.norm1.run(x))
-                o = self.attn1(m.view(nimg, N - plan.r, C), _vst_residual=None, _vst_lora_u=None, **kw, **gkw,
-                               **ctx.cross_kwargs).view(-1, C)
+                call = AttnCall(frames=frames, cross_frame=cf, lora_gate=gate)
+                o = self.attn1(m.view(nimg, N - plan.r, C), _vst=call, **ctx.cross_kwargs).view(-1, C)
                 x = tm.unmerge_add(plan, o, x)
             else:
                 n, u = self.norm1.run_lora(x, input_lora_ops(self.attn1, True, scale))
-                x = self.attn1(n.view(nimg, N, C), _vst_residual=x, _vst_lora_u=u, **kw, **gkw,
-                               **ctx.cross_kwargs).view(-1, C)
+                call = AttnCall(residual=x, lora_u=u, frames=frames, cross_frame=cf, lora_gate=gate)
+                x = self.attn1(n.view(nimg, N, C), _vst=call, **ctx.cross_kwargs).view(-1, C)
             n, u = self.norm2.run_lora(x, input_lora_ops(self.attn2, False, scale))
-            if ctx.image_prompt is not None:
-                gkw = dict(gkw, _vst_image_prompt=ctx.image_prompt)
-            x = self.attn2(n.view(nimg, N, C), encoder_hidden_states=ctx.enc, _vst_residual=x, _vst_lora_u=u, **gkw,
-                           **ctx.cross_kwargs).view(-1, C)
+            call = AttnCall(residual=x, lora_u=u, lora_gate=gate, image_prompt=opts.image_prompt)
+            x = self.attn2(n.view(nimg, N, C), encoder_hidden_states=ctx.enc, _vst=call, **ctx.cross_kwargs).view(-1, C)
             if plan is not None and tm.merge_mlp:
                 m = tm.merge(plan, self.norm3.run(x))
                 return tm.unmerge_add(plan, self.ff.run(m, residual=None), x)
@@ -387,7 +409,7 @@ class BasicTransformerBlock(nn.Module):
     def _token_merging(self, x, nimg, N, ctx: FwdCtx):
         """(the option, this block's plan computed from its input x), or (None, None) where the block runs as without
         the option: off, ratio 0, no tokens to merge, or a level above max_downsample."""
-        tm, hw = ctx.token_merging, ctx.spatial_hw
+        tm, hw = ctx.opts.token_merging, ctx.spatial_hw
         if tm is None or hw is None or hw[0] * hw[1] != N or not tm.enabled:
             return None, None
         H, W = hw
@@ -422,7 +444,7 @@ class Transformer2DModel(nn.Module):
     def run(self, x, nimg, H, W, ctx):
         h = self.norm.run(x, nimg, H * W)
         h = self.proj_in.run(h)
-        if ctx.token_merging is not None:
+        if ctx.opts.token_merging is not None:
             ctx = dataclasses.replace(ctx, spatial_hw=(H, W))
         for blk in self.transformer_blocks:
             h = blk.run(h, nimg, H * W, ctx)
@@ -611,9 +633,9 @@ class UpBlock(nn.Module):
         self.upsamplers = nn.ModuleList([Upsample2D(cout)]) if add_up else None
 
     def run(self, x, nimg, H, W, ctx, skips, stage=None):
-        """`stage`: this block's index in the up path; with ctx.freeu, stages 0 and 1 run apply_freeu before each
+        """`stage`: this block's index in the up path; with ctx.opts.freeu, stages 0 and 1 run apply_freeu before each
         resnet (x scaled in place: it is this path's own tensor; the skip filtered into a new one)."""
-        freeu = ctx.freeu if stage in (0, 1) else None
+        freeu = ctx.opts.freeu if stage in (0, 1) else None
         for j, res in enumerate(self.resnets):
             s, sh, sw = skips.pop()
             assert (sh, sw) == (H, W)
@@ -785,39 +807,30 @@ class UNetMotionModel(nn.Module):
     # ---- core (NHWC tokens) -----------------------------------------------------------------
     def forward_tokens(self, x, B, F, h, w, emb_silu, enc, cross_kwargs=None, shard=None, fusion_world=None,
                        temporal_context=None, cross_frame=None, lora_gate=None, freeu=None, image_prompt=None,
-                       token_merging=None):
+                       token_merging=None, options: Optional[ForwardOptions] = None):
         """x: [B*F*h*w, in_channels] bf16 -> noise prediction [B*F*h*w, out_channels] bf16.
         With `shard` (frame_shard.FrameShard), F is this rank's frames of each clip.  `fusion_world` P (default: the
         shard's world size, else 1): take the shape-dependent fusion decisions a P-way frame-sharded rank takes
-        (kernels.fusion_world), so an unsharded forward equals a P-way sharded one bit for bit.  `cross_frame`
-        (CrossFrameAttention or its sources): attn1 of the spatial transformer blocks also attends to the source
-        frames of the same clip.  `lora_gate` (lora_gate.LoraGate with B * F rows, one per (batch element, frame) in
-        row order; under a shard this rank's frames): the content / style strength of the UnZipLoRA delta of the
-        spatial transformer blocks' projections, per row.  The motion modules are not gated.  `freeu` (freeu.FreeU, or
-        its (s1, s2, b1, b2)): FreeU in the first two up blocks; None runs today's launches.  Here
-        None means off: the enable_freeu default is applied by forward().  `image_prompt` (ip_adapter.ImagePrompt with
-        B * F rows): the image tokens of the IP-Adapter attn2 layers (load_ip_adapter); required when
-        they are installed, refused when they are not.  `token_merging` (token_merge.TokenMerging, a dict of its
-        fields or a ratio): the spatial blocks up to its max_downsample merge tokens around attn1 (and the
-        feed-forward); None, as for freeu, means off here."""
-        from .ip_adapter import check_forward  # (local import: ip_adapter imports the attention processors)
-        check_forward(self, image_prompt, B * F, lora_gate)
-        token_merging = as_token_merging(token_merging)
-        check_token_merging(self, token_merging, (h, w), x)
-        freeu = as_freeu(freeu, x.device)
-        cross_frame = as_cross_frame(cross_frame)
-        check_cross_frame(self, F * (shard.world if shard is not None else 1), cross_frame, shard, (h, w))
-        if lora_gate is not None and lora_gate.rows != B * F:
-            raise K._lib.VstError(f"lora_gate: {lora_gate.rows} rows, expected B * F = {B * F}")
-        if self.config.motion_modules:
-            check_clip_length(F * (shard.world if shard is not None else 1), self.config.motion_max_seq_length,
-                              temporal_context)
+        (kernels.fusion_world), so an unsharded forward equals a P-way sharded one bit for bit.  The six option
+        keywords are ForwardOptions' fields, resolved (checked) here; None means off: the enable_freeu /
+        enable_token_merging defaults are applied by forward().  Or `options`: a ForwardOptions already resolved for
+        this call, in their place; it is taken as it is, nothing is checked again."""
+        given = dict(temporal_context=temporal_context, cross_frame=cross_frame, lora_gate=lora_gate, freeu=freeu,
+                     image_prompt=image_prompt, token_merging=token_merging)
+        if options is None:
+            options = ForwardOptions.resolve(self, B, F, (h, w), shard, x, use_model_defaults=False, **given)
+        elif any(v is not None for v in given.values()):
+            raise TypeError("forward_tokens: `options` holds every option of the call; no option keyword beside it")
+        return self._run_tokens(x, B, F, h, w, emb_silu, enc, cross_kwargs, shard, fusion_world, options)
+
+    def _run_tokens(self, x, B, F, h, w, emb_silu, enc, cross_kwargs, shard, fusion_world, opts: ForwardOptions):
+        """forward_tokens under resolved options: launches only."""
         if fusion_world is None:
             fusion_world = shard.world if shard is not None else 1
         # no split-K: a row's bits do not depend on the launch's row count (frame shards)
         with K.row_invariant(), K.fusion_world(fusion_world):
-            ctx = FwdCtx(B, F, emb_silu, enc, cross_kwargs or {}, shard, self.batched_temb(emb_silu),
-                         temporal_context, cross_frame, lora_gate, freeu, image_prompt, token_merging, (h, w))
+            ctx = FwdCtx(B=B, F=F, emb_silu=emb_silu, enc=enc, cross_kwargs=cross_kwargs or {}, opts=opts, shard=shard,
+                         temb=self.batched_temb(emb_silu), latent_hw=(h, w))
             nimg = B * F
             H, W = h, w
             x = self.conv_in.run(x, nimg, H, W)
@@ -837,26 +850,15 @@ class UNetMotionModel(nn.Module):
                 image_prompt=None, token_merging=None, **kwargs):
         """diffusers UNetMotionModel.forward signature (inference_animatediff.py:110-121).  With
         `frame_shard` (frame_shard.FrameShard) `sample` holds this rank's frames of each clip; `fusion_world`: see
-        forward_tokens; `temporal_context` (TemporalContext): the motion modules attend inside sliding windows when the
-        clip is longer than its length; `cross_frame` (CrossFrameAttention or its sources, e.g. ("first",)): attn1 of the
-        spatial transformer blocks also attends to the source frames of the same clip; `lora_gate`: see
-        forward_tokens; `freeu` (FreeU or (s1, s2, b1, b2)): FreeU for this call, default what enable_freeu set;
-        `image_prompt` (ip_adapter.ImagePrompt): see forward_tokens; `token_merging` (TokenMerging, a dict of its fields
-        or a ratio): token merging for this call, default what enable_token_merging set."""
+        forward_tokens; `temporal_context`, `cross_frame`, `lora_gate`, `freeu`, `image_prompt`, `token_merging`: the
+        options of this call (ForwardOptions), every one refused before any launch if it cannot be honoured; `freeu`
+        and `token_merging` default to what enable_freeu / enable_token_merging set."""
         if not sample.is_cuda:
             raise K._lib.VstError("UNetMotionModel: sample is on CPU; the HIP path has no CPU fallback")
         B, Cin, F, h, w = sample.shape
-        from .ip_adapter import check_forward
-        check_forward(self, image_prompt, B * F, lora_gate)
-        cross_frame = as_cross_frame(cross_frame)
-        check_cross_frame(self, F * (frame_shard.world if frame_shard is not None else 1), cross_frame,
-                          frame_shard, (h, w))
-        freeu = as_freeu(self.freeu if freeu is None else freeu, sample.device)  # bad values: before any launch
-        token_merging = as_token_merging(self.token_merging if token_merging is None else token_merging)
-        check_token_merging(self, token_merging, (h, w), sample)
-        if self.config.motion_modules:
-            check_clip_length(F * (frame_shard.world if frame_shard is not None else 1),
-                              self.config.motion_max_seq_length, temporal_context)
+        opts = ForwardOptions.resolve(self, B, F, (h, w), frame_shard, sample, use_model_defaults=True,
+                                      temporal_context=temporal_context, cross_frame=cross_frame, lora_gate=lora_gate,
+                                      freeu=freeu, image_prompt=image_prompt, token_merging=token_merging)
         dev = sample.device
         t = timestep if torch.is_tensor(timestep) else torch.tensor([timestep])
         t = t.to(device=dev, dtype=torch.float32).reshape(-1)
@@ -869,9 +871,6 @@ class UNetMotionModel(nn.Module):
         enc = encoder_hidden_states.to(dev, BF16).contiguous()
         x = torch.empty(B * F * h * w, Cin, dtype=BF16, device=dev)
         K.pack_latents(sample.float().contiguous(), x)
-        y = self.forward_tokens(x, B, F, h, w, emb_silu, enc, cross_attention_kwargs, shard=frame_shard,
-                                fusion_world=fusion_world, temporal_context=temporal_context,
-                                cross_frame=cross_frame, lora_gate=lora_gate,
-                                freeu=freeu, image_prompt=image_prompt, token_merging=token_merging)
+        y = self._run_tokens(x, B, F, h, w, emb_silu, enc, cross_attention_kwargs, frame_shard, fusion_world, opts)
         out = y.view(B, F, h, w, -1).permute(0, 4, 1, 2, 3).contiguous().to(sample.dtype)
         return UNetMotionOutput(out) if return_dict else (out,)
