@@ -251,6 +251,28 @@ int vst_ip_attention_add(const void* x, int ldx, int K, const void* G, int ldg, 
                          int ldv, int nbatch, int M, int Nq, int heads, int T, int kv_div, float scale,
                          float layer_scale, const float* row_scale, void* O, int ldo, void* stream);
 
+/* Regional prompts: attn2 over R <= 4 text prompts, blended per query row (no line of the reference does this; the
+ * definition is this project's).  Head size 64.  Per query row m (image b = m / Nq), head h:
+ *   o_r = softmax(q[m] K_r^T scale) V_r, one softmax per region r over that region's Nk keys, with
+ *         vst_spatial_attention's arithmetic and rounding points;
+ *   O[m][64h ..] = bf16(sum over r ascending with wts[m][r] != 0 of wts[m][r] * (o_r_unnormalised * (1 / l_r))),
+ * the sum in fp32, each product and each add rounded, the result rounded once to bf16.  A row with wts[m][r] == 0
+ * takes nothing from region r, whatever its K/V hold (a select, not a multiply); a region whose weight is 0 on every
+ * row of a workgroup's 128-query block is not loaded there.  A row whose weights are one-hot carries exactly the bits
+ * vst_spatial_attention gives it for that region's K/V; a row whose weights are all 0 is written as 0.
+ * q, O: bf16 [nimg*Nq, 64*heads] views; Kt, Vt: bf16 rows ((b / kv_div)*R + r)*Nk + key, head h at columns 64h,
+ * one row stride ldkv; wts: fp32 [nimg*Nq][4], the caller's already normalised weights, columns >= R ignored.  Any
+ * Nk >= 1, walked in 64-key tiles.  No workspace, no atomics, no lse; a row's bits do not depend on nimg.  Returns 1
+ * before any launch for a NULL pointer, a non-positive size, R > 4, nimg % kv_div, a stride below 64*heads or no
+ * multiple of 8, a base that is not 16-byte aligned, or byte extents past 2^31 - 1. */
+int vst_region_attention(const void* q, int ldq, const void* Kt, const void* Vt, int ldkv, const float* wts, void* O,
+                         int ldo, int nimg, int heads, int Nq, int Nk, int R, int kv_div, float scale, void* stream);
+/* The kernel's LDS plan for up to 128 keys per region, for every later vst_region_attention of this process: 0 the
+ * (region, tile) walk double-buffered through registers, 1 every live region's K/V up front by LDS-DMA, -1 (default:
+ * VST_REGION_PLAN, else -1) plan 1 where it needs at most 64 KiB of LDS (R <= 2 at 65 to 128 keys, R <= 4 below), else
+ * plan 0, as measured.  Returns the previous setting.  Same bits either way (tests / A/B). */
+int vst_region_plan(int plan);
+
 /* Frame-axis attention (motion module / TemporalTransformerBlock, animatediff/temporal_transformer.py:66-68):
  * token (clip b, frame f, pixel p) at row (b*F + f)*HW + p; F <= 32; head_dim in {8,16,32,40,64,80,160}. */
 int vst_temporal_attention(const void* q, const void* k, const void* v, int ldqkv, void* o, int ldo, int nclip,

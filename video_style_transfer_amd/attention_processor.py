@@ -31,6 +31,7 @@ from torch import nn
 
 from . import kernels as K
 from .lora_linear import LoRACompatibleLinear, build_ops, gate_operands, run_ops
+from .region_prompts import refuse_lora_gate as refuse_region_gate
 
 
 @dataclass
@@ -44,6 +45,7 @@ class AttnCall:
     cross_frame: Optional[object] = None     # attn1 only: an active unet_motion.CrossFrameAttention (needs `frames`)
     lora_gate: Optional[object] = None       # lora_gate.LoraGate, one row per image of the batch
     image_prompt: Optional[object] = None    # attn2 only: ip_adapter.ImagePrompt
+    regions: Optional[tuple] = None          # attn2 only: (region_prompts.RegionPrompts, this level's fp32 weight table)
     context: Optional[tuple] = None          # motion modules: (TemporalContext, fp32 PE table); the input carries no PE
 
 
@@ -108,7 +110,9 @@ def _finish(attn, out, residual_for_flag):
 
 
 class AnimateDiffAttnProcessor2_0:
-    """animatediff/attention_processor.py:6-96, kernel-backed."""
+    """animatediff/attention_processor.py:6-96, kernel-backed.  With `_vst.regions` (regional prompts, DESIGN.md
+    §24) attn2 attends to the regions' own text states and does not read encoder_hidden_states (it must still be
+    given: it is what makes the call a cross-attention)."""
 
     def __init__(self):
         if not hasattr(F, "scaled_dot_product_attention"):
@@ -156,12 +160,25 @@ class AnimateDiffAttnProcessor2_0:
             if batch % be:
                 raise ValueError(f"encoder batch {be} does not divide hidden batch {batch}")
             q_ops = build_ops([attn.to_q], s)
-            # (with a gate the text K/V carry each frame's own gates: one block per image, kv_div 1)
-            kv = _text_kv(attn, enc, s, gate)
-            kv_div = batch // (kv.shape[0] // L)
+            regions = call.regions
+            if regions is not None:
+                # regional prompts: the text K/V are those of the regions' own states, projected once
+                # per clip through the same cache; encoder_hidden_states is not read
+                refuse_region_gate(regions[0], gate)
+                kv, L, kv_div = _text_kv(attn, regions[0].states_rows, s), regions[0].L, regions[0].frames
+            else:
+                # (with a gate the text K/V carry each frame's own gates: one block per image, kv_div 1)
+                kv = _text_kv(attn, enc, s, gate)
+                kv_div = batch // (kv.shape[0] // L)
             if hd != 64:
                 raise NotImplementedError("spatial cross-attention kernel is specialised for head_dim 64 (SDXL)")
-            if lora_u is None and _cross_fusable(q_ops, batch * N, N, L):
+            if regions is not None:
+                # q is its own launch (the fused q + cross-attention steps aside), then one attention per live region,
+                # blended per row with this level's weights
+                q = run_ops(x, q_ops, u=lora_u)
+                o = K.region_attention(q, kv[:, :inner], kv[:, inner:], regions[1], nimg=batch, heads=heads, Nq=N,
+                                       Nk=L, R=regions[0].R, kv_div=kv_div, scale=hd ** -0.5)
+            elif lora_u is None and _cross_fusable(q_ops, batch * N, N, L):
                 # q projection (+ in-GEMM UnZipLoRA) and the text cross-attention as one launch: q stays on chip
                 g, gdiv = gate_operands(q_ops, gate, batch * N)
                 o = K.linear_cross_attention(x, q_ops.w, q_ops.a, q_ops.gn, q_ops.gr, q_ops.bias, kv[:, :inner],

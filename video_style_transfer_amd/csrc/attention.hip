@@ -25,14 +25,6 @@
 
 namespace vst {
 
-typedef __attribute__((address_space(3))) void sa_lds_void;
-
-// One 1-KiB LDS-DMA piece: 64 lanes x 16 B, lane-linear in LDS at `lds_piece` (wave-uniform).
-__device__ __forceinline__ void sa_dma16(__amdgpu_buffer_rsrc_t r, char* lds_piece, int off) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(
-      r, (sa_lds_void*)((__attribute__((address_space(3))) char*)(uintptr_t)lds_piece), 16, off, 0, 0, 0);
-}
-
 // PRE = 0: K/V tiles of 64 keys double-buffered through registers (long key ranges: the 32x32 / 64x64 levels).
 // PRE = n (1 or 2, Nk <= 64 n): the whole K/V of the (batch, head) is brought into LDS up front by LDS-DMA -- every
 // load of the workgroup in flight at once, no per-tile barrier -- for the 77 text tokens of cross-attention, where

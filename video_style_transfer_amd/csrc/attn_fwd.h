@@ -103,6 +103,14 @@ struct SaStage {
   }
 };
 
+typedef __attribute__((address_space(3))) void sa_lds_void;
+
+// One 1-KiB LDS-DMA piece: 64 lanes x 16 B, lane-linear in LDS at `lds_piece` (wave-uniform).
+__device__ __forceinline__ void sa_dma16(__amdgpu_buffer_rsrc_t r, char* lds_piece, int off) {
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(
+      r, (sa_lds_void*)((__attribute__((address_space(3))) char*)(uintptr_t)lds_piece), 16, off, 0, 0, 0);
+}
+
 // V^T fragment reads: lane 4q'+p' of group g reads row 4g + q' (+16, +32, +48), cols 16db + 4p'
 __device__ __forceinline__ void sa_voffs(int (&voff)[4], int lane) {
   const int li = lane & 15, g = lane >> 4;
@@ -237,6 +245,33 @@ __device__ __forceinline__ void sa_finish(const SaState& st, bf16_t* O, int ldo,
     if (q >= Nq) continue;
     if (lse && g == 0) lse[lse0 + q] = st.mrun[qb] * scale_log2 + __log2f(l);
     sa_store_row(st.o, qb, inv, O + (size_t)(row0 + q) * ldo + h * 64, lane);
+  }
+}
+
+// Regional finalize (region_attn_kernel, region_attention.hip): acc^T[d][q] += w[q] * (O^T[d][q] * 1/l) for the lane's
+// query columns with w != 0 -- a select, so a column with w == 0 takes nothing from this state, whatever it holds.
+// O^T * 1/l is sa_finish's product; the multiply by w and the add are rounded separately.  acc starts from -0.0f
+// (sa_blend_init): x + -0 = x for every x, signed zeros included, so a column's first term lands with its own bits.
+__device__ __forceinline__ void sa_blend_init(f32x4 (&acc)[4][2]) {
+#pragma unroll
+  for (int d = 0; d < 4; ++d)
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb) acc[d][cb] = f32x4{-0.f, -0.f, -0.f, -0.f};
+}
+__device__ __forceinline__ void sa_blend(const SaState& st, f32x4 (&acc)[4][2], const float (&w)[2]) {
+#pragma unroll
+  for (int qb = 0; qb < 2; ++qb) {
+    float l = st.lrun[qb];
+    l += __shfl_xor(l, 16);
+    l += __shfl_xor(l, 32);
+    const float inv = 1.0f / l;
+    if (w[qb] != 0.0f) {
+#pragma unroll
+      for (int db = 0; db < 4; ++db)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          acc[db][qb][i] = __fadd_rn(acc[db][qb][i], __fmul_rn(w[qb], __fmul_rn(st.o[db][qb][i], inv)));
+    }
   }
 }
 

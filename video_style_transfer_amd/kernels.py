@@ -792,6 +792,43 @@ def ip_attention_add(x, G, gbias, V, out, *, Nq, heads, T, kv_div=1, scale=0.125
     return out
 
 
+REGION_MAX = 4  # regions of vst_region_attention, the columns of its weight table
+
+
+def region_attention(q, k, v, wts, *, nimg, heads, Nq, Nk, R, kv_div=1, scale=None, out=None):
+    """Regional prompts: attn2 over R <= 4 prompts blended per query row (vst_region_attention).
+    q [nimg*Nq, >= 64*heads] bf16 view; k / v [(nimg // kv_div)*R*Nk, >= 64*heads] bf16 views sharing a row stride,
+    region r of token batch b at rows (b*R + r)*Nk; wts fp32 [nimg*Nq, 4], the normalised weights (columns >= R are
+    not read).  out[m] = bf16(sum over r with wts[m, r] != 0 of wts[m, r] * softmax(q[m] K_r^T scale) V_r): a zero
+    weight is a select, and a region that is zero on a whole 128-query block is not loaded there."""
+    fn = "region_attention"
+    nimg, heads, Nq, Nk, R, kv_div = int(nimg), int(heads), int(Nq), int(Nk), int(R), int(kv_div)
+    if min(nimg, heads, Nq, Nk, kv_div) < 1:
+        _fail(fn, "nimg, heads, Nq, Nk, kv_div", f"= {nimg}, {heads}, {Nq}, {Nk}, {kv_div}: expected positive counts")
+    if not 1 <= R <= REGION_MAX:
+        _fail(fn, "R", f"= {R}: the kernel blends 1 to {REGION_MAX} regions")
+    if nimg % kv_div:
+        _fail(fn, "nimg", f"= {nimg}: not a multiple of kv_div = {kv_div}")
+    inner = 64 * heads
+    _qkv(fn, q, k, v, nimg * Nq, (nimg // kv_div) * R * Nk)
+    out = _new(out, (nimg * Nq, inner), q, "out", fn)
+    for name, t in (("q", q), ("k", k), ("v", v), ("out", out)):
+        if t.shape[1] < inner or _ld(t) % 8 or t.data_ptr() % 16:
+            _fail(fn, name, f"needs >= {inner} columns, a row stride that is a multiple of 8 and a 16-byte aligned "
+                            f"base, got shape {tuple(t.shape)} stride {t.stride()}")
+    _block(wts, F32, "wts", fn, shape=(nimg * Nq, REGION_MAX))
+    if wts.data_ptr() % 16:
+        _fail(fn, "wts", "needs a 16-byte aligned base")
+    scale = 0.125 if scale is None else scale
+    # every region's scores and P.V for every row (an upper bound: dead regions are skipped); q, out, weights, K/V
+    with _Rec("region_attention", 4.0 * nimg * heads * Nq * R * Nk * 64,
+              2.0 * inner * (2 * nimg * Nq + 2 * (nimg // kv_div) * R * Nk) + 16.0 * nimg * Nq,
+              lambda: "region_attn_kernel", (nimg * heads, Nq, R * Nk)):
+        _lib.call("vst_region_attention", _p(q), _ld(q), _p(k), _p(v), k.stride(0), _p(wts), _p(out), _ld(out), nimg,
+                  heads, Nq, Nk, R, kv_div, float(scale), _stream())
+    return out
+
+
 def temporal_attention(q, k, v, nclip, F, HW, heads, head_dim, out=None, scale=None):
     """Frame-axis attention; rows (b*F + f)*HW + p.  q/k/v views share one row stride."""
     fn = "temporal_attention"

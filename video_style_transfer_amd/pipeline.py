@@ -21,6 +21,8 @@ result with the run's initial noise, keeps its low spatio-temporal frequencies a
 counter-based noise.  The mix runs between passes, outside the step, so the captured step replays untouched.
 With token_merging= the spatial transformer blocks merge tokens around attn1 (and the feed-forward); the
 plans live in static buffers and the destination draw reads the device seed and step counter, so the step still replays.
+With set_region_prompts (DESIGN.md §24) every spatial attn2 blends up to four prompts per pixel (vst_region_attention);
+the states and the per-level weight tables are static buffers, so new masks replay the captured step.
 """
 from __future__ import annotations
 
@@ -36,6 +38,8 @@ from .free_init import FreeInit, as_free_init, check_free_init_arg, check_free_i
 from .freeu import FreeU, as_freeu, check_freeu_arg
 from .ip_adapter import ImagePrompt, check_forward, refresh_image_kv, refuse_lora_gate
 from .lora_gate import LoraGate
+from .region_prompts import MAX_MASKS, RegionPrompts, attention_levels, region_weights
+from .region_prompts import refuse_lora_gate as refuse_region_gate
 from .token_merge import TokenMerging, as_token_merging, check_token_merging
 from .scheduler import (SAMPLERS, STOCHASTIC_SAMPLERS, EulerDiscreteScheduler, check_eta, sampler_coefficients,
                         start_index)
@@ -163,6 +167,10 @@ class AnimateDiffDenoiser:
         self.lora_gate = None
         # IP-Adapter image prompt (set_image_prompt): None = the plain step
         self.image_prompt = None
+        # regional prompts (set_region_prompts): None = the plain step; the regions' embeds as given, for a later
+        # set_prompt_embeds
+        self.region_prompts = None
+        self._region_embeds = None
         # table-driven sampler step: the previous step's denoised estimate, the (a, b, c) rows, the
         # per-clip rescale factor and its workspace; allocated here once, a captured step holds their pointers.  A
         # stochastic sampler (§16) has (a, b, c, d) rows and the seed of its noise, rewritten in place.
@@ -204,7 +212,10 @@ class AnimateDiffDenoiser:
             pooled = torch.cat([uncond_pooled, cond_pooled], 0)
         else:
             enc, pooled = cond_embeds, cond_pooled
-        self.enc = enc.to(dev, BF16).contiguous()
+        enc = enc.to(dev, BF16).contiguous()
+        if self.region_prompts is not None:  # region 0 is this prompt: refused before anything is replaced
+            self.region_prompts.set_states(self._region_states(enc, self._region_embeds))
+        self.enc = enc
         self.pooled = pooled.to(dev, BF16).contiguous()
         # SDXL time ids (inference_animatediff.py:81-85)
         tid = torch.tensor([self.height, self.width, 0, 0, self.height, self.width], dtype=torch.float32)
@@ -215,7 +226,8 @@ class AnimateDiffDenoiser:
         """The per-call options as they stand now, by ForwardOptions' field names: the one place that maps this
         object's attributes to them.  The forward resolves (and so checks) them, once per call."""
         return dict(temporal_context=self.context, cross_frame=self.cross_frame, lora_gate=self.lora_gate,
-                    freeu=self.freeu, image_prompt=self.image_prompt, token_merging=self.token_merging)
+                    freeu=self.freeu, image_prompt=self.image_prompt, token_merging=self.token_merging,
+                    region_prompts=self.region_prompts)
 
     def _step(self):
         B = self.ncopy * self.nclips
@@ -323,6 +335,7 @@ class AnimateDiffDenoiser:
         tables in place, re-project the text K/V of every attn2 into their buffers, and keep it, so a schedule can
         be driven from the host: run_steps(k), set_lora_gates(...), run_steps()."""
         refuse_lora_gate(self.image_prompt, True)  # (True: the gate this call would make)
+        refuse_region_gate(self.region_prompts, True)
         c = self._gate_rows(content, "content")
         s = self._gate_rows(style, "style")
         if self.lora_gate is None:
@@ -390,6 +403,70 @@ class AnimateDiffDenoiser:
         still installed, refuse a forward without a prompt: take them off with ip_adapter.unload_ip_adapter."""
         if self.image_prompt is not None:
             self.image_prompt = None
+            self.graph = None
+
+    def _region_states(self, enc, embeds):
+        """[ncopy * num_clips, 1 + n, L, D] in UNet batch order from the prompt states `enc` and the regions' embeds
+        [n, L, D]: a cond clip has its prompt in slot 0 and the regions' after it, an uncond clip its own (uncond)
+        states in every slot."""
+        n = self.nclips
+        if tuple(embeds.shape[1:]) != tuple(enc.shape[1:]):
+            raise ValueError(f"region prompts: embeds of {tuple(embeds.shape[1:])} per region, prompt states of "
+                             f"{tuple(enc.shape[1:])}")
+        R = 1 + embeds.shape[0]
+        cond = torch.cat([enc[-n:].unsqueeze(1), embeds.to(enc).unsqueeze(0).expand(n, *embeds.shape)], 1)
+        if not self.cfg:
+            return cond
+        return torch.cat([enc[:n].unsqueeze(1).expand(n, R, *enc.shape[1:]), cond], 0)
+
+    def set_region_prompts(self, embeds, masks, *, base_mask=None):
+        """Regional prompts: `embeds` (n, L, D), the text states of n <= 3 further prompts, and
+        `masks` (n, F_total | F_local | 1, h, w), bool or float in [0, 1], where each applies, at latent resolution.
+        Region 0 is the prompt of set_prompt_embeds (call it first) with weight max(1 - sum of the masks, 0), or
+        `base_mask` (frames, h, w) when given; per pixel the weights are normalised, so overlapping masks share.  Maps
+        that are constant in space and vary over the frames are a prompt schedule.  Every clip of the batch takes
+        the same regions.  The pooled embeds and the time ids stay the global prompt's.  The uncond branch of CFG
+        attends to the uncond states alone (weights (1, 0, 0, 0): the other slots are skipped).
+        The first call, another n, or other embeds drop a captured step; new masks with the same embeds rewrite
+        the weight tables in place and keep it.  Not together with set_lora_gates.  While regions are on, the spatial
+        attn2 layers do not read the plain prompt states."""
+        refuse_region_gate(True, self.lora_gate)  # (True: the prompts this call would make)
+        if self.enc is None:
+            raise ValueError("set_region_prompts: region 0 is the prompt of set_prompt_embeds; call that first")
+        e = torch.as_tensor(embeds)
+        if e.dim() != 3 or not 1 <= e.shape[0] <= MAX_MASKS:
+            raise ValueError(f"set_region_prompts: embeds {tuple(e.shape)}, expected (1 to {MAX_MASKS}, L, D)")
+        m = torch.as_tensor(masks)
+        if m.dim() != 4 or m.shape[0] != e.shape[0]:
+            raise ValueError(f"set_region_prompts: masks {tuple(m.shape)} for {e.shape[0]} embeds, expected "
+                             f"({e.shape[0]}, frames, {self.h}, {self.w})")
+        frames = max([self.F if t.shape[-3] == 1 else t.shape[-3]
+                      for t in (m,) + (() if base_mask is None else (torch.as_tensor(base_mask),))])
+        raw = self._local(region_weights(m, frames, (self.h, self.w), base_mask), 0, "region masks")
+        states = self._region_states(self.enc, e.to(self.device, BF16))
+        R, n = states.shape[1], self.nclips
+        rows = raw.unsqueeze(0).expand(n, *raw.shape)
+        if self.cfg:
+            base_only = torch.zeros_like(rows)
+            base_only[:, :, 0] = 1.0
+            rows = torch.cat([base_only, rows], 0)
+        rows = rows.reshape(-1, R, self.h, self.w)
+        rp = self.region_prompts
+        if rp is None or rp.R != R:
+            self.region_prompts = RegionPrompts(states, rows, self.F, attention_levels(self.unet, (self.h, self.w)),
+                                                self.device)
+            self.graph = None
+        else:
+            rp.set_weights(rows)
+            if not torch.equal(rp.states, states):
+                rp.set_states(states)
+                self.graph = None
+        self._region_embeds = e.detach().to(self.device, BF16).clone()
+
+    def clear_region_prompts(self):
+        """Back to the plain step (drops a captured step with the regional attention)."""
+        if self.region_prompts is not None:
+            self.region_prompts = self._region_embeds = None
             self.graph = None
 
     def set_ip_adapter_scale(self, scale):

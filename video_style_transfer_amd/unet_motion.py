@@ -255,24 +255,30 @@ class ForwardOptions:
     (ip_adapter.ImagePrompt with B * F rows): the image tokens of the IP-Adapter attn2 layers (load_ip_adapter, §20);
     required when they are installed, refused when they are not.  `token_merging` (given as a TokenMerging, a dict of
     its fields or a ratio; §22): the spatial blocks up to its max_downsample merge tokens around attn1 (and the
-    feed-forward)."""
+    feed-forward).  `region_prompts` (region_prompts.RegionPrompts with B * F rows; §24): regional prompts, every
+    spatial attn2 attends to the regions' own text states, blended per pixel by their weight maps, and does not read
+    encoder_hidden_states (whose L and D they must share); not together with a lora_gate."""
     temporal_context: Optional[TemporalContext] = None
     cross_frame: Optional[CrossFrameAttention] = None
     lora_gate: Optional[object] = None
     freeu: Optional[FreeU] = None
     image_prompt: Optional[object] = None
     token_merging: Optional[TokenMerging] = None
+    region_prompts: Optional[object] = None
 
     @classmethod
-    def resolve(cls, model, B: int, F: int, hw, shard=None, x=None, *, use_model_defaults: bool, **given):
+    def resolve(cls, model, B: int, F: int, hw, shard=None, x=None, *, use_model_defaults: bool, enc=None, **given):
         """The options `given` (by field name, in the forms forward() takes) for a call of `model` on B clips of F
         frames (this rank's, under `shard`) of an hw = (h, w) latent; `x`: the call's input, for its device and
         whether it asks for gradients.  `use_model_defaults`: freeu / token_merging not given are what enable_freeu /
-        enable_token_merging set (forward()); else None means off (forward_tokens()).
+        enable_token_merging set (forward()); else None means off (forward_tokens()).  `enc`: the call's
+        encoder_hidden_states, which regional prompts are checked against.
         Every refusal is raised here, before any launch, each check once and in this order: the image prompt against
         the model (and against a lora_gate), cross_frame, the freeu values, token_merging, the clip length against
-        the motion modules' positions, the lora_gate's rows."""
+        the motion modules' positions, the lora_gate's rows, the regional prompts (rows, a table per attention level,
+        the text shape, and against a lora_gate)."""
         from .ip_adapter import check_forward  # (local import: ip_adapter imports the attention processors)
+        from .region_prompts import check_forward as check_regions
         o = cls(**given)  # (an option that does not exist is a TypeError here)
         F_clip = F * (shard.world if shard is not None else 1)
         check_forward(model, o.image_prompt, B * F, o.lora_gate)
@@ -289,6 +295,7 @@ class ForwardOptions:
             check_clip_length(F_clip, model.config.motion_max_seq_length, o.temporal_context)
         if o.lora_gate is not None and o.lora_gate.rows != B * F:
             raise K._lib.VstError(f"lora_gate: {o.lora_gate.rows} rows, expected B * F = {B * F}")
+        check_regions(model, o.region_prompts, B * F, hw, enc, o.lora_gate)
         return dataclasses.replace(o, cross_frame=cross_frame, freeu=freeu, token_merging=token_merging)
 
 
@@ -398,13 +405,26 @@ class BasicTransformerBlock(nn.Module):
                 call = AttnCall(residual=x, lora_u=u, frames=frames, cross_frame=cf, lora_gate=gate)
                 x = self.attn1(n.view(nimg, N, C), _vst=call, **ctx.cross_kwargs).view(-1, C)
             n, u = self.norm2.run_lora(x, input_lora_ops(self.attn2, False, scale))
-            call = AttnCall(residual=x, lora_u=u, lora_gate=gate, image_prompt=opts.image_prompt)
+            call = AttnCall(residual=x, lora_u=u, lora_gate=gate, image_prompt=opts.image_prompt,
+                            regions=self._regions(ctx, nimg, N))
             x = self.attn2(n.view(nimg, N, C), encoder_hidden_states=ctx.enc, _vst=call, **ctx.cross_kwargs).view(-1, C)
             if plan is not None and tm.merge_mlp:
                 m = tm.merge(plan, self.norm3.run(x))
                 return tm.unmerge_add(plan, self.ff.run(m, residual=None), x)
         n = self.norm3.run(x)
         return self.ff.run(n, residual=x)
+
+    @staticmethod
+    def _regions(ctx: FwdCtx, nimg, N):
+        """(the regional prompts, the weight table of this block's level), or None without the option."""
+        rp = ctx.opts.region_prompts
+        if rp is None:
+            return None
+        wts = None if ctx.spatial_hw is None else rp.table(ctx.spatial_hw)
+        if wts is None or wts.shape[0] != nimg * N:
+            raise K._lib.VstError(f"region_prompts: no weight table for a block of {nimg} x {N} tokens at level "
+                                  f"{ctx.spatial_hw}")
+        return rp, wts
 
     def _token_merging(self, x, nimg, N, ctx: FwdCtx):
         """(the option, this block's plan computed from its input x), or (None, None) where the block runs as without
@@ -444,7 +464,7 @@ class Transformer2DModel(nn.Module):
     def run(self, x, nimg, H, W, ctx):
         h = self.norm.run(x, nimg, H * W)
         h = self.proj_in.run(h)
-        if ctx.opts.token_merging is not None:
+        if ctx.opts.token_merging is not None or ctx.opts.region_prompts is not None:
             ctx = dataclasses.replace(ctx, spatial_hw=(H, W))
         for blk in self.transformer_blocks:
             h = blk.run(h, nimg, H * W, ctx)
@@ -807,18 +827,18 @@ class UNetMotionModel(nn.Module):
     # ---- core (NHWC tokens) -----------------------------------------------------------------
     def forward_tokens(self, x, B, F, h, w, emb_silu, enc, cross_kwargs=None, shard=None, fusion_world=None,
                        temporal_context=None, cross_frame=None, lora_gate=None, freeu=None, image_prompt=None,
-                       token_merging=None, options: Optional[ForwardOptions] = None):
+                       token_merging=None, region_prompts=None, options: Optional[ForwardOptions] = None):
         """x: [B*F*h*w, in_channels] bf16 -> noise prediction [B*F*h*w, out_channels] bf16.
         With `shard` (frame_shard.FrameShard), F is this rank's frames of each clip.  `fusion_world` P (default: the
         shard's world size, else 1): take the shape-dependent fusion decisions a P-way frame-sharded rank takes
-        (kernels.fusion_world), so an unsharded forward equals a P-way sharded one bit for bit.  The six option
+        (kernels.fusion_world), so an unsharded forward equals a P-way sharded one bit for bit.  The seven option
         keywords are ForwardOptions' fields, resolved (checked) here; None means off: the enable_freeu /
         enable_token_merging defaults are applied by forward().  Or `options`: a ForwardOptions already resolved for
         this call, in their place; it is taken as it is, nothing is checked again."""
         given = dict(temporal_context=temporal_context, cross_frame=cross_frame, lora_gate=lora_gate, freeu=freeu,
-                     image_prompt=image_prompt, token_merging=token_merging)
+                     image_prompt=image_prompt, token_merging=token_merging, region_prompts=region_prompts)
         if options is None:
-            options = ForwardOptions.resolve(self, B, F, (h, w), shard, x, use_model_defaults=False, **given)
+            options = ForwardOptions.resolve(self, B, F, (h, w), shard, x, use_model_defaults=False, enc=enc, **given)
         elif any(v is not None for v in given.values()):
             raise TypeError("forward_tokens: `options` holds every option of the call; no option keyword beside it")
         return self._run_tokens(x, B, F, h, w, emb_silu, enc, cross_kwargs, shard, fusion_world, options)
@@ -847,18 +867,21 @@ class UNetMotionModel(nn.Module):
     def forward(self, sample, timestep, encoder_hidden_states, timestep_cond=None, attention_mask=None,
                 cross_attention_kwargs=None, added_cond_kwargs=None, return_dict=True, frame_shard=None,
                 fusion_world=None, temporal_context=None, cross_frame=None, lora_gate=None, freeu=None,
-                image_prompt=None, token_merging=None, **kwargs):
+                image_prompt=None, token_merging=None, region_prompts=None, **kwargs):
         """diffusers UNetMotionModel.forward signature (inference_animatediff.py:110-121).  With
         `frame_shard` (frame_shard.FrameShard) `sample` holds this rank's frames of each clip; `fusion_world`: see
-        forward_tokens; `temporal_context`, `cross_frame`, `lora_gate`, `freeu`, `image_prompt`, `token_merging`: the
-        options of this call (ForwardOptions), every one refused before any launch if it cannot be honoured; `freeu`
-        and `token_merging` default to what enable_freeu / enable_token_merging set."""
+        forward_tokens; `temporal_context`, `cross_frame`, `lora_gate`, `freeu`, `image_prompt`, `token_merging`,
+        `region_prompts`: the options of this call (ForwardOptions), every one refused before any launch if it cannot
+        be honoured; `freeu` and `token_merging` default to what enable_freeu / enable_token_merging set.  With
+        regional prompts the spatial attn2 layers attend to the regions' own text states:
+        `encoder_hidden_states` gives only the shape they must share and is not read by them."""
         if not sample.is_cuda:
             raise K._lib.VstError("UNetMotionModel: sample is on CPU; the HIP path has no CPU fallback")
         B, Cin, F, h, w = sample.shape
         opts = ForwardOptions.resolve(self, B, F, (h, w), frame_shard, sample, use_model_defaults=True,
                                       temporal_context=temporal_context, cross_frame=cross_frame, lora_gate=lora_gate,
-                                      freeu=freeu, image_prompt=image_prompt, token_merging=token_merging)
+                                      freeu=freeu, image_prompt=image_prompt, token_merging=token_merging,
+                                      region_prompts=region_prompts, enc=encoder_hidden_states)
         dev = sample.device
         t = timestep if torch.is_tensor(timestep) else torch.tensor([timestep])
         t = t.to(device=dev, dtype=torch.float32).reshape(-1)
